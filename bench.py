@@ -9,7 +9,10 @@ Inputs are resident in HBM before the timed region.  One solve = one trajectory'
 (n_sqp = 10 RTI iterations).  Weak scaling: every rank owns `scenes` x 64 trajectories of each scene's
 (64 x world_size)-trajectory guidance set.
 
-Usage: python bench.py --gpus N --steps K --warmup W
+Usage: python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line (plus DIR/<name>.npy: what the last timed step computed).
+--full adds everything else: the CPU baseline, the oracle parity and FindBestPlanner checks of the launch, the tight-tolerance leg, the
+end-to-end leg and the control-tick latencies.
 N > 1: either under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per GPU; RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* from the environment), or the plain command -- without WORLD_SIZE in the environment bench.py re-executes itself
 under torch.distributed.run on 127.0.0.1 (self_launch below); either way rank 0 prints exactly ONE JSON line.
@@ -409,9 +412,32 @@ def end_to_end_leg(a, dims, sv, batch, t_xinit, t_x0, t_params, dev, n_sets, tra
             "winners_copied_back_equal_device_trajectories": winners_ok}
 
 
-# keys every bench line carries, at every N (the driver's contract + this tier's roofline / cpu_baseline objects)
+# keys every bench line carries, at every N (the driver's contract + this tier's roofline / cpu_baseline objects; cpu_baseline only when it
+# was measured: --full without --no-cpu-baseline)
 REQUIRED_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
                  "config", "roofline", "cpu_baseline", "parity")
+
+DUMP_LIMIT_BYTES = 64 << 20                     # --dump-outputs: at most this much in all
+
+
+def write_outputs(out_dir, arrays, per_traj, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (the integer outputs are exact in it).  Arrays whose first axis is the
+    trajectory (`per_traj` rows) are cut to a fixed, seeded sample of trajectories -- the same rows in every such array, saved as
+    trajectory_index.npy -- when the whole set would exceed `limit` bytes.  Returns {name: shape}."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    fixed = sum(v.size for v in arrays.values() if v.shape[:1] != (per_traj,))
+    row = sum(v.size // per_traj for v in arrays.values() if v.shape[:1] == (per_traj,))
+    if 8 * (fixed + row * per_traj) > limit:
+        n_keep = max(1, (limit // 8 - fixed) // (row + 1))                     # (+1: the index array itself)
+        idx = np.sort(np.random.default_rng(seed).choice(per_traj, n_keep, replace=False))
+        arrays = {k: (v[idx] if v.shape[:1] == (per_traj,) else v) for k, v in arrays.items()}
+        arrays["trajectory_index"] = idx
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(v, dtype=np.float64))
+        shapes[k] = list(v.shape)
+    return shapes
 
 
 def gathered_index_inputs(dist, host_pg, batch, n_traj, rank, world):
@@ -499,7 +525,7 @@ def launcher_selftest(a, world, rank):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     host_pg = dist.new_group(backend="gloo", timeout=datetime.timedelta(minutes=60))
     cpu_base = None
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         dist.barrier(group=host_pg)
         if rank == 0:
             cpu_base = cpu_baseline(1, quick=True)
@@ -535,7 +561,7 @@ def launcher_selftest(a, world, rank):
                                          "inputs_gathered_from_ranks": len(blk), "input_shapes_rank_last": [list(x.shape) for x in blk[-1]]}}}
         if cpu_base is not None:
             out["cpu_baseline"] = cpu_base
-        missing = [k for k in REQUIRED_KEYS if k not in out and not (k == "cpu_baseline" and a.no_cpu_baseline)]
+        missing = [k for k in REQUIRED_KEYS if k not in out and not (k == "cpu_baseline" and cpu_base is None)]
         assert not missing, missing
         print(json.dumps(out))
     dist.barrier(group=host_pg)
@@ -577,6 +603,12 @@ def main():
     ap.add_argument("--parity-check", type=int, default=256,
                     help="trajectories of the timed launch re-solved by the CPU oracle after timing (0 = skip)")
     ap.add_argument("--launcher-selftest", action="store_true", help="exercise the N > 1 launch path on CPU (gloo) and exit; no GPU needed")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: CPU baseline, parity and FindBestPlanner checks against the oracle, the tight-tolerance, end-to-end "
+                         "and control-tick latency legs (the --no-* / --lanes / --*-check options choose among them); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (trajectories, objectives, exit codes, iteration counts, best index per "
+                         "set) as DIR/<name>.npy in float64, at most 64 MB in all (a fixed, seeded sample of the trajectories beyond that); rank 0's share at N > 1")
     a = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -620,7 +652,7 @@ def main():
         n_sets, traj_local = a.scenes, TRAJ_SET
     B = batch["xinit"].shape[0]
     batch_in = None
-    if a.workload == "cfg2" and not a.no_end_to_end and world == 1 and "RANK" not in os.environ and a.scenes >= 32 and not a.latency_mode:
+    if a.full and a.workload == "cfg2" and not a.no_end_to_end and world == 1 and "RANK" not in os.environ and a.scenes >= 32 and not a.latency_mode:
         # scenes on which projectToSafety acts, for the end-to-end leg (generated before the GPU runtime is touched: forked workers)
         batch_in = scenes.make_batch(range(900000, 900016), workers=gen_workers, B=TRAJ_SET, inside_share=0.1, **wl["scene"])
 
@@ -648,7 +680,7 @@ def main():
 
     # ---- reported CPU baseline (rank 0, at every N): before the timed region, while the other ranks wait and the host cores are free -------
     cpu_base = None
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         host_barrier()                                      # every rank's scene generation is done
         if rank == 0:
             cpu_base = cpu_baseline(a.cpu_scenes)
@@ -737,6 +769,13 @@ def main():
     best = t_best.cpu().numpy()
     ok = res["exit_code"] == 1
     full_iter = res["sqp_iter"] == dims.n_sqp
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # what the last timed step hands its caller: every trajectory's solution and status, the best index per set (and, cfg 5, the support counts)
+        arrays = dict(res, best_index=best)
+        if scn is not None:
+            arrays["scenario_support"] = scn["support"].cpu().numpy().T
+        dumped = {"dir": os.path.abspath(a.dump_outputs), "arrays": write_outputs(a.dump_outputs, arrays, B)}
     scenario_info = None
     if scn is not None:
         # the rows the last step built on device are what its solve saw: the parity block below re-solves exactly those
@@ -749,13 +788,13 @@ def main():
 
     # ---- parity spot check of THIS launch against the CPU oracle (outside the timed region; rank 0) ---------------------
     parity = None
-    if rank == 0 and a.parity_check > 0:
+    if rank == 0 and a.full and a.parity_check > 0:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         parity = parity_block(O, wl, batch, res, a.parity_check, {})
         if a.index_check_sets > 0 and not use_dist:
             parity["best_index"] = best_index_block(O, wl, batch, res, best, traj_local, a.index_check_sets)
-    if use_dist and a.index_check_sets > 0:
+    if use_dist and a.full and a.index_check_sets > 0:
         # N > 1 (and N = 1 under the launcher): the selection ran on the GATHERED records -- check it there.  Every rank hands rank 0 the inputs of
         # its first sets over the host group; rank 0 re-solves them with the oracle and applies the reference's rule to the gathered records.
         n_chk = min(n_sets, 16)
@@ -776,7 +815,7 @@ def main():
     # residual on these QPs and two correct implementations disagree on integers in ~0.6 % of the solves, in either Riccati form
     # (profiles/round6_tight_tolerance_study.json names trajectory, iteration, stopping test and both sides' residuals); the 1e-9 numbers stay beside it
     tight = None
-    if rank == 0 and not a.no_tight and not use_dist:
+    if rank == 0 and a.full and not a.no_tight and not use_dist:
         def tight_leg(tol):
             dims_t = solver.default_dims(**wl["dims"], qp_tol=tol)
             st = solver.BatchedSolver(dims_t, B_max=B, device=local_rank)
@@ -801,7 +840,7 @@ def main():
 
     # ---- end to end: per-tick inputs uploaded every step, x0 / halfspace rows built on device, winners copied back ----------
     e2e = None
-    if rank == 0 and not use_dist and a.workload == "cfg2" and not a.no_end_to_end and "guidance_pos" in batch and share_map is not None and not a.latency_mode:
+    if rank == 0 and a.full and not use_dist and a.workload == "cfg2" and not a.no_end_to_end and "guidance_pos" in batch and share_map is not None and not a.latency_mode:
         sv.get_timings()
         sv.set_param_sharing(share_map, copies_not_maintained=True)      # this leg writes a set's shared rows into the base entry only: say so (strict mode)
         e2e = end_to_end_leg(a, dims, sv, batch, t_xinit, t_x0, t_params, dev, n_sets, traj_local, res, best, batch_in)
@@ -811,7 +850,7 @@ def main():
     lat5 = None
     lat5_n30 = None
     lanes = None
-    if rank == 0 and a.lanes and not use_dist and not dims.cost_model and not dims.row_model and solver.has_lane_kernels():
+    if rank == 0 and a.full and a.lanes and not use_dist and not dims.cost_model and not dims.row_model and solver.has_lane_kernels():
         # the lane-per-trajectory variant (tmpc_set_throughput_mode) on the same resident batch: the measured alternative design
         sv.set_throughput_mode(True)
         sv.solve(); sv.solve(sync=False)
@@ -824,7 +863,7 @@ def main():
                  "exit_code_mismatch_vs_default": int((rl["exit_code"] != res["exit_code"]).sum()),
                  "ipm_iter_mismatch_vs_default": int((rl["qp_iter_total"][okl] != res["qp_iter_total"][okl]).sum()),
                  "max_abs_traj_diff_vs_default": float(np.abs(rl["xtraj"][okl] - res["xtraj"][okl]).max()) if okl.any() else None}
-    if rank == 0 and a.latency_reps > 0 and a.workload == "cfg2":
+    if rank == 0 and a.full and a.latency_reps > 0 and a.workload == "cfg2":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         VARIANT = {1: "latency 1 (two waves per trajectory, sequential Riccati recursion)",
@@ -958,10 +997,12 @@ def main():
             "latency_b5_n30": lat5_n30,
             "best_index_sample": best[:4].tolist(),
             "scenario_pipeline": scenario_info,
+            "full": bool(a.full),
+            "dumped_outputs": dumped,
         }
         if cpu_base is not None:                                      # reported baseline: rank 0's host cores, measured before the timed region (at every N)
             out["cpu_baseline"] = cpu_base
-        missing = [k for k in REQUIRED_KEYS if k not in out and not (k == "cpu_baseline" and a.no_cpu_baseline)]
+        missing = [k for k in REQUIRED_KEYS if k not in out and not (k == "cpu_baseline" and cpu_base is None)]
         assert not missing, missing
         print(json.dumps(out))
     sv.close()

@@ -27,7 +27,7 @@ def test_self_launch_command_is_the_drivers_form():
 
 
 def test_plain_command_at_two_ranks_prints_one_json_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launcher-selftest"], capture_output=True, text=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launcher-selftest", "--full"], capture_output=True, text=True,
                          timeout=300, env=_clean_env(), cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -24,3 +24,28 @@ def test_flops_per_solve_is_the_survey_model():
 def test_usable_cpus_is_positive_and_bounded_by_the_visible_cpus():
     n = bench.usable_cpus()
     assert 1 <= n <= (os.cpu_count() or 1)
+
+
+def test_write_outputs_float64_whole_or_one_seeded_sample(tmp_path):
+    """--dump-outputs: float64 files; under the cap every array whole, over it the same seeded sample of trajectories in every per-trajectory
+    array (plus trajectory_index) -- the same files from run to run."""
+    import numpy as np
+    B = 1000
+    arrays = {"xtraj": np.arange(B * 6, dtype=np.float64).reshape(B, 3, 2), "exit_code": np.arange(B, dtype=np.int32) % 5,
+              "best_index": np.array([3, -1], np.int32)}
+    shapes = bench.write_outputs(str(tmp_path / "whole"), arrays, B)
+    assert shapes == {"xtraj": [B, 3, 2], "exit_code": [B], "best_index": [2]}
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    limit = 8 * 2000                                            # room for 2000 float64 values: 7 per trajectory kept -> 285 trajectories
+    for run in ("a", "b"):
+        shapes = bench.write_outputs(str(tmp_path / run), arrays, B, limit=limit)
+        assert sum(int(np.prod(s)) for s in shapes.values()) * 8 <= limit
+    idx = np.load(tmp_path / "a" / "trajectory_index.npy").astype(int)
+    assert 0 < len(idx) < B and np.all(np.diff(idx) > 0)
+    for k in ("xtraj", "exit_code", "best_index", "trajectory_index"):
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "xtraj.npy"), arrays["xtraj"][idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "best_index.npy"), arrays["best_index"])

@@ -6,7 +6,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}; export TMPDIR=/tmp; O=gpurun_out/round5_p_dpa
 run() { # name, env value ('' = the model's choice), bench args...
   local name=$1 v=$2; shift 2
   ( if [ -n "$v" ]; then export TMPC_EXP_DPAD=$v; fi
-    python bench.py "$@" --no-cpu-baseline --no-tight --no-end-to-end --parity-check 64 --index-check-sets 0 2>/dev/null | python -c "
+    python bench.py --full "$@" --no-cpu-baseline --no-tight --no-end-to-end --parity-check 64 --index-check-sets 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 lat=d.get('latency_b64') or {}

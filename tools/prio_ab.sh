@@ -17,7 +17,7 @@ if [ "$1" != "measure" ]; then
   ls -la build/exp/libtmpc_hip_prio*.so; exit 0
 fi
 export TMPDIR=/tmp
-BENCH="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --latency-reps 0 --no-tight --no-end-to-end --parity-check 64 --index-check-sets 0 --gen-workers 1 --scene-cache /tmp/tmpc_bench_scenes"
+BENCH="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --latency-reps 0 --no-tight --no-end-to-end --parity-check 64 --index-check-sets 0 --gen-workers 1 --scene-cache /tmp/tmpc_bench_scenes"
 for st in prio1e-32 prio1e-28 prio1e-24 prio1e-20; do
   export TMPC_HIP_LIBRARY=$R/build/exp/libtmpc_hip_$st.so
   $BENCH 2>/dev/null | python -c "

@@ -19,7 +19,7 @@ fi
 export TMPDIR=/tmp
 for st in default $STRATS; do
   if [ "$st" != default ]; then export TMPC_HIP_LIBRARY=$R/build/exp/libtmpc_hip_sched_$st.so; else unset TMPC_HIP_LIBRARY; fi
-  python bench.py --steps 10 --warmup 3 --no-cpu-baseline --latency-reps 0 --no-tight --no-end-to-end --parity-check 64 --index-check-sets 0 --gen-workers 1 --scene-cache /tmp/tmpc_bench_scenes 2>/dev/null | python -c "
+  python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --latency-reps 0 --no-tight --no-end-to-end --parity-check 64 --index-check-sets 0 --gen-workers 1 --scene-cache /tmp/tmpc_bench_scenes 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); p=d['parity']
 print(json.dumps({'strategy':'$st','value':d['value'],'kernel_ms_avg':d['roofline']['kernel_ms_avg'],'parity':[p['exit_code_mismatch'],p['sqp_iter_mismatch'],p['ipm_iter_mismatch'],p['parity_max_rel']]}))"
