@@ -242,7 +242,10 @@ int tmpc_result_device_ptrs(tmpc_handle *h, void **d_pobj, void **d_exit_code);
  * tmpc_select_best_records by making that stream the collective's current stream. */
 int tmpc_get_stream(tmpc_handle *h, void **stream);
 /* Which solve kernel this handle dispatches and how it is launched, as a short text for logs and benchmark records (kernel family,
- * trajectories per workgroup, LDS bytes per workgroup, resident workgroups of a persistent launch).  Returns the length written. */
+ * trajectories per workgroup, LDS bytes per workgroup, resident workgroups of a persistent launch), ending in the template instantiation of
+ * every kernel slot the handle fills: "; kernels: default=<name>[, small=<name>][, cp2=<name>][, lat1=<name>][, lat2=<name>][, lat3=<name>]"
+ * with <name> "fast<NLIN,MM,LPS,NTH,TEAM,CM>", "compact<NLIN,MM,LPS,NTH,CM>" or "generic<CM>" (small: the fast kernel of a compact shape for
+ * launches it holds resident; cp2: the two-wave compact kernel for larger launches; latN: tmpc_set_latency_mode(h, N)).  Returns the length written. */
 int tmpc_kernel_info(const tmpc_handle *h, char *buf, int32_t capacity);
 
 /* ---- multi-GPU sharding: a scene's trajectories are split over ranks; after the solve every rank
@@ -384,7 +387,9 @@ int tmpc_debug_get_x0(tmpc_handle *h, double *x0, double *xinit);
 int tmpc_debug_get_params(tmpc_handle *h, double *params);
 
 /* Mean shader-clock cycles per phase over the batch (one extra instrumented solve).  cycles[10]:
- * linearise, residuals, barrier Hessian, Riccati factor, rhs build, Riccati solve, row passes, update, final, total. */
+ * linearise, residuals, barrier Hessian, Riccati factor, rhs build, Riccati solve, row passes, update, final, total.
+ * Runs the instrumented twin of the instantiation tmpc_solve would run for the current batch and latency mode (a compact kernel: the fast kernel
+ * of its shape, bitwise the same results) and leaves that solve's results in the handle; TMPC_ERR_INVALID where no such twin exists. */
 int tmpc_debug_profile(tmpc_handle *h, int64_t *cycles, int32_t n_phases);
 
 /* The LDS bank-conflict model behind the compact kernels' layout padding (no handle, no GPU): the passes the row passes' coefficient loads

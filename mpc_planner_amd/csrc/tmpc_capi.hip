@@ -11,23 +11,25 @@
 #if !defined(TMPC_GENERATED_STAGE) && !defined(TMPC_SINGLE_TU)
 TMPC_ALL_INSTANCES(EXT)
 extern template __global__ void tmpc::tmpc_solve_fast_kernel<8, 8, 6, 128, true, tmpc::ScanSolo>(TMPC_KARGS);
+extern template __global__ void tmpc::tmpc_solve_fast_kernel<8, 8, 2, 64, true>(TMPC_KARGS);
 #endif
 #include "tmpc_aux_kernels.hpp"
 // The lane-per-trajectory kernel family (tmpc_lanes.hip, tmpc_set_throughput_mode) is an OPTIONAL part of the library since round 5: it loses to
 // the wave kernels on every shape measured and is kept for its persistent-state protocol on arbitrary shapes.  -DTMPC_WITH_LANES links
 // it (__graft_entry__.build(with_lanes=True) / TMPC_BUILD_LANES=1); without it tmpc_set_throughput_mode reports that the build has no such kernels.
-#ifdef TMPC_WITH_LANES
-#include "tmpc_lanes_api.hpp"
-#else
 // Lab switches (kernel selection overrides for A/B measurements and for tests that have to reach one particular kernel family): environment variables
 // TMPC_* read when a handle is created.  They exist ONLY in a library built with -DTMPC_LAB_SWITCHES (mpc_planner_amd/libtmpc_hip_lab.so, which
 // __graft_entry__.build() links from the same kernel objects; tools/build_compact_variants.sh): the product library never reads the environment -- what a
-// drop-in does depends on the C-ABI calls alone (round-5 verdict, next-8).  INTEGRATION.md section 7 lists them.
+// drop-in does depends on the C-ABI calls alone (round-5 verdict, next-8).  INTEGRATION.md section 7 lists them.  (Defined for every build, the lane
+// family's included: tests/test_dispatch_table.py compiles this unit with and without -DTMPC_WITH_LANES.)
 #ifdef TMPC_LAB_SWITCHES
 static inline const char *lab_env(const char *name) { return getenv(name); }
 #else
 static inline const char *lab_env(const char *) { return nullptr; }
 #endif
+#ifdef TMPC_WITH_LANES
+#include "tmpc_lanes_api.hpp"
+#else
 namespace tmpc {
 namespace lanes {
 struct Context;
@@ -55,8 +57,20 @@ typedef void (*SolveKernel)(Dims, int, const double *, const double *, const dou
 // per lane ((8,8) at 2 lanes/stage for N > 21, (12,12) at 2 lanes/stage) therefore use the generic kernel for now.  The library is
 // built with -mllvm -disable-machine-licm: hoisted constant materialisations were what pushed (12,12,3) into scratch.
 // prof: the instrumented instantiation (tmpc_debug_profile) instead of the production one.
-#define TMPC_FAST(...) (prof ? (SolveKernel)tmpc_solve_fast_kernel<__VA_ARGS__, true> : (SolveKernel)tmpc_solve_fast_kernel<__VA_ARGS__, false>)
-static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof)
+// Every instantiation a pick_*_kernel function returns is written through one of the macros below, which also store the instantiation's name in
+// *name (when given): "fast<NLIN,MM,LPS,NTH,TEAM,CM>" / "compact<NLIN,MM,LPS,NTH,CM>", the template arguments as written (tmpc_kernel_info reports
+// them; tests/test_dispatch_table.py reads the same macro calls from this file and requires a test case for each name).
+//   TMPC_FAST(NLIN, MM, LPS, NTH)        MPCC + ellipsoid rows (TEAM = Solo, CM = 0), production or profiled twin by `prof`
+//   TMPC_FASTP(NLIN, MM, LPS, NTH, TEAM) another TEAM (CM = 0), production or profiled twin by `prof`
+//   TMPC_FASTX(NLIN, MM, LPS, NTH, TEAM, CM) production only (no profiled twin: the caller returns nullptr for `prof` first)
+//   TMPC_CP(NLIN, MM, LPS, CM) / TMPC_CP2(NLIN, MM, LPS, CM)   compact one-wave / two-wave kernels (set *lay)
+#define TMPC_KNAME(s) (name ? (void)(*name = (s)) : (void)0)
+#define TMPC_FAST(a, b, c, t) (TMPC_KNAME("fast<" #a "," #b "," #c "," #t ",Solo,0>"), \
+                               prof ? (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, true> : (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, false>)
+#define TMPC_FASTP(a, b, c, t, team) (TMPC_KNAME("fast<" #a "," #b "," #c "," #t "," #team ",0>"), \
+                                      prof ? (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, true, team> : (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, false, team>)
+#define TMPC_FASTX(a, b, c, t, team, m) (TMPC_KNAME("fast<" #a "," #b "," #c "," #t "," #team "," #m ">"), (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, false, team, m>)
+static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof, const char **name = nullptr)
 {
     *threads = NT;
     if (lab_env("TMPC_FORCE_GENERIC")) return nullptr;
@@ -70,9 +84,9 @@ static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof)
         const int nrc = d.n_up + d.M + 14;
         if (lps != 3 && 4 * d.N <= 128 && d.n_up == 20 && d.M == 8 && !lab_env("TMPC_NO_TWO_WAVE")) {
             *threads = 128;
-            return (SolveKernel)tmpc_solve_fast_kernel<20, 8, 4, 128, false, Solo, 1>;
+            return TMPC_FASTX(20, 8, 4, 128, Solo, 1);
         }
-        if (lps == 3 && nrc <= 3 * 13) return (SolveKernel)tmpc_solve_fast_kernel<-1, 13, 3, 64, false, Solo, 1>;
+        if (lps == 3 && nrc <= 3 * 13) return TMPC_FASTX(-1, 13, 3, 64, Solo, 1);
         return nullptr;
     }
     if (d.row_model == 1) {
@@ -83,15 +97,15 @@ static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof)
         // mpc_planner_jackal's default (generate_jackal_solver.py:53-73: N = 30, 5 + 5 rows) on ONE wave at two lanes per stage (round 6): twelve rows per lane
         // fit the registers, and eight one-wave trajectories per CU keep eight waves busy where four two-wave ones idle a wave through every Riccati sweep --
         // saturated +27 % (585 -> 741 k solves/s).  Its small-launch twin below, the compact kernel in pick_compact_kernel; ticks: latency modes 2 / 3.
-        if (lps == 2 && d.n_up == 5 && d.M == 5 && !lab_env("TMPC_NO_ONE_WAVE_N30")) return (SolveKernel)tmpc_solve_fast_kernel<5, 5, 2, 64, false, Solo, 2>;
+        if (lps == 2 && d.n_up == 5 && d.M == 5 && !lab_env("TMPC_NO_ONE_WAVE_N30")) return TMPC_FASTX(5, 5, 2, 64, Solo, 2);
         if (lps != 3 && 4 * d.N <= 128 && !lab_env("TMPC_NO_TWO_WAVE")) {
             *threads = 128;
-            if (d.n_up == 5 && d.M == 5) return (SolveKernel)tmpc_solve_fast_kernel<5, 5, 4, 128, false, Solo, 2>;     // mpc_planner_jackal's default (generate_jackal_solver.py:53-73), tuned
-            if (nrg <= 4 * 6) return (SolveKernel)tmpc_solve_fast_kernel<-1, 6, 4, 128, false, Solo, 2>;
-            if (nrg <= 4 * 12) return (SolveKernel)tmpc_solve_fast_kernel<-1, 12, 4, 128, false, Solo, 2>;
+            if (d.n_up == 5 && d.M == 5) return TMPC_FASTX(5, 5, 4, 128, Solo, 2);     // mpc_planner_jackal's default (generate_jackal_solver.py:53-73), tuned
+            if (nrg <= 4 * 6) return TMPC_FASTX(-1, 6, 4, 128, Solo, 2);
+            if (nrg <= 4 * 12) return TMPC_FASTX(-1, 12, 4, 128, Solo, 2);
             *threads = NT;
         }
-        if (lps == 3 && nrg <= 3 * 13) return (SolveKernel)tmpc_solve_fast_kernel<-1, 13, 3, 64, false, Solo, 2>;
+        if (lps == 3 && nrg <= 3 * 13) return TMPC_FASTX(-1, 13, 3, 64, Solo, 2);
         return nullptr;
     }
 #endif
@@ -108,8 +122,9 @@ static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof)
 #else
     const int nr = d.n_up + d.M + 14;                    // interior-point rows per stage
     // the jackalsimulator T-MPC stack at the horizon it ships with (8 + 8 rows, N = 30; settings.yaml) on ONE wave at two lanes per stage (round 6, like
-    // mpc_planner_jackal's default above: fifteen rows per lane still fit the registers); its compact twin in pick_compact_kernel
-    if (lps == 2 && d.n_up == 8 && d.M == 8 && !prof && !lab_env("TMPC_NO_ONE_WAVE_N30")) return (SolveKernel)tmpc_solve_fast_kernel<8, 8, 2, 64, false, Solo, 0>;
+    // mpc_planner_jackal's default above: fifteen rows per lane still fit the registers); its compact twin in pick_compact_kernel, its profiled twin
+    // in tmpc_solve.hip (TMPC_TU_PROF)
+    if (lps == 2 && d.n_up == 8 && d.M == 8 && !lab_env("TMPC_NO_ONE_WAVE_N30")) return TMPC_FAST(8, 8, 2, 64);
     if (lps != 3 && 4 * d.N <= 128 && !lab_env("TMPC_NO_TWO_WAVE")) {
         // two waves per trajectory, 4 lanes per stage (22 <= N <= 32: the reference's default N = 30 and BASELINE cfg 3)
         SolveKernel k2 = nullptr;
@@ -141,22 +156,22 @@ static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof)
 }
 // Square-root form of the Riccati recursion (tmpc_dims.riccati_form = TMPC_RICCATI_SQUARE_ROOT; csrc/tmpc_riccati.hpp SQ): run-time-shape fast kernels only
 // -- a comparison aid (HPIPM's default recursion) with one instantiation per kernel family member that the BASELINE shapes need, not a throughput path.
-static SolveKernel pick_sqrt_kernel(const Dims &d, int *threads)
+static SolveKernel pick_sqrt_kernel(const Dims &d, int *threads, const char **name = nullptr)
 {
     *threads = NT;
 #ifndef TMPC_GENERATED_STAGE
     const int nr = d.n_up + d.M + 14, sm = stage_model(d);
     if (3 * d.N <= NT) {
-        if (sm == 0 && nr <= 3 * 13) return (SolveKernel)tmpc_solve_fast_kernel<-1, 13, 3, 64, false, SoloSqrt>;
+        if (sm == 0 && nr <= 3 * 13) return TMPC_FASTX(-1, 13, 3, 64, SoloSqrt, 0);
         return nullptr;
     }
     if (4 * d.N <= 128 && nr <= 4 * 12) {
         *threads = 128;
-        if (sm == 0) return (SolveKernel)tmpc_solve_fast_kernel<-1, 12, 4, 128, false, SoloSqrt>;
-        if (sm == 1 && d.n_up == 20 && d.M == 8) return (SolveKernel)tmpc_solve_fast_kernel<20, 8, 4, 128, false, SoloSqrt, 1>;      // cfg 3 as named (CA-MPC)
+        if (sm == 0) return TMPC_FASTX(-1, 12, 4, 128, SoloSqrt, 0);
+        if (sm == 1 && d.n_up == 20 && d.M == 8) return TMPC_FASTX(20, 8, 4, 128, SoloSqrt, 1);      // cfg 3 as named (CA-MPC)
     }
 #endif
-    (void)d;
+    (void)d; (void)name;
     return nullptr;
 }
 // Compact variant (tmpc_fast.hpp: tmpc_solve_compact_kernel): two waves per SIMD, eight trajectories per CU, persistent
@@ -167,31 +182,31 @@ static SolveKernel pick_sqrt_kernel(const Dims &d, int *threads)
 // (168 B) and is not registered.
 // *lay: the instantiation's Hh layout (compact_layout, tmpc_fast.hpp) -- evaluated on the template arguments
 // where they are written, so that the host's LDS size and the kernel's layout cannot disagree
-#define TMPC_CP(a, b, c) (*lay = compact_layout(a, b, 64), (SolveKernel)tmpc_solve_compact_kernel<a, b, c, false>)
-#define TMPC_CP2(a, b, c, m) (*lay = compact_layout(a, b, 128), (SolveKernel)tmpc_solve_compact_kernel<a, b, c, false, 128, m>)
-static SolveKernel pick_compact_kernel(const Dims &d, bool prof, int *lay)
+#define TMPC_CP(a, b, c, m) (*lay = compact_layout(a, b, 64), TMPC_KNAME("compact<" #a "," #b "," #c ",64," #m ">"), (SolveKernel)tmpc_solve_compact_kernel<a, b, c, false, 64, m>)
+#define TMPC_CP2(a, b, c, m) (*lay = compact_layout(a, b, 128), TMPC_KNAME("compact<" #a "," #b "," #c ",128," #m ">"), (SolveKernel)tmpc_solve_compact_kernel<a, b, c, false, 128, m>)
+static SolveKernel pick_compact_kernel(const Dims &d, bool prof, int *lay, const char **name = nullptr)
 {
     *lay = 1;
 #ifndef TMPC_GENERATED_STAGE
     if (!lab_env("TMPC_FORCE_GENERIC") && !lab_env("TMPC_NO_COMPACT") && !lab_env("TMPC_NO_ONE_WAVE_N30") && !prof && 2 * d.N <= NT && 3 * d.N > NT) {
         // 22 <= N <= 32 on one wave, two lanes per stage (pick_fast_kernel): mpc_planner_jackal's default, the jackalsimulator stack
-        if (stage_model(d) == 2 && d.n_up == 5 && d.M == 5) { *lay = compact_layout(5, 5, 64); return (SolveKernel)tmpc_solve_compact_kernel<5, 5, 2, false, 64, 2>; }
-        if (stage_model(d) == 0 && d.n_up == 8 && d.M == 8) { *lay = compact_layout(8, 8, 64); return (SolveKernel)tmpc_solve_compact_kernel<8, 8, 2, false>; }
+        if (stage_model(d) == 2 && d.n_up == 5 && d.M == 5) return TMPC_CP(5, 5, 2, 2);
+        if (stage_model(d) == 0 && d.n_up == 8 && d.M == 8) return TMPC_CP(8, 8, 2, 0);
     }
     if (lab_env("TMPC_FORCE_GENERIC") || lab_env("TMPC_NO_COMPACT") || prof || d.N > 20 || (stage_model(d) != 0 && stage_model(d) != 2)) return nullptr;
     if (stage_model(d) == 2) {                       // Gaussian chance-constraint rows (round 6): the run-time-shape instantiation with up to ten rows per lane
-        if (d.n_up + d.M + 14 <= 3 * 10) { *lay = compact_layout(-1, 10, 64); return (SolveKernel)tmpc_solve_compact_kernel<-1, 10, 3, false, 64, 2>; }
+        if (d.n_up + d.M + 14 <= 3 * 10) return TMPC_CP(-1, 10, 3, 2);
         return nullptr;
     }
     const int nr = d.n_up + d.M + 14;                    // interior-point rows per stage
-    if (d.n_up == 8 && d.M == 8) return TMPC_CP(8, 8, 3);
-    if (d.n_up == 0 && d.M == 4) return TMPC_CP(0, 4, 3);
-    if (d.n_up == 12 && d.M == 12) return TMPC_CP(12, 12, 3);
-    if (d.n_up == 24 && d.M == 0) return TMPC_CP(24, 0, 3);
-    if (nr <= 3 * 7) return TMPC_CP(-1, 7, 3);       // runtime-shape instantiations
-    if (nr <= 3 * 10) return TMPC_CP(-1, 10, 3);
+    if (d.n_up == 8 && d.M == 8) return TMPC_CP(8, 8, 3, 0);
+    if (d.n_up == 0 && d.M == 4) return TMPC_CP(0, 4, 3, 0);
+    if (d.n_up == 12 && d.M == 12) return TMPC_CP(12, 12, 3, 0);
+    if (d.n_up == 24 && d.M == 0) return TMPC_CP(24, 0, 3, 0);
+    if (nr <= 3 * 7) return TMPC_CP(-1, 7, 3, 0);       // runtime-shape instantiations
+    if (nr <= 3 * 10) return TMPC_CP(-1, 10, 3, 0);
 #endif
-    (void)d; (void)prof;
+    (void)d; (void)prof; (void)name;
     return nullptr;
 }
 // Two-wave compact variant (round 4: 22 <= N <= 32, four lanes per stage -- the reference's N = 30 defaults, cfg 3): the same kernel with
@@ -199,7 +214,7 @@ static SolveKernel pick_compact_kernel(const Dims &d, bool prof, int *lay)
 // fast two-wave kernel (57-70 KB of LDS) holds two.  Bitwise the same results; a trajectory takes longer on it (NLP data in the global
 // workspace, the linearisation on one of the two waves), so launch_solve uses it only for launches that the fast kernel could not hold
 // resident at once (more than two trajectories per CU).  The runtime-shape instantiation with 12 rows per lane spills (144 B): not registered.
-static SolveKernel pick_compact2_kernel(const Dims &d, int *lay, int *threads)
+static SolveKernel pick_compact2_kernel(const Dims &d, int *lay, int *threads, const char **name = nullptr)
 {
     *lay = 1; *threads = 128;
 #ifndef TMPC_GENERATED_STAGE
@@ -218,7 +233,7 @@ static SolveKernel pick_compact2_kernel(const Dims &d, int *lay, int *threads)
     if (nr <= 4 * 6) return TMPC_CP2(-1, 6, 4, 0);
     if (nr <= 4 * 9) return TMPC_CP2(-1, 9, 4, 0);
 #endif
-    (void)d;
+    (void)d; (void)name;
     return nullptr;
 }
 // Latency variant (tmpc_set_latency_mode): two waves per trajectory at 6 lanes per stage, built for two waves per SIMD
@@ -226,13 +241,13 @@ static SolveKernel pick_compact2_kernel(const Dims &d, int *lay, int *threads)
 // -8 % kernel time on a 64-trajectory control tick; on a saturated GPU the one-wave kernel is as fast or faster, which is
 // why it stays the default.  The variant is chosen by the caller, never by the batch size: a trajectory's result does
 // not depend on what else is in the launch.
-static SolveKernel pick_latency_kernel(const Dims &d, bool prof)
+static SolveKernel pick_latency_kernel(const Dims &d, bool prof, const char **name = nullptr)
 {
 #ifndef TMPC_GENERATED_STAGE
     if (lab_env("TMPC_FORCE_GENERIC") || lab_env("TMPC_NO_TWO_WAVE") || d.N > 2 * (64 / 6) || stage_model(d) != 0) return nullptr;
     if (d.n_up == 8 && d.M == 8) return TMPC_FAST(8, 8, 6, 128);
 #endif
-    (void)d; (void)prof;
+    (void)d; (void)prof; (void)name;
     return nullptr;
 }
 // Latency variant 2 (tmpc_set_latency_mode(h, 2)): one wave per trajectory like the fast kernels, the interior-point Newton systems
@@ -240,30 +255,32 @@ static SolveKernel pick_latency_kernel(const Dims &d, bool prof)
 // tick gives it anyway: built for one wave per SIMD (all 512 registers, 73 KB of LDS).  Another factorisation of the same systems:
 // steps agree with the recursion's to rounding (~1e-6 of a step on ill-conditioned late iterations, like the recursion itself
 // against an exact solve), so iteration counts can differ by one where a residual sits at the tolerance -- the caller opts in.
-static SolveKernel pick_scan_kernel(const Dims &d, int *threads, int *sl)
+// prof: the profiled twin (registered for the cfg-2 shape (8, 8) on two waves only).
+static SolveKernel pick_scan_kernel(const Dims &d, int *threads, int *sl, bool prof = false, const char **name = nullptr)
 {
     *sl = 3;
 #ifndef TMPC_GENERATED_STAGE
     if (lab_env("TMPC_FORCE_GENERIC") || d.N > 31 || d.N < 2 || (stage_model(d) != 0 && stage_model(d) != 2)) return nullptr;
     const bool gauss = stage_model(d) == 2;                      // Gaussian chance-constraint rows (mpc_planner_jackal's default stack): the run-time-shape instantiations, CM = 2
     if (d.N > 20) {                                              // 21 <= N <= 31 (cfg 3, the reference's N = 30 defaults): two lanes per stage in the
-        if (d.n_up + d.M + 14 > 4 * 12) return nullptr;          // Newton solve, the runtime-shape two-wave kernel (4 lanes per stage, up to 34 rows) around it
+        if (d.n_up + d.M + 14 > 4 * 12 || prof) return nullptr;  // Newton solve, the runtime-shape two-wave kernel (4 lanes per stage, up to 34 rows) around it
         *threads = 128; *sl = 2;
-        return gauss ? (SolveKernel)tmpc_solve_fast_kernel<-1, 12, 4, 128, false, ScanSoloT<2>, 2> : (SolveKernel)tmpc_solve_fast_kernel<-1, 12, 4, 128, false, ScanSoloT<2>>;
+        return gauss ? TMPC_FASTX(-1, 12, 4, 128, ScanSoloT<2>, 2) : TMPC_FASTX(-1, 12, 4, 128, ScanSoloT<2>, 0);
     }
     if (gauss) {
-        if (d.N <= 2 * (64 / 6) && d.n_up + d.M + 14 <= 6 * 9) { *threads = 128; return (SolveKernel)tmpc_solve_fast_kernel<-1, 9, 6, 128, false, ScanSolo, 2>; }
+        if (!prof && d.N <= 2 * (64 / 6) && d.n_up + d.M + 14 <= 6 * 9) { *threads = 128; return TMPC_FASTX(-1, 9, 6, 128, ScanSolo, 2); }
         return nullptr;
     }
     const char *w = lab_env("TMPC_SCAN_WAVES");               // A/B: "1" = one wave per trajectory
-    if (d.n_up == 8 && d.M == 8 && d.N <= 2 * (64 / 6) && !(w && atoi(w) == 1)) { *threads = 128; return (SolveKernel)tmpc_solve_fast_kernel<8, 8, 6, 128, false, ScanSolo>; }
-    if (d.n_up == 8 && d.M == 8) { *threads = 64; return (SolveKernel)tmpc_solve_fast_kernel<8, 8, 3, 64, false, ScanSolo>; }
+    if (d.n_up == 8 && d.M == 8 && d.N <= 2 * (64 / 6) && !(w && atoi(w) == 1)) { *threads = 128; return TMPC_FASTP(8, 8, 6, 128, ScanSolo); }
+    if (prof) return nullptr;
+    if (d.n_up == 8 && d.M == 8) { *threads = 64; return TMPC_FASTX(8, 8, 3, 64, ScanSolo, 0); }
     if (d.N <= 2 * (64 / 6) && d.n_up + d.M + 14 <= 6 * 9) {     // every other row mix of the one-wave shapes (cfg 1, cfg 4, cfg 5, ...): runtime row counts, two waves
         *threads = 128;
-        return (SolveKernel)tmpc_solve_fast_kernel<-1, 9, 6, 128, false, ScanSolo>;
+        return TMPC_FASTX(-1, 9, 6, 128, ScanSolo, 0);
     }
 #endif
-    (void)d; (void)threads;
+    (void)d; (void)threads; (void)prof; (void)name;
     return nullptr;
 }
 // Latency variant 3 (tmpc_set_latency_mode(h, 3), round 6): FOUR waves per trajectory -- a control tick of a few planners leaves a whole CU (four SIMDs,
@@ -272,7 +289,7 @@ static SolveKernel pick_scan_kernel(const Dims &d, int *threads, int *sl)
 // factorisation (the stage phase: one column per lane instead of four; level 0 of the cyclic reduction: one instead of two) use all 256 lanes
 // (csrc/tmpc_scan.hpp factor4).  Same algorithm as variant 2 (sums associate differently: rounding level).  N <= 20, hand-written MPCC stages.
 // `ab`: TMPC_QUAD_AB=1 in a lab build picks the twin whose factorisation stays on one wave (A/B of the factorisation split alone).
-static SolveKernel pick_quad_kernel(const Dims &d, bool prof, bool ab, int *sl = nullptr)
+static SolveKernel pick_quad_kernel(const Dims &d, bool prof, bool ab, int *sl = nullptr, const char **name = nullptr)
 {
     if (sl) *sl = 3;
 #ifndef TMPC_GENERATED_STAGE
@@ -281,20 +298,17 @@ static SolveKernel pick_quad_kernel(const Dims &d, bool prof, bool ab, int *sl =
         // every stage model (the four-wave linearisation regularises a coupled W -- curvature-aware cost -- on wave 0)
         if (sl) *sl = 2;
         const int sm = stage_model(d);
-        return sm == 0 ? (SolveKernel)tmpc_solve_fast_kernel<-1, 6, 8, 256, false, ScanQuadT<2>, 0>
-             : sm == 1 ? (SolveKernel)tmpc_solve_fast_kernel<-1, 6, 8, 256, false, ScanQuadT<2>, 1>
-             : sm == 2 ? (SolveKernel)tmpc_solve_fast_kernel<-1, 6, 8, 256, false, ScanQuadT<2>, 2>
-             : sm == 3 ? (SolveKernel)tmpc_solve_fast_kernel<-1, 6, 8, 256, false, ScanQuadT<2>, 3> : nullptr;
+        return sm == 0 ? TMPC_FASTX(-1, 6, 8, 256, ScanQuadT<2>, 0)
+             : sm == 1 ? TMPC_FASTX(-1, 6, 8, 256, ScanQuadT<2>, 1)
+             : sm == 2 ? TMPC_FASTX(-1, 6, 8, 256, ScanQuadT<2>, 2)
+             : sm == 3 ? TMPC_FASTX(-1, 6, 8, 256, ScanQuadT<2>, 3) : nullptr;
     }
     if (d.N > 20 || d.N < 2 || (stage_model(d) != 0 && stage_model(d) != 2)) return nullptr;
-    if (stage_model(d) == 2) return (!prof && d.n_up + d.M + 14 <= 12 * 4) ? (SolveKernel)tmpc_solve_fast_kernel<-1, 4, 12, 256, false, ScanQuad, 2> : nullptr;      // Gaussian rows
-    if (d.n_up == 8 && d.M == 8) {
-        if (prof) return (SolveKernel)tmpc_solve_fast_kernel<8, 8, 12, 256, true, ScanQuad>;
-        return ab ? (SolveKernel)tmpc_solve_fast_kernel<8, 8, 12, 256, false, ScanSolo> : (SolveKernel)tmpc_solve_fast_kernel<8, 8, 12, 256, false, ScanQuad>;
-    }
-    if (!prof && d.n_up + d.M + 14 <= 12 * 4) return (SolveKernel)tmpc_solve_fast_kernel<-1, 4, 12, 256, false, ScanQuad>;      // cfg 1, cfg 4, cfg 5, any row mix up to 34 rows
+    if (stage_model(d) == 2) return (!prof && d.n_up + d.M + 14 <= 12 * 4) ? TMPC_FASTX(-1, 4, 12, 256, ScanQuad, 2) : nullptr;      // Gaussian rows
+    if (d.n_up == 8 && d.M == 8) return (ab && !prof) ? TMPC_FASTX(8, 8, 12, 256, ScanSolo, 0) : TMPC_FASTP(8, 8, 12, 256, ScanQuad);    // (prof: the twin of ScanQuad)
+    if (!prof && d.n_up + d.M + 14 <= 12 * 4) return TMPC_FASTX(-1, 4, 12, 256, ScanQuad, 0);      // cfg 1, cfg 4, cfg 5, any row mix up to 34 rows
 #endif
-    (void)d; (void)prof; (void)ab;
+    (void)d; (void)prof; (void)ab; (void)name;
     return nullptr;
 }
 // ---- stage stride of the row Jacobians in LDS (Dims::dpad) --------------------------------------------------------------------
@@ -393,6 +407,9 @@ struct tmpc_handle {
     bool prio_cp = false, prio_cp2 = false;   // wave issue priorities (Dims::prio) for the compact one-wave / two-wave kernel: only when its residency puts two waves on
                                               // every SIMD (8 waves per CU) -- with an odd count the waves that share a SIMD starve and set the makespan (tmpc_riccati.hpp)
     int latency_mode = 0;                     // 0: throughput kernels, 1: two-wave variant, 2: parallel-in-time variant
+    // the instantiation in each kernel slot above (pick_*_kernel's names; "generic<CM>" for the generic kernel; empty: the slot is not filled) --
+    // tmpc_kernel_info reports them, tmpc_debug_profile profiles only the twin of the instantiation a solve runs
+    std::string name_default, name_small, name_cp2, name_lat1, name_lat2, name_lat3;
     bool throughput_mode = false;             // lane-per-trajectory kernels (tmpc_lanes.hip) instead of one wave per trajectory
     tmpc::lanes::Context *lanes = nullptr;    // their HBM workspace, created when the mode is first enabled
     bool fast = false;
@@ -525,14 +542,16 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
     d.riccati_form = dims->riccati_form;
     tmpc::derive_dims(d);
     d.split_rows = tmpc::split_rows_for(d.N, d.n_up + d.M) ? 1 : 0;
-    h->kernel = d.riccati_form == TMPC_RICCATI_SQUARE_ROOT ? tmpc::pick_sqrt_kernel(d, &h->threads) : tmpc::pick_fast_kernel(d, &h->threads, false);
+    const char *nm_default = "", *nm_lat1 = "", *nm_lat2 = "", *nm_lat3 = "", *nm_cp = "", *nm_cp2 = "";
+    h->kernel = d.riccati_form == TMPC_RICCATI_SQUARE_ROOT ? tmpc::pick_sqrt_kernel(d, &h->threads, &nm_default) : tmpc::pick_fast_kernel(d, &h->threads, false, &nm_default);
     if (d.riccati_form == TMPC_RICCATI_SQUARE_ROOT && !h->kernel) { delete h; return TMPC_ERR_INVALID; }       // (no square-root instantiation for this shape: never a silent other form)
     if (const char *lm = lab_env("TMPC_LATENCY_MODE")) {      // experiments: latency variant regardless of the caller ("0" .. "3"; anything else is ignored)
         if (lm[0] >= '0' && lm[0] <= '3' && lm[1] == '\0') h->latency_mode = lm[0] - '0';
     }
     h->fast = h->kernel != nullptr;
     if (h->fast) h->lds_bytes = sizeof(double) * (size_t)tmpc::lds_doubles_fast(d.N, d.n_up + d.M);
-    else { const int sm = tmpc::stage_model(d); h->kernel = sm == 3 ? tmpc::tmpc_solve_kernel<3> : sm == 1 ? tmpc::tmpc_solve_kernel<1> : (sm == 2 ? tmpc::tmpc_solve_kernel<2> : tmpc::tmpc_solve_kernel<0>); h->lds_bytes = sizeof(double) * (size_t)tmpc::lds_doubles(d.N, d.n_up + d.M); }
+    else { const int sm = tmpc::stage_model(d); h->kernel = sm == 3 ? tmpc::tmpc_solve_kernel<3> : sm == 1 ? tmpc::tmpc_solve_kernel<1> : (sm == 2 ? tmpc::tmpc_solve_kernel<2> : tmpc::tmpc_solve_kernel<0>); h->lds_bytes = sizeof(double) * (size_t)tmpc::lds_doubles(d.N, d.n_up + d.M);
+           static const char *const generic_names[4] = {"generic<0>", "generic<1>", "generic<2>", "generic<3>"}; nm_default = generic_names[sm]; }
     h->lds_bytes_fast = h->lds_bytes;
     // two-wave (128-thread) fast kernels park one share of W per stage behind the layout while they linearise (linearise<.., 128>)
     // (a shape whose default is the generic kernel may still have a four-wave tick kernel -- curvature-aware cost + Gaussian rows: the fast LAYOUT's size then)
@@ -542,11 +561,11 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
     if (hipSetDevice(device) != hipSuccess) return fail(TMPC_ERR_HIP);
     if (h->lds_bytes > 160 * 1024) return fail(TMPC_ERR_INVALID);
     const bool schur = d.riccati_form == TMPC_RICCATI_SCHUR;      // the square-root form has its fast kernels only: no latency / compact variants
-    if (schur && h->fast && h->threads == tmpc::NT && (h->kernel_lat = tmpc::pick_latency_kernel(d, false)) != nullptr) {
+    if (schur && h->fast && h->threads == tmpc::NT && (h->kernel_lat = tmpc::pick_latency_kernel(d, false, &nm_lat1)) != nullptr) {
         if (hipFuncSetAttribute((const void *)h->kernel_lat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_fast2) != hipSuccess)
             h->kernel_lat = nullptr;
     }
-    if (schur && h->fast && (h->threads == tmpc::NT || d.N > 20) && (h->kernel_scan = tmpc::pick_scan_kernel(d, &h->scan_threads, &h->scan_sl)) != nullptr) {
+    if (schur && h->fast && (h->threads == tmpc::NT || d.N > 20) && (h->kernel_scan = tmpc::pick_scan_kernel(d, &h->scan_threads, &h->scan_sl, false, &nm_lat2)) != nullptr) {
         h->lds_bytes_scan = h->lds_bytes_fast2 + sizeof(double) * (size_t)(h->scan_sl == 3 ? tmpc::scan::lds_doubles<3>(d.N) : tmpc::scan::lds_doubles<2>(d.N));
         if (h->lds_bytes_scan > 160 * 1024) h->kernel_scan = nullptr;
     }
@@ -555,24 +574,24 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
             h->kernel_scan = nullptr;
     }
     int quad_sl = 3;
-    if (schur && (h->fast || tmpc::stage_model(d) == 3) && (h->threads == tmpc::NT || d.N > 20) && (h->kernel_quad = tmpc::pick_quad_kernel(d, false, lab_env("TMPC_QUAD_AB") != nullptr, &quad_sl)) != nullptr) {
+    if (schur && (h->fast || tmpc::stage_model(d) == 3) && (h->threads == tmpc::NT || d.N > 20) && (h->kernel_quad = tmpc::pick_quad_kernel(d, false, lab_env("TMPC_QUAD_AB") != nullptr, &quad_sl, &nm_lat3)) != nullptr) {
         // fast layout + the W shares of the split linearisation (wave 0's N x 28, the obstacle lanes' 36 N / 24 N: they lie inside the scan scratch, which is dead then) + the scan scratch
         h->lds_bytes_quad = h->lds_bytes_fast2 + sizeof(double) * (size_t)(quad_sl == 3 ? tmpc::scan::lds_doubles<3>(d.N) : tmpc::scan::lds_doubles<2>(d.N));
         if (h->lds_bytes_quad > 160 * 1024 ||
             hipFuncSetAttribute((const void *)h->kernel_quad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_quad) != hipSuccess)
             h->kernel_quad = nullptr;
     }
-    if (tmpc::SolveKernel kc = (schur && h->fast && h->threads == tmpc::NT) ? tmpc::pick_compact_kernel(d, false, &h->lay_cp) : nullptr) {
+    if (tmpc::SolveKernel kc = (schur && h->fast && h->threads == tmpc::NT) ? tmpc::pick_compact_kernel(d, false, &h->lay_cp, &nm_cp) : nullptr) {
         // the fast kernel of the shape (everything in LDS, four per CU) stays for launches it holds resident at once: bitwise the same results
         // (tests/test_gpu_compact2.py), a trajectory is ~10 % faster on it.  TMPC_COMPACT_MIN_B=0: the compact kernel for every launch (rounds 3-4)
         int fast_per_cu = 0, cus = 0;
         if (hipFuncSetAttribute((const void *)h->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes) == hipSuccess &&
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&fast_per_cu, (const void *)h->kernel, 64, h->lds_bytes) == hipSuccess && fast_per_cu > 0 &&
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) {
-            h->kernel_small = h->kernel; h->lds_bytes_small = h->lds_bytes; h->cp_min_B = fast_per_cu * cus;
+            h->kernel_small = h->kernel; h->lds_bytes_small = h->lds_bytes; h->cp_min_B = fast_per_cu * cus; h->name_small = nm_default;
             if (const char *e = lab_env("TMPC_COMPACT_MIN_B")) h->cp_min_B = atoi(e);                                              // experiments
         }
-        h->kernel = kc; h->compact = true;
+        h->kernel = kc; h->compact = true; nm_default = nm_cp;
         // padding of the packed rows' stage stride: only what keeps the residency (LDS is what bounds it: 8 x 20 KB at cfg 2)
         auto lds_cp = [&](int pad) { return sizeof(double) * (size_t)tmpc::lds_doubles_compact(d.N, d.n_lin, d.n_up + d.M, 64, pad, h->lay_cp); };
         auto per_cu_cp = [&](int pad) {
@@ -588,7 +607,7 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
     if (hipFuncSetAttribute((const void *)h->kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)h->lds_bytes) != hipSuccess)
         return fail(TMPC_ERR_NO_DEVICE);
-    if (schur && h->fast && h->threads == 128 && !h->compact && (h->kernel_cp2 = tmpc::pick_compact2_kernel(d, &h->lay_cp2, &h->cp2_threads)) != nullptr) {
+    if (schur && h->fast && h->threads == 128 && !h->compact && (h->kernel_cp2 = tmpc::pick_compact2_kernel(d, &h->lay_cp2, &h->cp2_threads, &nm_cp2)) != nullptr) {
         {
             auto lds_cp2 = [&](int pad) { return sizeof(double) * (size_t)tmpc::lds_doubles_compact(d.N, d.n_lin, d.n_up + d.M, h->cp2_threads, pad, h->lay_cp2); };
             auto per_cu_cp2 = [&](int pad) {
@@ -621,6 +640,11 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
         if (const char *e = lab_env("TMPC_COMPACT_PER_CU")) { const int v = atoi(e); if (v > 0 && v < per_cu) per_cu = v; }   // experiments
         h->grid_max = per_cu * cus; h->prio_cp = per_cu == 8;
     }
+    h->name_default = nm_default;
+    if (h->kernel_cp2) h->name_cp2 = nm_cp2;
+    if (h->kernel_lat) h->name_lat1 = nm_lat1;
+    if (h->kernel_scan) h->name_lat2 = nm_lat2;
+    if (h->kernel_quad) h->name_lat3 = nm_lat3;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(TMPC_ERR_HIP);
     const size_t N = d.N, B = B_max;
     bool ok = true;
@@ -740,6 +764,23 @@ int tmpc_set_batch_device(tmpc_handle *h, int32_t B, const void *d_xinit, const 
     return TMPC_OK;
 }
 
+// Which kernel slot a launch of the current batch runs (launch_solve; tmpc_debug_profile profiles the twin of that slot's instantiation).
+struct LaunchSlot { bool lat3, lat2, lat, cp2, small, cp; };
+static LaunchSlot launch_slot(const tmpc_handle *h)
+{
+    LaunchSlot k;
+    k.lat3 = h->kernel_quad && h->latency_mode == 3;
+    k.lat2 = !k.lat3 && h->kernel_scan && h->latency_mode >= 2;          // (mode 3 without a four-wave variant runs as mode 2, ...
+    k.lat = !k.lat3 && !k.lat2 && h->kernel_lat && h->latency_mode != 0;  //  ... mode 2 without a scan variant as the two-wave variant)
+    // compact <-> fast kernels of a shape compute bit for bit the same, so the launch size may choose between them: the fast kernel while it
+    // holds the whole launch resident (lower latency per trajectory), the compact one (twice the residency) above that
+    const bool any_lat = k.lat || k.lat2 || k.lat3;
+    k.cp2 = h->kernel_cp2 && !any_lat && h->B > h->cp2_min_B;
+    k.small = h->compact && h->kernel_small && !any_lat && h->B <= h->cp_min_B;
+    k.cp = (h->compact && !any_lat && !k.small) || k.cp2;
+    return k;
+}
+
 // One launch over the current batch: n_iter RTI iterations per trajectory + completeOneIteration.  st_flags: ST_* (0 = fresh
 // solver instances from the batch's warm start, nothing kept or stored: Solver::solve() of a new capsule).
 static int launch_solve(tmpc_handle *h, int n_iter, int st_flags)
@@ -759,14 +800,8 @@ static int launch_solve(tmpc_handle *h, int n_iter, int st_flags)
         dd.n_sqp = n_iter;
         tmpc::StateIO io{h->st_z, h->st_pi, h->st_lamh, h->st_stopped, st_flags, h->ws, h->ticket, (h->slots_set && h->slots_B == h->B) ? h->d_slot : nullptr, h->st_has,
                          (h->share_B == h->B) ? h->d_share : nullptr};      // (a map given for another batch size is not applied)
-        const bool lat3 = h->kernel_quad && h->latency_mode == 3;
-        const bool lat2 = !lat3 && h->kernel_scan && h->latency_mode >= 2;        // (mode 3 without a four-wave variant runs as mode 2, ...
-        const bool lat = !lat3 && !lat2 && h->kernel_lat && h->latency_mode != 0; //  ... mode 2 without a scan variant as the two-wave variant)
-        // compact <-> fast kernels of a shape compute bit for bit the same, so the launch size may choose between them: the fast kernel while it
-        // holds the whole launch resident (lower latency per trajectory), the compact one (twice the residency) above that
-        const bool cp2 = h->kernel_cp2 && !lat && !lat2 && !lat3 && h->B > h->cp2_min_B;
-        const bool small = h->compact && h->kernel_small && !lat && !lat2 && !lat3 && h->B <= h->cp_min_B;
-        const bool cp = (h->compact && !lat && !lat2 && !lat3 && !small) || cp2;
+        const LaunchSlot k = launch_slot(h);
+        const bool lat3 = k.lat3, lat2 = k.lat2, lat = k.lat, cp2 = k.cp2, small = k.small, cp = k.cp;
         dd.prio = cp2 ? h->prio_cp2 : (cp ? h->prio_cp : false);
         dd.dpad = cp2 ? h->dpad_cp2 : (cp ? h->dpad_cp : 0);      // (layout only: results do not depend on it)
         if (cp) TMPC_HIP_CHECK(h, hipMemsetAsync(h->ticket, 0, 8 * 4, h->stream));    // the persistent launch's work counters (one per XCD)
@@ -1147,9 +1182,14 @@ int tmpc_kernel_info(const tmpc_handle *h, char *buf, int32_t capacity)
                                                                                 std::to_string(h->lds_bytes_small) + " B, one workgroup per trajectory)" : "";
     const std::string cp2 = h->kernel_cp2 ? "; launches of more than " + std::to_string(h->cp2_min_B) + " trajectories: compact two-wave variant (LDS " +
                                             std::to_string(h->lds_bytes_cp2) + " B, persistent launch, resident workgroups " + std::to_string(h->grid_max) + ")" : "";
-    const int n = snprintf(buf, (size_t)capacity, "%s; trajectories per workgroup %d; LDS %zu B per workgroup; %s%s", family, 1,
+    // the instantiation of every filled slot (pick_*_kernel names): default (the compact kernel of a compact handle), small-launch twin, compact two-wave, latency modes 1-3
+    std::string names = "; kernels: default=" + h->name_default;
+    const std::pair<const char *, const std::string *> slots[] = {{"small", &h->name_small}, {"cp2", &h->name_cp2}, {"lat1", &h->name_lat1},
+                                                                  {"lat2", &h->name_lat2}, {"lat3", &h->name_lat3}};
+    for (const auto &sl : slots) if (!sl.second->empty()) names += std::string(", ") + sl.first + "=" + *sl.second;
+    const int n = snprintf(buf, (size_t)capacity, "%s; trajectories per workgroup %d; LDS %zu B per workgroup; %s%s%s", family, 1,
                            h->lds_bytes, h->compact ? (std::string("persistent launch, resident workgroups ") + std::to_string(h->grid_max)).c_str()
-                                                    : "one workgroup per trajectory", (cp2 + sm).c_str());
+                                                    : "one workgroup per trajectory", (cp2 + sm).c_str(), names.c_str());
     return n < capacity ? n : capacity - 1;
 }
 
@@ -1444,26 +1484,31 @@ int tmpc_debug_profile(tmpc_handle *h, int64_t *cycles, int32_t n_phases)
     TMPC_HIP_CHECK(h, bufs.alloc(&dp_, n * 8));
     long long *dp = (long long *)dp_;
     TMPC_HIP_CHECK(h, hipMemset(dp, 0, n * 8));
-    tmpc::SolveKernel pk = h->kernel;                   // the generic kernel profiles itself; fast shapes have an instrumented twin
+    // The instrumented twin of the instantiation a solve of the current batch runs (launch_slot): the generic kernel profiles itself, the fast kernels
+    // have profiled twins for some shapes, a compact kernel is profiled through the fast kernel of its shape (bitwise the same results, one wave per
+    // SIMD).  A slot without an exact twin is refused -- never another instantiation in its place.  LDS: what the twin's thread count needs.
+    const LaunchSlot k = launch_slot(h);
+    const std::string &running = k.lat3 ? h->name_lat3 : k.lat2 ? h->name_lat2 : k.lat ? h->name_lat1
+                               : h->compact ? h->name_small : h->name_default;  // (the fast kernel of a compact shape; cp2: the default slot holds it)
+    tmpc::SolveKernel pk = nullptr;
     int thr = h->threads;
-    size_t lds = h->fast ? h->lds_bytes_fast : h->lds_bytes;
-    if (h->fast && h->threads == 128) lds = h->lds_bytes_fast2;
-    if (h->fast && tmpc::stage_model(h->d) != 0) { h->err = "tmpc_debug_profile: no profiled twin for the curvature-aware cost / Gaussian rows"; return TMPC_ERR_INVALID; }
-    if (h->fast) {
-        pk = tmpc::pick_fast_kernel(h->d, &thr, true);
+    size_t lds = h->lds_bytes;
+    const char *twin = "";
+    if (!h->fast && !k.lat3) pk = h->kernel;
 #ifndef TMPC_GENERATED_STAGE
-        // the latency variants of cfg 2 are profiled as themselves (tmpc_set_latency_mode before the call)
-        if (h->latency_mode == 3 && h->kernel_quad && tmpc::pick_quad_kernel(h->d, true, false)) {
-            pk = tmpc::pick_quad_kernel(h->d, true, false); thr = 256; lds = h->lds_bytes_quad;
-        } else if (h->latency_mode >= 2 && h->kernel_scan && h->scan_threads == 128 && h->scan_sl == 3 && h->d.n_up == 8 && h->d.M == 8) {
-            pk = (tmpc::SolveKernel)tmpc::tmpc_solve_fast_kernel<8, 8, 6, 128, true, tmpc::ScanSolo>; thr = 128; lds = h->lds_bytes_scan;
-        } else if (h->latency_mode != 0 && h->kernel_lat) {
-            pk = tmpc::pick_latency_kernel(h->d, true); thr = 128; lds = h->lds_bytes_fast2;
-        }
+    else if (k.lat3) { pk = tmpc::pick_quad_kernel(h->d, true, false, nullptr, &twin); thr = 256; lds = h->lds_bytes_quad; }
+    else if (k.lat2) { int sl = 3; pk = tmpc::pick_scan_kernel(h->d, &thr, &sl, true, &twin); lds = h->lds_bytes_scan; }
+    else if (k.lat) { pk = tmpc::pick_latency_kernel(h->d, true, &twin); thr = 128; lds = h->lds_bytes_fast2; }
 #endif
+    else if (h->d.riccati_form == TMPC_RICCATI_SCHUR) { pk = tmpc::pick_fast_kernel(h->d, &thr, true, &twin); lds = thr == 128 ? h->lds_bytes_fast2 : h->lds_bytes_fast; }
+    if (h->fast || k.lat3) {
+        if (!pk || running != twin) {
+            h->err = "tmpc_debug_profile: no profiled twin of " + (running.empty() ? std::string("this kernel") : running) + " (the launch of " + std::to_string(h->B) +
+                     " trajectories in latency mode " + std::to_string(h->latency_mode) + ")";
+            return TMPC_ERR_INVALID;
+        }
         TMPC_HIP_CHECK(h, hipFuncSetAttribute((const void *)pk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    // (a compact handle is profiled through the fast kernel of its shape: same phases and arithmetic, one wave per SIMD)
     hipLaunchKernelGGL(pk, dim3(h->B), dim3(thr), lds, h->stream, h->d, h->B,
                        h->xinit, h->x0, h->params, h->xtraj, h->utraj, h->pobj, h->exit_code, h->qp_status,
                        h->sqp_iter, h->res_eq, h->qp_iter, dp, tmpc::StateIO{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr});

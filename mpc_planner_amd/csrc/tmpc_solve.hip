@@ -30,6 +30,7 @@ TMPC_SCAN_SHAPES(TMPC_I_SCAN_DEF)
 #elif defined(TMPC_TU_PROF)
 TMPC_FAST_SHAPES(TMPC_I_PROF_DEF)
 template __global__ void tmpc::tmpc_solve_fast_kernel<8, 8, 6, 128, true, tmpc::ScanSolo>(TMPC_KARGS);      // profiled twin of latency mode 2 (cfg 2)
+template __global__ void tmpc::tmpc_solve_fast_kernel<8, 8, 2, 64, true>(TMPC_KARGS);                   // profiled twin of the one-wave (8, 8) kernel of 22 <= N <= 32
 #elif defined(TMPC_TU_CP2)
 TMPC_CP2_SHAPES(TMPC_I_CP2_DEF)
 #elif defined(TMPC_TU_SQRT)

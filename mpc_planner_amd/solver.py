@@ -299,8 +299,8 @@ class BatchedSolver:
 
     def kernel_info(self):
         """Which solve kernel the handle dispatches and how it is launched (text)."""
-        buf = C.create_string_buffer(512)
-        n = self.lib.tmpc_kernel_info(self._h, buf, 512)
+        buf = C.create_string_buffer(2048)
+        n = self.lib.tmpc_kernel_info(self._h, buf, 2048)
         return buf.value.decode() if n >= 0 else ""
 
     def stream_ptr(self):
