@@ -50,29 +50,56 @@ static inline int clear_stopped(Context *, hipStream_t, int, std::string &err) {
 namespace tmpc {
 typedef void (*SolveKernel)(Dims, int, const double *, const double *, const double *, double *, double *, double *, int *,
                             int *, int *, double *, int *, long long *, StateIO);
+// ---- the solve-kernel slots of a handle ---------------------------------------------------------------------------------------------------------
+// A handle holds up to six solve kernels, one per slot (the labels tmpc_kernel_info reports); launch_slot() chooses the one a launch runs.
+enum Slot {
+    SLOT_DEFAULT,   // the fast kernel of the shape, else the generic kernel; on a one-wave compact handle the compact kernel (pick_compact_kernel)
+    SLOT_SMALL,     // one-wave compact handles: the fast one-wave kernel, for launches of AT MOST `bound` trajectories (what it holds resident at once)
+    SLOT_CP2,       // beside a two-wave fast default: the compact two-wave kernel, for launches of MORE THAN `bound` trajectories (what the default
+                    //   holds resident at once)
+    SLOT_LAT1,      // latency mode 1: two waves per trajectory (pick_latency_kernel)
+    SLOT_LAT2,      // latency mode 2: parallel-in-time Newton solve (pick_scan_kernel)
+    SLOT_LAT3,      // latency mode 3: four waves per trajectory (pick_quad_kernel)
+    SLOT_COUNT
+};
+struct KernelSlot {
+    enum Kind { GENERIC, FAST, COMPACT };
+    SolveKernel kernel = nullptr;   // nullptr: the slot is not filled
+    SolveKernel twin = nullptr;     // the instrumented instantiation tmpc_debug_profile runs in its place (nullptr: none; the generic kernel is its own)
+    const char *name = "";          // the instantiation (pick_*_kernel's names; "generic<CM>" for the generic kernel): tmpc_kernel_info reports it
+    Kind kind = FAST;               // COMPACT: a persistent launch -- grid = min(B, resident), the handle's ws + ticket
+    int threads = 0;                // threads per trajectory
+    size_t lds_bytes = 0;
+    int lay = 1;                    // compact kernels: the Hh layout (compact_layout, tmpc_fast.hpp)
+    int dpad = 0;                   // Dims::dpad: compact kernels' stage-stride padding (choose_compact_pad); the fast layouts do not pad
+    bool prio = false;              // Dims::prio: wave issue priorities (set_resident)
+    int resident = 0;               // compact kernels: the workgroups the device holds at once
+    int bound = 0;                  // small / cp2: the launch-size bound (Slot)
+};
 // Registered fast shapes (upper-bounded rows n_lin + n_slk, ellipsoids M) x lanes-per-stage; anything else runs the generic kernel.
 // Only instantiations that compile WITHOUT scratch (zero VGPR spills) are registered: __graft_entry__.build() checks
 // the compiler's resource remarks and fails otherwise.  Reason: with > ~100 spilled VGPRs this kernel was observed to
 // return wrong iterates (spill/reload around partially-masked regions), see DESIGN.md section 5.  Shapes with more rows
 // per lane ((8,8) at 2 lanes/stage for N > 21, (12,12) at 2 lanes/stage) therefore use the generic kernel for now.  The library is
 // built with -mllvm -disable-machine-licm: hoisted constant materialisations were what pushed (12,12,3) into scratch.
-// prof: the instrumented instantiation (tmpc_debug_profile) instead of the production one.
-// Every instantiation a pick_*_kernel function returns is written through one of the macros below, which also store the instantiation's name in
-// *name (when given): "fast<NLIN,MM,LPS,NTH,TEAM,CM>" / "compact<NLIN,MM,LPS,NTH,CM>", the template arguments as written (tmpc_kernel_info reports
-// them; tests/test_dispatch_table.py reads the same macro calls from this file and requires a test case for each name).
-//   TMPC_FAST(NLIN, MM, LPS, NTH)        MPCC + ellipsoid rows (TEAM = Solo, CM = 0), production or profiled twin by `prof`
-//   TMPC_FASTP(NLIN, MM, LPS, NTH, TEAM) another TEAM (CM = 0), production or profiled twin by `prof`
-//   TMPC_FASTX(NLIN, MM, LPS, NTH, TEAM, CM) production only (no profiled twin: the caller returns nullptr for `prof` first)
-//   TMPC_CP(NLIN, MM, LPS, CM) / TMPC_CP2(NLIN, MM, LPS, CM)   compact one-wave / two-wave kernels (set *lay)
-#define TMPC_KNAME(s) (name ? (void)(*name = (s)) : (void)0)
-#define TMPC_FAST(a, b, c, t) (TMPC_KNAME("fast<" #a "," #b "," #c "," #t ",Solo,0>"), \
-                               prof ? (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, true> : (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, false>)
-#define TMPC_FASTP(a, b, c, t, team) (TMPC_KNAME("fast<" #a "," #b "," #c "," #t "," #team ",0>"), \
-                                      prof ? (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, true, team> : (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, false, team>)
-#define TMPC_FASTX(a, b, c, t, team, m) (TMPC_KNAME("fast<" #a "," #b "," #c "," #t "," #team "," #m ">"), (SolveKernel)tmpc_solve_fast_kernel<a, b, c, t, false, team, m>)
-static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof, const char **name = nullptr)
+// Every instantiation a pick_*_kernel function returns is written through one of the macros below.  Each fills the slot *s from the template
+// arguments as written: the name "fast<NLIN,MM,LPS,NTH,TEAM,CM>" / "compact<NLIN,MM,LPS,NTH,CM>" (tests/test_dispatch_table.py reads the same
+// macro calls from this file and requires a test case for each name), the threads (NTH), the kind, the compact layout and the profiled twin;
+// it yields the production kernel.
+//   TMPC_FAST(NLIN, MM, LPS, NTH)        MPCC + ellipsoid rows (TEAM = Solo, CM = 0), with a profiled twin
+//   TMPC_FASTP(NLIN, MM, LPS, NTH, TEAM) another TEAM (CM = 0), with a profiled twin
+//   TMPC_FASTX(NLIN, MM, LPS, NTH, TEAM, CM) no profiled twin
+//   TMPC_CP(NLIN, MM, LPS, CM) / TMPC_CP2(NLIN, MM, LPS, CM)   compact one-wave / two-wave kernels (persistent: tmpc_debug_profile runs the fast kernel
+//                                                              of the shape instead)
+#define TMPC_INST(nm, nth, kind_, lay_, twin_, k) (s->name = (nm), s->threads = (nth), s->kind = KernelSlot::kind_, s->lay = (lay_), s->twin = (twin_), (k))
+#define TMPC_FAST(a, b, c, t) TMPC_INST("fast<" #a "," #b "," #c "," #t ",Solo,0>", t, FAST, 1, (SolveKernel)(tmpc_solve_fast_kernel<a, b, c, t, true>), \
+                                        (SolveKernel)(tmpc_solve_fast_kernel<a, b, c, t, false>))
+#define TMPC_FASTP(a, b, c, t, team) TMPC_INST("fast<" #a "," #b "," #c "," #t "," #team ",0>", t, FAST, 1, (SolveKernel)(tmpc_solve_fast_kernel<a, b, c, t, true, team>), \
+                                               (SolveKernel)(tmpc_solve_fast_kernel<a, b, c, t, false, team>))
+#define TMPC_FASTX(a, b, c, t, team, m) TMPC_INST("fast<" #a "," #b "," #c "," #t "," #team "," #m ">", t, FAST, 1, nullptr, \
+                                                  (SolveKernel)(tmpc_solve_fast_kernel<a, b, c, t, false, team, m>))
+static SolveKernel pick_fast_kernel(const Dims &d, KernelSlot *s)
 {
-    *threads = NT;
     if (lab_env("TMPC_FORCE_GENERIC")) return nullptr;
     const int lps = (3 * d.N <= NT) ? 3 : ((2 * d.N <= NT) ? 2 : 0);
 #ifndef TMPC_GENERATED_STAGE
@@ -80,30 +107,23 @@ static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof, cons
     if (d.cost_model == 1) {
         // curvature-aware contouring (BASELINE configs[2]): the cfg-3 shape on the two-wave kernel, every other row mix of N <= 20 on the
         // runtime-shape one-wave kernel, anything else on the generic kernel -- all instantiated with CM = 1 (no profiled twins)
-        if (prof) return nullptr;
         const int nrc = d.n_up + d.M + 14;
-        if (lps != 3 && 4 * d.N <= 128 && d.n_up == 20 && d.M == 8 && !lab_env("TMPC_NO_TWO_WAVE")) {
-            *threads = 128;
-            return TMPC_FASTX(20, 8, 4, 128, Solo, 1);
-        }
+        if (lps != 3 && 4 * d.N <= 128 && d.n_up == 20 && d.M == 8 && !lab_env("TMPC_NO_TWO_WAVE")) return TMPC_FASTX(20, 8, 4, 128, Solo, 1);
         if (lps == 3 && nrc <= 3 * 13) return TMPC_FASTX(-1, 13, 3, 64, Solo, 1);
         return nullptr;
     }
     if (d.row_model == 1) {
         // Gaussian chance-constraint rows instead of the ellipsoids (mpc_planner_jackal's default: N = 30, 5 topology + 5 Gaussian rows):
-        // runtime-shape instantiations with CM = 2 -- two-wave for 22 <= N <= 32, one-wave for N <= 21, else the generic kernel
-        if (prof) return nullptr;
+        // runtime-shape instantiations with CM = 2 (no profiled twins) -- two-wave for 22 <= N <= 32, one-wave for N <= 21, else the generic kernel
         const int nrg = d.n_up + d.M + 14;
         // mpc_planner_jackal's default (generate_jackal_solver.py:53-73: N = 30, 5 + 5 rows) on ONE wave at two lanes per stage (round 6): twelve rows per lane
         // fit the registers, and eight one-wave trajectories per CU keep eight waves busy where four two-wave ones idle a wave through every Riccati sweep --
         // saturated +27 % (585 -> 741 k solves/s).  Its small-launch twin below, the compact kernel in pick_compact_kernel; ticks: latency modes 2 / 3.
         if (lps == 2 && d.n_up == 5 && d.M == 5 && !lab_env("TMPC_NO_ONE_WAVE_N30")) return TMPC_FASTX(5, 5, 2, 64, Solo, 2);
         if (lps != 3 && 4 * d.N <= 128 && !lab_env("TMPC_NO_TWO_WAVE")) {
-            *threads = 128;
             if (d.n_up == 5 && d.M == 5) return TMPC_FASTX(5, 5, 4, 128, Solo, 2);     // mpc_planner_jackal's default (generate_jackal_solver.py:53-73), tuned
             if (nrg <= 4 * 6) return TMPC_FASTX(-1, 6, 4, 128, Solo, 2);
             if (nrg <= 4 * 12) return TMPC_FASTX(-1, 12, 4, 128, Solo, 2);
-            *threads = NT;
         }
         if (lps == 3 && nrg <= 3 * 13) return TMPC_FASTX(-1, 13, 3, 64, Solo, 2);
         return nullptr;
@@ -116,7 +136,7 @@ static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof, cons
     if (lps == 3) return TMPC_FAST(tmpc_gen::NH, 0, 3, 64);
 #endif
 #ifdef TMPC_GEN_FAST2
-    if (lps != 3 && 4 * d.N <= 128) { *threads = 128; return TMPC_FAST(tmpc_gen::NH, 0, 4, 128); }
+    if (lps != 3 && 4 * d.N <= 128) return TMPC_FAST(tmpc_gen::NH, 0, 4, 128);
 #endif
     return nullptr;
 #else
@@ -127,14 +147,12 @@ static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof, cons
     if (lps == 2 && d.n_up == 8 && d.M == 8 && !lab_env("TMPC_NO_ONE_WAVE_N30")) return TMPC_FAST(8, 8, 2, 64);
     if (lps != 3 && 4 * d.N <= 128 && !lab_env("TMPC_NO_TWO_WAVE")) {
         // two waves per trajectory, 4 lanes per stage (22 <= N <= 32: the reference's default N = 30 and BASELINE cfg 3)
-        SolveKernel k2 = nullptr;
-        if (d.n_up == 8 && d.M == 8) k2 = TMPC_FAST(8, 8, 4, 128);
-        else if (d.n_up == 12 && d.M == 12) k2 = TMPC_FAST(12, 12, 4, 128);  // mpc_planner_jackalsimulator defaults (N = 30, 12 obstacles)
-        else if (d.n_up == 20 && d.M == 8) k2 = TMPC_FAST(20, 8, 4, 128);    // cfg 3: 8 topology + 12 decomp rows + 8 ellipsoids
-        else if (nr <= 4 * 6) k2 = TMPC_FAST(-1, 6, 4, 128);                 // any other row mix: runtime-shape instantiations
-        else if (nr <= 4 * 9) k2 = TMPC_FAST(-1, 9, 4, 128);                 //   (e.g. mpc_planner_jackal: N = 30, 5 obstacles)
-        else if (nr <= 4 * 12) k2 = TMPC_FAST(-1, 12, 4, 128);
-        if (k2) { *threads = 128; return k2; }
+        if (d.n_up == 8 && d.M == 8) return TMPC_FAST(8, 8, 4, 128);
+        if (d.n_up == 12 && d.M == 12) return TMPC_FAST(12, 12, 4, 128);  // mpc_planner_jackalsimulator defaults (N = 30, 12 obstacles)
+        if (d.n_up == 20 && d.M == 8) return TMPC_FAST(20, 8, 4, 128);    // cfg 3: 8 topology + 12 decomp rows + 8 ellipsoids
+        if (nr <= 4 * 6) return TMPC_FAST(-1, 6, 4, 128);                 // any other row mix: runtime-shape instantiations
+        if (nr <= 4 * 9) return TMPC_FAST(-1, 9, 4, 128);                 //   (e.g. mpc_planner_jackal: N = 30, 5 obstacles)
+        if (nr <= 4 * 12) return TMPC_FAST(-1, 12, 4, 128);
     }
     if (lps == 3) {
         if (d.n_up == 0 && d.M == 4) return TMPC_FAST(0, 4, 3, 64);
@@ -144,10 +162,8 @@ static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof, cons
         if (nr <= 3 * 7) return TMPC_FAST(-1, 7, 3, 64);                     // runtime-shape instantiations
         if (nr <= 3 * 10) return TMPC_FAST(-1, 10, 3, 64);
         if (nr <= 3 * 13) return TMPC_FAST(-1, 13, 3, 64);
-        if (d.N <= 2 * (64 / 6) && nr <= 6 * 9 && !lab_env("TMPC_NO_TWO_WAVE")) {   // more rows: two waves, 6 lanes per stage
-            *threads = 128;                                                  //   (mpc_planner_rosnavigation T-MPC: 24 + 12 rows)
-            return TMPC_FAST(-1, 9, 6, 128);
-        }
+        if (d.N <= 2 * (64 / 6) && nr <= 6 * 9 && !lab_env("TMPC_NO_TWO_WAVE"))    // more rows: two waves, 6 lanes per stage
+            return TMPC_FAST(-1, 9, 6, 128);                                 //   (mpc_planner_rosnavigation T-MPC: 24 + 12 rows)
     } else if (lps == 2) {
         if (d.n_up == 0 && d.M == 4) return TMPC_FAST(0, 4, 2, 64);
     }
@@ -156,9 +172,8 @@ static SolveKernel pick_fast_kernel(const Dims &d, int *threads, bool prof, cons
 }
 // Square-root form of the Riccati recursion (tmpc_dims.riccati_form = TMPC_RICCATI_SQUARE_ROOT; csrc/tmpc_riccati.hpp SQ): run-time-shape fast kernels only
 // -- a comparison aid (HPIPM's default recursion) with one instantiation per kernel family member that the BASELINE shapes need, not a throughput path.
-static SolveKernel pick_sqrt_kernel(const Dims &d, int *threads, const char **name = nullptr)
+static SolveKernel pick_sqrt_kernel(const Dims &d, KernelSlot *s)
 {
-    *threads = NT;
 #ifndef TMPC_GENERATED_STAGE
     const int nr = d.n_up + d.M + 14, sm = stage_model(d);
     if (3 * d.N <= NT) {
@@ -166,12 +181,11 @@ static SolveKernel pick_sqrt_kernel(const Dims &d, int *threads, const char **na
         return nullptr;
     }
     if (4 * d.N <= 128 && nr <= 4 * 12) {
-        *threads = 128;
         if (sm == 0) return TMPC_FASTX(-1, 12, 4, 128, SoloSqrt, 0);
         if (sm == 1 && d.n_up == 20 && d.M == 8) return TMPC_FASTX(20, 8, 4, 128, SoloSqrt, 1);      // cfg 3 as named (CA-MPC)
     }
 #endif
-    (void)d; (void)name;
+    (void)d; (void)s;
     return nullptr;
 }
 // Compact variant (tmpc_fast.hpp: tmpc_solve_compact_kernel): two waves per SIMD, eight trajectories per CU, persistent
@@ -180,20 +194,21 @@ static SolveKernel pick_sqrt_kernel(const Dims &d, int *threads, const char **na
 // row passes are specialised by the compile-time kind of each row slot (FastCfg::KIND): 238 registers, zero scratch; their larger row tables
 // allow 7 (cfg 4: 23.3 KB) and 6 (cfg 5: 25.2 KB) workgroups per CU.  The runtime-shape instantiation with 13 rows per lane still spills
 // (168 B) and is not registered.
-// *lay: the instantiation's Hh layout (compact_layout, tmpc_fast.hpp) -- evaluated on the template arguments
-// where they are written, so that the host's LDS size and the kernel's layout cannot disagree
-#define TMPC_CP(a, b, c, m) (*lay = compact_layout(a, b, 64), TMPC_KNAME("compact<" #a "," #b "," #c ",64," #m ">"), (SolveKernel)tmpc_solve_compact_kernel<a, b, c, false, 64, m>)
-#define TMPC_CP2(a, b, c, m) (*lay = compact_layout(a, b, 128), TMPC_KNAME("compact<" #a "," #b "," #c ",128," #m ">"), (SolveKernel)tmpc_solve_compact_kernel<a, b, c, false, 128, m>)
-static SolveKernel pick_compact_kernel(const Dims &d, bool prof, int *lay, const char **name = nullptr)
+// The layout: the instantiation's Hh layout (compact_layout, tmpc_fast.hpp) -- evaluated on the template arguments where they are written, so that
+// the host's LDS size and the kernel's layout cannot disagree
+#define TMPC_CP(a, b, c, m) TMPC_INST("compact<" #a "," #b "," #c ",64," #m ">", 64, COMPACT, compact_layout(a, b, 64), nullptr, \
+                                      (SolveKernel)(tmpc_solve_compact_kernel<a, b, c, false, 64, m>))
+#define TMPC_CP2(a, b, c, m) TMPC_INST("compact<" #a "," #b "," #c ",128," #m ">", 128, COMPACT, compact_layout(a, b, 128), nullptr, \
+                                       (SolveKernel)(tmpc_solve_compact_kernel<a, b, c, false, 128, m>))
+static SolveKernel pick_compact_kernel(const Dims &d, KernelSlot *s)
 {
-    *lay = 1;
 #ifndef TMPC_GENERATED_STAGE
-    if (!lab_env("TMPC_FORCE_GENERIC") && !lab_env("TMPC_NO_COMPACT") && !lab_env("TMPC_NO_ONE_WAVE_N30") && !prof && 2 * d.N <= NT && 3 * d.N > NT) {
+    if (!lab_env("TMPC_FORCE_GENERIC") && !lab_env("TMPC_NO_COMPACT") && !lab_env("TMPC_NO_ONE_WAVE_N30") && 2 * d.N <= NT && 3 * d.N > NT) {
         // 22 <= N <= 32 on one wave, two lanes per stage (pick_fast_kernel): mpc_planner_jackal's default, the jackalsimulator stack
         if (stage_model(d) == 2 && d.n_up == 5 && d.M == 5) return TMPC_CP(5, 5, 2, 2);
         if (stage_model(d) == 0 && d.n_up == 8 && d.M == 8) return TMPC_CP(8, 8, 2, 0);
     }
-    if (lab_env("TMPC_FORCE_GENERIC") || lab_env("TMPC_NO_COMPACT") || prof || d.N > 20 || (stage_model(d) != 0 && stage_model(d) != 2)) return nullptr;
+    if (lab_env("TMPC_FORCE_GENERIC") || lab_env("TMPC_NO_COMPACT") || d.N > 20 || (stage_model(d) != 0 && stage_model(d) != 2)) return nullptr;
     if (stage_model(d) == 2) {                       // Gaussian chance-constraint rows (round 6): the run-time-shape instantiation with up to ten rows per lane
         if (d.n_up + d.M + 14 <= 3 * 10) return TMPC_CP(-1, 10, 3, 2);
         return nullptr;
@@ -206,7 +221,7 @@ static SolveKernel pick_compact_kernel(const Dims &d, bool prof, int *lay, const
     if (nr <= 3 * 7) return TMPC_CP(-1, 7, 3, 0);       // runtime-shape instantiations
     if (nr <= 3 * 10) return TMPC_CP(-1, 10, 3, 0);
 #endif
-    (void)d; (void)prof; (void)name;
+    (void)d; (void)s;
     return nullptr;
 }
 // Two-wave compact variant (round 4: 22 <= N <= 32, four lanes per stage -- the reference's N = 30 defaults, cfg 3): the same kernel with
@@ -214,11 +229,9 @@ static SolveKernel pick_compact_kernel(const Dims &d, bool prof, int *lay, const
 // fast two-wave kernel (57-70 KB of LDS) holds two.  Bitwise the same results; a trajectory takes longer on it (NLP data in the global
 // workspace, the linearisation on one of the two waves), so launch_solve uses it only for launches that the fast kernel could not hold
 // resident at once (more than two trajectories per CU).  The runtime-shape instantiation with 12 rows per lane spills (144 B): not registered.
-static SolveKernel pick_compact2_kernel(const Dims &d, int *lay, int *threads, const char **name = nullptr)
+static SolveKernel pick_compact2_kernel(const Dims &d, KernelSlot *s)
 {
-    *lay = 1; *threads = 128;
 #ifndef TMPC_GENERATED_STAGE
-
     if (lab_env("TMPC_FORCE_GENERIC") || lab_env("TMPC_NO_COMPACT") || lab_env("TMPC_NO_TWO_WAVE") || 3 * d.N <= NT || 4 * d.N > 128) return nullptr;
     const int nr = d.n_up + d.M + 14, sm = stage_model(d);
     if (sm == 1) return (d.n_up == 20 && d.M == 8) ? TMPC_CP2(20, 8, 4, 1) : nullptr;      // cfg 3 as named (CA-MPC)
@@ -233,7 +246,7 @@ static SolveKernel pick_compact2_kernel(const Dims &d, int *lay, int *threads, c
     if (nr <= 4 * 6) return TMPC_CP2(-1, 6, 4, 0);
     if (nr <= 4 * 9) return TMPC_CP2(-1, 9, 4, 0);
 #endif
-    (void)d; (void)name;
+    (void)d; (void)s;
     return nullptr;
 }
 // Latency variant (tmpc_set_latency_mode): two waves per trajectory at 6 lanes per stage, built for two waves per SIMD
@@ -241,13 +254,13 @@ static SolveKernel pick_compact2_kernel(const Dims &d, int *lay, int *threads, c
 // -8 % kernel time on a 64-trajectory control tick; on a saturated GPU the one-wave kernel is as fast or faster, which is
 // why it stays the default.  The variant is chosen by the caller, never by the batch size: a trajectory's result does
 // not depend on what else is in the launch.
-static SolveKernel pick_latency_kernel(const Dims &d, bool prof, const char **name = nullptr)
+static SolveKernel pick_latency_kernel(const Dims &d, KernelSlot *s)
 {
 #ifndef TMPC_GENERATED_STAGE
     if (lab_env("TMPC_FORCE_GENERIC") || lab_env("TMPC_NO_TWO_WAVE") || d.N > 2 * (64 / 6) || stage_model(d) != 0) return nullptr;
     if (d.n_up == 8 && d.M == 8) return TMPC_FAST(8, 8, 6, 128);
 #endif
-    (void)d; (void)prof; (void)name;
+    (void)d; (void)s;
     return nullptr;
 }
 // Latency variant 2 (tmpc_set_latency_mode(h, 2)): one wave per trajectory like the fast kernels, the interior-point Newton systems
@@ -255,32 +268,29 @@ static SolveKernel pick_latency_kernel(const Dims &d, bool prof, const char **na
 // tick gives it anyway: built for one wave per SIMD (all 512 registers, 73 KB of LDS).  Another factorisation of the same systems:
 // steps agree with the recursion's to rounding (~1e-6 of a step on ill-conditioned late iterations, like the recursion itself
 // against an exact solve), so iteration counts can differ by one where a residual sits at the tolerance -- the caller opts in.
-// prof: the profiled twin (registered for the cfg-2 shape (8, 8) on two waves only).
-static SolveKernel pick_scan_kernel(const Dims &d, int *threads, int *sl, bool prof = false, const char **name = nullptr)
+// A profiled twin exists for the cfg-2 shape (8, 8) on two waves only.  *sl: the scan depth of the factorisation (tmpc_scan.hpp).
+static SolveKernel pick_scan_kernel(const Dims &d, KernelSlot *s, int *sl)
 {
     *sl = 3;
 #ifndef TMPC_GENERATED_STAGE
     if (lab_env("TMPC_FORCE_GENERIC") || d.N > 31 || d.N < 2 || (stage_model(d) != 0 && stage_model(d) != 2)) return nullptr;
     const bool gauss = stage_model(d) == 2;                      // Gaussian chance-constraint rows (mpc_planner_jackal's default stack): the run-time-shape instantiations, CM = 2
     if (d.N > 20) {                                              // 21 <= N <= 31 (cfg 3, the reference's N = 30 defaults): two lanes per stage in the
-        if (d.n_up + d.M + 14 > 4 * 12 || prof) return nullptr;  // Newton solve, the runtime-shape two-wave kernel (4 lanes per stage, up to 34 rows) around it
-        *threads = 128; *sl = 2;
+        if (d.n_up + d.M + 14 > 4 * 12) return nullptr;          // Newton solve, the runtime-shape two-wave kernel (4 lanes per stage, up to 34 rows) around it
+        *sl = 2;
         return gauss ? TMPC_FASTX(-1, 12, 4, 128, ScanSoloT<2>, 2) : TMPC_FASTX(-1, 12, 4, 128, ScanSoloT<2>, 0);
     }
     if (gauss) {
-        if (!prof && d.N <= 2 * (64 / 6) && d.n_up + d.M + 14 <= 6 * 9) { *threads = 128; return TMPC_FASTX(-1, 9, 6, 128, ScanSolo, 2); }
+        if (d.N <= 2 * (64 / 6) && d.n_up + d.M + 14 <= 6 * 9) return TMPC_FASTX(-1, 9, 6, 128, ScanSolo, 2);
         return nullptr;
     }
     const char *w = lab_env("TMPC_SCAN_WAVES");               // A/B: "1" = one wave per trajectory
-    if (d.n_up == 8 && d.M == 8 && d.N <= 2 * (64 / 6) && !(w && atoi(w) == 1)) { *threads = 128; return TMPC_FASTP(8, 8, 6, 128, ScanSolo); }
-    if (prof) return nullptr;
-    if (d.n_up == 8 && d.M == 8) { *threads = 64; return TMPC_FASTX(8, 8, 3, 64, ScanSolo, 0); }
-    if (d.N <= 2 * (64 / 6) && d.n_up + d.M + 14 <= 6 * 9) {     // every other row mix of the one-wave shapes (cfg 1, cfg 4, cfg 5, ...): runtime row counts, two waves
-        *threads = 128;
+    if (d.n_up == 8 && d.M == 8 && d.N <= 2 * (64 / 6) && !(w && atoi(w) == 1)) return TMPC_FASTP(8, 8, 6, 128, ScanSolo);
+    if (d.n_up == 8 && d.M == 8) return TMPC_FASTX(8, 8, 3, 64, ScanSolo, 0);
+    if (d.N <= 2 * (64 / 6) && d.n_up + d.M + 14 <= 6 * 9)      // every other row mix of the one-wave shapes (cfg 1, cfg 4, cfg 5, ...): runtime row counts, two waves
         return TMPC_FASTX(-1, 9, 6, 128, ScanSolo, 0);
-    }
 #endif
-    (void)d; (void)threads; (void)prof; (void)name;
+    (void)d; (void)s;
     return nullptr;
 }
 // Latency variant 3 (tmpc_set_latency_mode(h, 3), round 6): FOUR waves per trajectory -- a control tick of a few planners leaves a whole CU (four SIMDs,
@@ -288,15 +298,15 @@ static SolveKernel pick_scan_kernel(const Dims &d, int *threads, int *sl, bool p
 // the interior-point row passes run at twelve lanes per stage (three rows per lane instead of five), and the wide phases of the parallel-in-time
 // factorisation (the stage phase: one column per lane instead of four; level 0 of the cyclic reduction: one instead of two) use all 256 lanes
 // (csrc/tmpc_scan.hpp factor4).  Same algorithm as variant 2 (sums associate differently: rounding level).  N <= 20, hand-written MPCC stages.
-// `ab`: TMPC_QUAD_AB=1 in a lab build picks the twin whose factorisation stays on one wave (A/B of the factorisation split alone).
-static SolveKernel pick_quad_kernel(const Dims &d, bool prof, bool ab, int *sl = nullptr, const char **name = nullptr)
+// `ab`: TMPC_QUAD_AB=1 in a lab build picks the twin whose factorisation stays on one wave (A/B of the factorisation split alone).  *sl: as pick_scan_kernel.
+static SolveKernel pick_quad_kernel(const Dims &d, bool ab, KernelSlot *s, int *sl)
 {
-    if (sl) *sl = 3;
+    *sl = 3;
 #ifndef TMPC_GENERATED_STAGE
-    if (d.N > 20 && d.N <= 31 && !prof && !ab && d.n_up + d.M + 14 <= 8 * 6) {
+    if (d.N > 20 && d.N <= 31 && !ab && d.n_up + d.M + 14 <= 8 * 6) {
         // 21 <= N <= 31 (the horizon the reference ships for jackal / jackalsimulator: N = 30): eight lanes per stage around the two-lanes-per-stage Newton solve;
         // every stage model (the four-wave linearisation regularises a coupled W -- curvature-aware cost -- on wave 0)
-        if (sl) *sl = 2;
+        *sl = 2;
         const int sm = stage_model(d);
         return sm == 0 ? TMPC_FASTX(-1, 6, 8, 256, ScanQuadT<2>, 0)
              : sm == 1 ? TMPC_FASTX(-1, 6, 8, 256, ScanQuadT<2>, 1)
@@ -304,11 +314,11 @@ static SolveKernel pick_quad_kernel(const Dims &d, bool prof, bool ab, int *sl =
              : sm == 3 ? TMPC_FASTX(-1, 6, 8, 256, ScanQuadT<2>, 3) : nullptr;
     }
     if (d.N > 20 || d.N < 2 || (stage_model(d) != 0 && stage_model(d) != 2)) return nullptr;
-    if (stage_model(d) == 2) return (!prof && d.n_up + d.M + 14 <= 12 * 4) ? TMPC_FASTX(-1, 4, 12, 256, ScanQuad, 2) : nullptr;      // Gaussian rows
-    if (d.n_up == 8 && d.M == 8) return (ab && !prof) ? TMPC_FASTX(8, 8, 12, 256, ScanSolo, 0) : TMPC_FASTP(8, 8, 12, 256, ScanQuad);    // (prof: the twin of ScanQuad)
-    if (!prof && d.n_up + d.M + 14 <= 12 * 4) return TMPC_FASTX(-1, 4, 12, 256, ScanQuad, 0);      // cfg 1, cfg 4, cfg 5, any row mix up to 34 rows
+    if (stage_model(d) == 2) return (d.n_up + d.M + 14 <= 12 * 4) ? TMPC_FASTX(-1, 4, 12, 256, ScanQuad, 2) : nullptr;      // Gaussian rows
+    if (d.n_up == 8 && d.M == 8) return ab ? TMPC_FASTX(8, 8, 12, 256, ScanSolo, 0) : TMPC_FASTP(8, 8, 12, 256, ScanQuad);    // (a profiled twin: ScanQuad's only)
+    if (d.n_up + d.M + 14 <= 12 * 4) return TMPC_FASTX(-1, 4, 12, 256, ScanQuad, 0);      // cfg 1, cfg 4, cfg 5, any row mix up to 34 rows
 #endif
-    (void)d; (void)prof; (void)ab; (void)name;
+    (void)d; (void)ab; (void)s;
     return nullptr;
 }
 // ---- stage stride of the row Jacobians in LDS (Dims::dpad) --------------------------------------------------------------------
@@ -360,6 +370,49 @@ static int pick_d_pad(int N, int n_pair, int nh, int threads, int max_pad, Allow
     }
     return best;
 }
+
+// ---- filling a slot (tmpc_create) ---------------------------------------------------------------------------------------------------------------
+constexpr size_t LDS_CAP = 160 * 1024;     // what one CU has: a slot that needs more is not filled
+// The LDS a slot's kernel needs, from its kind and geometry; sl: the scan depth of the latency-2 / -3 kernels (pick_scan_kernel, pick_quad_kernel)
+static size_t slot_lds(const Dims &d, int slot, const KernelSlot &s, int sl)
+{
+    const int nh = d.n_up + d.M;
+    if (s.kind == KernelSlot::GENERIC) return sizeof(double) * (size_t)lds_doubles(d.N, nh);
+    if (s.kind == KernelSlot::COMPACT) return sizeof(double) * (size_t)lds_doubles_compact(d.N, d.n_lin, nh, s.threads, s.dpad, s.lay);
+    size_t n = lds_doubles_fast(d.N, nh);
+    // two-wave (128-thread) fast kernels park one share of W per stage behind the layout while they linearise (linearise<.., 128>), and so do all
+    // latency kernels; the four-wave one parks the W shares of its split linearisation there (wave 0's N x 28) and inside the scan scratch (the
+    // obstacle lanes' 36 N / 24 N), which is dead then
+    if (s.threads == 128 || slot >= SLOT_LAT1) n += (size_t)d.N * NP28;
+    if (slot == SLOT_LAT2 || slot == SLOT_LAT3) n += sl == 3 ? scan::lds_doubles<3>(d.N) : scan::lds_doubles<2>(d.N);
+    return sizeof(double) * n;
+}
+// Sets `lds` as the kernel's maximum dynamic LDS and returns how many workgroups of `threads` threads one CU holds at once (0: a call failed)
+static int blocks_per_cu(SolveKernel k, int threads, size_t lds)
+{
+    int n = 0;
+    if (hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k, threads, lds) != hipSuccess) return 0;
+    return n;
+}
+// A compact kernel's padding of the packed rows' stage stride (Dims::dpad): only what keeps the residency of no padding (LDS is what bounds it:
+// 8 x 20 KB at cfg 2).  Sets s.dpad and s.lds_bytes.
+static void choose_compact_pad(const Dims &d, int slot, KernelSlot &s)
+{
+    auto per_cu = [&](int pad) { s.dpad = pad; return blocks_per_cu(s.kernel, s.threads, slot_lds(d, slot, s, 0)); };
+    const int per_cu0 = per_cu(0);
+    const int pad = pick_d_pad(d.N, d.n_lin, d.n_up + d.M, s.threads, DPAD_MAX, [&](int p) { return p == 0 || (per_cu0 > 0 && per_cu(p) == per_cu0); });
+    s.dpad = pad;
+    s.lds_bytes = slot_lds(d, slot, s, 0);
+}
+// A compact slot's resident workgroups, and its wave issue priorities: only when the residency puts two waves on every SIMD (8 waves per CU) --
+// with an odd count the waves that share a SIMD starve and set the makespan (tmpc_riccati.hpp)
+static void set_resident(KernelSlot &s, int per_cu, int cus)
+{
+    if (const char *e = lab_env("TMPC_COMPACT_PER_CU")) { const int v = atoi(e); if (v > 0 && v < per_cu) per_cu = v; }   // experiments
+    s.resident = per_cu * cus;
+    s.prio = per_cu * (s.threads / 64) == 8;
+}
 }  // namespace tmpc
 
 struct tmpc_handle {
@@ -380,39 +433,12 @@ struct tmpc_handle {
     size_t slab_in_bytes = 0, slab_out_bytes = 0;
     hipEvent_t in_done = nullptr, slot_done = nullptr;    // the last H2D copies out of pin_in -- batch inputs / slot map: disjoint regions of the mirror, each rewritten only after ITS copy
     bool in_pending = false, slot_pending = false;
-    size_t lds_bytes = 0;
-    tmpc::SolveKernel kernel = nullptr;
-    int threads = tmpc::NT;          // threads per trajectory (64, or 128 for the two-wave fast variant)
-    tmpc::SolveKernel kernel_lat = nullptr;   // optional latency variant (128 threads), used when latency_mode is 1
-    tmpc::SolveKernel kernel_scan = nullptr;  // optional latency variant 2 (parallel-in-time Newton solve, 64 threads)
-    tmpc::SolveKernel kernel_quad = nullptr;  // optional latency variant 3 (four waves per trajectory, 256 threads; LDS = lds_bytes_scan3)
-    size_t lds_bytes_quad = 0;
-    size_t lds_bytes_scan = 0;
-    int scan_threads = 64, scan_sl = 3;
-    size_t lds_bytes_fast = 0;                // LDS of the fast-layout kernels (the profiled twin) when `kernel` is compact
-    size_t lds_bytes_fast2 = 0;               // ... of their two-wave variants (kernel_lat): + the W shares parked during the linearisation
-    bool compact = false;                     // `kernel` is a compact persistent kernel: grid = resident workgroups, needs ws + ticket
-    int grid_max = 0;                         // resident workgroups of the compact kernel on this device
-    double *ws = nullptr;                     // [grid_max][ws_doubles(N)] per-workgroup NLP workspace
+    tmpc::KernelSlot slot[tmpc::SLOT_COUNT];  // the solve kernels (tmpc::Slot)
+    double *ws = nullptr;                     // [resident][ws_doubles(N)] per-workgroup NLP workspace of the compact slot
     int *ticket = nullptr;
-    tmpc::SolveKernel kernel_small = nullptr; // compact shapes (N <= 21): the fast one-wave kernel, for launches of at most cp_min_B trajectories
-    size_t lds_bytes_small = 0;
-    int cp_min_B = 0;                         // what the fast one-wave kernel holds resident at once (workgroups per CU x CUs)
-    tmpc::SolveKernel kernel_cp2 = nullptr;   // optional two-wave compact variant (22 <= N <= 32): launches of more than cp2_min_B trajectories
-    size_t lds_bytes_cp2 = 0;
-    int cp2_min_B = 0;                        // what the fast two-wave kernel holds resident at once (workgroups per CU x CUs)
-    int cp2_threads = 128;
-    int dpad_cp = 0, dpad_cp2 = 0;            // Dims::dpad of the compact one-wave / two-wave kernel (pick_d_pad); the fast layouts do not pad
-    int lay_cp = 1, lay_cp2 = 1;              // the compact kernels' Hh layout (pick_compact*_kernel)
-    bool prio_cp = false, prio_cp2 = false;   // wave issue priorities (Dims::prio) for the compact one-wave / two-wave kernel: only when its residency puts two waves on
-                                              // every SIMD (8 waves per CU) -- with an odd count the waves that share a SIMD starve and set the makespan (tmpc_riccati.hpp)
-    int latency_mode = 0;                     // 0: throughput kernels, 1: two-wave variant, 2: parallel-in-time variant
-    // the instantiation in each kernel slot above (pick_*_kernel's names; "generic<CM>" for the generic kernel; empty: the slot is not filled) --
-    // tmpc_kernel_info reports them, tmpc_debug_profile profiles only the twin of the instantiation a solve runs
-    std::string name_default, name_small, name_cp2, name_lat1, name_lat2, name_lat3;
+    int latency_mode = 0;                     // 0: throughput kernels, 1-3: the latency slots (tmpc_set_latency_mode)
     bool throughput_mode = false;             // lane-per-trajectory kernels (tmpc_lanes.hip) instead of one wave per trajectory
     tmpc::lanes::Context *lanes = nullptr;    // their HBM workspace, created when the mode is first enabled
-    bool fast = false;
     // persistent per-slot solver state (tmpc_solve_iterations), allocated on first use
     double *st_z = nullptr, *st_pi = nullptr, *st_lamh = nullptr;
     int *st_stopped = nullptr;
@@ -542,109 +568,76 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
     d.riccati_form = dims->riccati_form;
     tmpc::derive_dims(d);
     d.split_rows = tmpc::split_rows_for(d.N, d.n_up + d.M) ? 1 : 0;
-    const char *nm_default = "", *nm_lat1 = "", *nm_lat2 = "", *nm_lat3 = "", *nm_cp = "", *nm_cp2 = "";
-    h->kernel = d.riccati_form == TMPC_RICCATI_SQUARE_ROOT ? tmpc::pick_sqrt_kernel(d, &h->threads, &nm_default) : tmpc::pick_fast_kernel(d, &h->threads, false, &nm_default);
-    if (d.riccati_form == TMPC_RICCATI_SQUARE_ROOT && !h->kernel) { delete h; return TMPC_ERR_INVALID; }       // (no square-root instantiation for this shape: never a silent other form)
+    using tmpc::KernelSlot;
+    KernelSlot *slot = h->slot, &def = h->slot[tmpc::SLOT_DEFAULT];
+    const bool schur = d.riccati_form == TMPC_RICCATI_SCHUR;      // the square-root form has its fast kernels only: no latency / compact variants
+    def.kernel = schur ? tmpc::pick_fast_kernel(d, &def) : tmpc::pick_sqrt_kernel(d, &def);
+    if (!schur && !def.kernel) { delete h; return TMPC_ERR_INVALID; }       // (no square-root instantiation for this shape: never a silent other form)
     if (const char *lm = lab_env("TMPC_LATENCY_MODE")) {      // experiments: latency variant regardless of the caller ("0" .. "3"; anything else is ignored)
         if (lm[0] >= '0' && lm[0] <= '3' && lm[1] == '\0') h->latency_mode = lm[0] - '0';
     }
-    h->fast = h->kernel != nullptr;
-    if (h->fast) h->lds_bytes = sizeof(double) * (size_t)tmpc::lds_doubles_fast(d.N, d.n_up + d.M);
-    else { const int sm = tmpc::stage_model(d); h->kernel = sm == 3 ? tmpc::tmpc_solve_kernel<3> : sm == 1 ? tmpc::tmpc_solve_kernel<1> : (sm == 2 ? tmpc::tmpc_solve_kernel<2> : tmpc::tmpc_solve_kernel<0>); h->lds_bytes = sizeof(double) * (size_t)tmpc::lds_doubles(d.N, d.n_up + d.M);
-           static const char *const generic_names[4] = {"generic<0>", "generic<1>", "generic<2>", "generic<3>"}; nm_default = generic_names[sm]; }
-    h->lds_bytes_fast = h->lds_bytes;
-    // two-wave (128-thread) fast kernels park one share of W per stage behind the layout while they linearise (linearise<.., 128>)
-    // (a shape whose default is the generic kernel may still have a four-wave tick kernel -- curvature-aware cost + Gaussian rows: the fast LAYOUT's size then)
-    h->lds_bytes_fast2 = (h->fast ? h->lds_bytes_fast : sizeof(double) * (size_t)tmpc::lds_doubles_fast(d.N, d.n_up + d.M)) + sizeof(double) * (size_t)d.N * tmpc::NP28;
-    if (h->fast && h->threads == 128) h->lds_bytes = h->lds_bytes_fast2;
+    const bool fast = def.kernel != nullptr;
+    if (!fast) {                                              // the generic kernel (rows in LDS): every shape; it is its own profiled twin
+        static const char *const generic_names[4] = {"generic<0>", "generic<1>", "generic<2>", "generic<3>"};
+        const int sm = tmpc::stage_model(d);
+        def.kernel = def.twin = sm == 3 ? tmpc::tmpc_solve_kernel<3> : sm == 1 ? tmpc::tmpc_solve_kernel<1> : (sm == 2 ? tmpc::tmpc_solve_kernel<2> : tmpc::tmpc_solve_kernel<0>);
+        def.name = generic_names[sm]; def.threads = tmpc::NT; def.kind = KernelSlot::GENERIC;
+    }
+    def.lds_bytes = tmpc::slot_lds(d, tmpc::SLOT_DEFAULT, def, 0);
     auto fail = [&](int code) { delete h; return code; };
     if (hipSetDevice(device) != hipSuccess) return fail(TMPC_ERR_HIP);
-    if (h->lds_bytes > 160 * 1024) return fail(TMPC_ERR_INVALID);
-    const bool schur = d.riccati_form == TMPC_RICCATI_SCHUR;      // the square-root form has its fast kernels only: no latency / compact variants
-    if (schur && h->fast && h->threads == tmpc::NT && (h->kernel_lat = tmpc::pick_latency_kernel(d, false, &nm_lat1)) != nullptr) {
-        if (hipFuncSetAttribute((const void *)h->kernel_lat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_fast2) != hipSuccess)
-            h->kernel_lat = nullptr;
+    if (def.lds_bytes > tmpc::LDS_CAP) return fail(TMPC_ERR_INVALID);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 0;
+    // the latency slots: beside a fast one-wave default; lat2 and lat3 also beside a two-wave one at N > 20, lat3 also beside the generic kernel of
+    // curvature-aware cost + Gaussian rows.  A slot whose LDS the kernel does not accept stays empty (lat1: one shape, far below the cap)
+    const bool one_wave = schur && fast && def.threads == tmpc::NT, lat23_ok = def.threads == tmpc::NT || d.N > 20;
+    int sl2 = 3, sl3 = 3;
+    if (one_wave) slot[tmpc::SLOT_LAT1].kernel = tmpc::pick_latency_kernel(d, &slot[tmpc::SLOT_LAT1]);
+    if (schur && fast && lat23_ok) slot[tmpc::SLOT_LAT2].kernel = tmpc::pick_scan_kernel(d, &slot[tmpc::SLOT_LAT2], &sl2);
+    if (schur && (fast || tmpc::stage_model(d) == 3) && lat23_ok)
+        slot[tmpc::SLOT_LAT3].kernel = tmpc::pick_quad_kernel(d, lab_env("TMPC_QUAD_AB") != nullptr, &slot[tmpc::SLOT_LAT3], &sl3);
+    for (int i = tmpc::SLOT_LAT1; i <= tmpc::SLOT_LAT3; i++) {
+        KernelSlot &s = slot[i];
+        if (!s.kernel) continue;
+        s.lds_bytes = tmpc::slot_lds(d, i, s, i == tmpc::SLOT_LAT3 ? sl3 : sl2);
+        if ((i != tmpc::SLOT_LAT1 && s.lds_bytes > tmpc::LDS_CAP) ||
+            hipFuncSetAttribute((const void *)s.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds_bytes) != hipSuccess)
+            s = KernelSlot{};
     }
-    if (schur && h->fast && (h->threads == tmpc::NT || d.N > 20) && (h->kernel_scan = tmpc::pick_scan_kernel(d, &h->scan_threads, &h->scan_sl, false, &nm_lat2)) != nullptr) {
-        h->lds_bytes_scan = h->lds_bytes_fast2 + sizeof(double) * (size_t)(h->scan_sl == 3 ? tmpc::scan::lds_doubles<3>(d.N) : tmpc::scan::lds_doubles<2>(d.N));
-        if (h->lds_bytes_scan > 160 * 1024) h->kernel_scan = nullptr;
-    }
-    if (h->kernel_scan) {
-        if (hipFuncSetAttribute((const void *)h->kernel_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_scan) != hipSuccess)
-            h->kernel_scan = nullptr;
-    }
-    int quad_sl = 3;
-    if (schur && (h->fast || tmpc::stage_model(d) == 3) && (h->threads == tmpc::NT || d.N > 20) && (h->kernel_quad = tmpc::pick_quad_kernel(d, false, lab_env("TMPC_QUAD_AB") != nullptr, &quad_sl, &nm_lat3)) != nullptr) {
-        // fast layout + the W shares of the split linearisation (wave 0's N x 28, the obstacle lanes' 36 N / 24 N: they lie inside the scan scratch, which is dead then) + the scan scratch
-        h->lds_bytes_quad = h->lds_bytes_fast2 + sizeof(double) * (size_t)(quad_sl == 3 ? tmpc::scan::lds_doubles<3>(d.N) : tmpc::scan::lds_doubles<2>(d.N));
-        if (h->lds_bytes_quad > 160 * 1024 ||
-            hipFuncSetAttribute((const void *)h->kernel_quad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_quad) != hipSuccess)
-            h->kernel_quad = nullptr;
-    }
-    if (tmpc::SolveKernel kc = (schur && h->fast && h->threads == tmpc::NT) ? tmpc::pick_compact_kernel(d, false, &h->lay_cp, &nm_cp) : nullptr) {
+    KernelSlot cp;
+    if (one_wave && (cp.kernel = tmpc::pick_compact_kernel(d, &cp)) != nullptr) {
         // the fast kernel of the shape (everything in LDS, four per CU) stays for launches it holds resident at once: bitwise the same results
         // (tests/test_gpu_compact2.py), a trajectory is ~10 % faster on it.  TMPC_COMPACT_MIN_B=0: the compact kernel for every launch (rounds 3-4)
-        int fast_per_cu = 0, cus = 0;
-        if (hipFuncSetAttribute((const void *)h->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&fast_per_cu, (const void *)h->kernel, 64, h->lds_bytes) == hipSuccess && fast_per_cu > 0 &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) {
-            h->kernel_small = h->kernel; h->lds_bytes_small = h->lds_bytes; h->cp_min_B = fast_per_cu * cus; h->name_small = nm_default;
-            if (const char *e = lab_env("TMPC_COMPACT_MIN_B")) h->cp_min_B = atoi(e);                                              // experiments
+        const int fast_per_cu = tmpc::blocks_per_cu(def.kernel, def.threads, def.lds_bytes);
+        if (fast_per_cu > 0 && cus > 0) {
+            slot[tmpc::SLOT_SMALL] = def;
+            slot[tmpc::SLOT_SMALL].bound = fast_per_cu * cus;
+            if (const char *e = lab_env("TMPC_COMPACT_MIN_B")) slot[tmpc::SLOT_SMALL].bound = atoi(e);                                 // experiments
         }
-        h->kernel = kc; h->compact = true; nm_default = nm_cp;
-        // padding of the packed rows' stage stride: only what keeps the residency (LDS is what bounds it: 8 x 20 KB at cfg 2)
-        auto lds_cp = [&](int pad) { return sizeof(double) * (size_t)tmpc::lds_doubles_compact(d.N, d.n_lin, d.n_up + d.M, 64, pad, h->lay_cp); };
-        auto per_cu_cp = [&](int pad) {
-            int n = 0;
-            if (hipFuncSetAttribute((const void *)kc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cp(pad)) != hipSuccess ||
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)kc, 64, lds_cp(pad)) != hipSuccess) return 0;
-            return n;
-        };
-        const int per_cu0 = per_cu_cp(0);
-        h->dpad_cp = tmpc::pick_d_pad(d.N, d.n_lin, d.n_up + d.M, 64, tmpc::DPAD_MAX, [&](int pad) { return pad == 0 || (per_cu0 > 0 && per_cu_cp(pad) == per_cu0); });
-        h->lds_bytes = lds_cp(h->dpad_cp);
+        def = cp;
+        tmpc::choose_compact_pad(d, tmpc::SLOT_DEFAULT, def);
     }
-    if (hipFuncSetAttribute((const void *)h->kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)h->lds_bytes) != hipSuccess)
+    if (hipFuncSetAttribute((const void *)def.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)def.lds_bytes) != hipSuccess)
         return fail(TMPC_ERR_NO_DEVICE);
-    if (schur && h->fast && h->threads == 128 && !h->compact && (h->kernel_cp2 = tmpc::pick_compact2_kernel(d, &h->lay_cp2, &h->cp2_threads, &nm_cp2)) != nullptr) {
-        {
-            auto lds_cp2 = [&](int pad) { return sizeof(double) * (size_t)tmpc::lds_doubles_compact(d.N, d.n_lin, d.n_up + d.M, h->cp2_threads, pad, h->lay_cp2); };
-            auto per_cu_cp2 = [&](int pad) {
-                int n = 0;
-                if (hipFuncSetAttribute((const void *)h->kernel_cp2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cp2(pad)) != hipSuccess ||
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)h->kernel_cp2, h->cp2_threads, lds_cp2(pad)) != hipSuccess) return 0;
-                return n;
-            };
-            const int per_cu0 = per_cu_cp2(0);
-            h->dpad_cp2 = tmpc::pick_d_pad(d.N, d.n_lin, d.n_up + d.M, h->cp2_threads, tmpc::DPAD_MAX, [&](int pad) { return pad == 0 || (per_cu0 > 0 && per_cu_cp2(pad) == per_cu0); });
-            h->lds_bytes_cp2 = lds_cp2(h->dpad_cp2);
-        }
-        int per_cu = 0, fast_per_cu = 0, cus = 0;
-        if (hipFuncSetAttribute((const void *)h->kernel_cp2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes_cp2) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)h->kernel_cp2, h->cp2_threads, h->lds_bytes_cp2) != hipSuccess || per_cu <= 0 ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&fast_per_cu, (const void *)h->kernel, 128, h->lds_bytes) != hipSuccess || fast_per_cu <= 0 ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0 || per_cu <= fast_per_cu)
-            h->kernel_cp2 = nullptr;                         // (no gain in residency: the fast kernel stays alone)
+    if (def.kind == KernelSlot::COMPACT) {
+        const int per_cu = tmpc::blocks_per_cu(def.kernel, def.threads, def.lds_bytes);
+        if (per_cu <= 0 || cus <= 0) return fail(TMPC_ERR_HIP);
+        tmpc::set_resident(def, per_cu, cus);
+    }
+    KernelSlot &cp2 = slot[tmpc::SLOT_CP2];
+    if (schur && def.kind == KernelSlot::FAST && def.threads == 128 && (cp2.kernel = tmpc::pick_compact2_kernel(d, &cp2)) != nullptr) {
+        tmpc::choose_compact_pad(d, tmpc::SLOT_CP2, cp2);
+        const int per_cu = tmpc::blocks_per_cu(cp2.kernel, cp2.threads, cp2.lds_bytes);
+        const int fast_per_cu = tmpc::blocks_per_cu(def.kernel, def.threads, def.lds_bytes);
+        if (fast_per_cu <= 0 || cus <= 0 || per_cu <= fast_per_cu)
+            cp2 = KernelSlot{};                              // (no gain in residency: the fast kernel stays alone)
         else {
-            if (const char *e = lab_env("TMPC_COMPACT_PER_CU")) { const int v = atoi(e); if (v > 0 && v < per_cu) per_cu = v; }   // experiments
-            h->grid_max = per_cu * cus; h->cp2_min_B = fast_per_cu * cus; h->prio_cp2 = per_cu * (h->cp2_threads / 64) == 8;
-            if (const char *e = lab_env("TMPC_COMPACT2_MIN_B")) h->cp2_min_B = atoi(e);                                            // experiments
+            cp2.bound = fast_per_cu * cus;
+            if (const char *e = lab_env("TMPC_COMPACT2_MIN_B")) cp2.bound = atoi(e);                                                   // experiments
+            tmpc::set_resident(cp2, per_cu, cus);
         }
     }
-    if (h->compact) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)h->kernel, 64, h->lds_bytes) != hipSuccess || per_cu <= 0 ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0)
-            return fail(TMPC_ERR_HIP);
-        if (const char *e = lab_env("TMPC_COMPACT_PER_CU")) { const int v = atoi(e); if (v > 0 && v < per_cu) per_cu = v; }   // experiments
-        h->grid_max = per_cu * cus; h->prio_cp = per_cu == 8;
-    }
-    h->name_default = nm_default;
-    if (h->kernel_cp2) h->name_cp2 = nm_cp2;
-    if (h->kernel_lat) h->name_lat1 = nm_lat1;
-    if (h->kernel_scan) h->name_lat2 = nm_lat2;
-    if (h->kernel_quad) h->name_lat3 = nm_lat3;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(TMPC_ERR_HIP);
     const size_t N = d.N, B = B_max;
     bool ok = true;
@@ -686,8 +679,8 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
     ok &= hipMalloc(&h->d_weight, B * 8) == hipSuccess;
     ok &= hipMalloc(&h->d_best, 4) == hipSuccess;
     ok &= hipMalloc(&h->d_disabled, B) == hipSuccess;
-    if (h->compact || h->kernel_cp2) {
-        ok &= hipMalloc(&h->ws, (size_t)h->grid_max * tmpc::ws_doubles(d.N, h->kernel_cp2 != nullptr && h->cp2_threads == 128) * 8) == hipSuccess;
+    if (const KernelSlot *p = def.kind == KernelSlot::COMPACT ? &def : cp2.kernel ? &cp2 : nullptr) {
+        ok &= hipMalloc(&h->ws, (size_t)p->resident * tmpc::ws_doubles(d.N, p->threads == 128) * 8) == hipSuccess;
         ok &= hipMalloc(&h->ticket, 8 * 4) == hipSuccess;         // one work counter per XCD (next_trajectory)
     }
     if (!ok) { tmpc_destroy(h); return TMPC_ERR_HIP; }
@@ -764,21 +757,18 @@ int tmpc_set_batch_device(tmpc_handle *h, int32_t B, const void *d_xinit, const 
     return TMPC_OK;
 }
 
-// Which kernel slot a launch of the current batch runs (launch_solve; tmpc_debug_profile profiles the twin of that slot's instantiation).
-struct LaunchSlot { bool lat3, lat2, lat, cp2, small, cp; };
-static LaunchSlot launch_slot(const tmpc_handle *h)
+// The slot (tmpc::Slot) a launch of the current batch runs (launch_solve; tmpc_debug_profile profiles the twin of that slot's instantiation).
+static int launch_slot(const tmpc_handle *h)
 {
-    LaunchSlot k;
-    k.lat3 = h->kernel_quad && h->latency_mode == 3;
-    k.lat2 = !k.lat3 && h->kernel_scan && h->latency_mode >= 2;          // (mode 3 without a four-wave variant runs as mode 2, ...
-    k.lat = !k.lat3 && !k.lat2 && h->kernel_lat && h->latency_mode != 0;  //  ... mode 2 without a scan variant as the two-wave variant)
+    // mode 3 without a four-wave variant runs as mode 2, mode 2 without a scan variant as mode 1
+    for (int m = h->latency_mode; m >= 1; m--)
+        if (h->slot[tmpc::SLOT_LAT1 + m - 1].kernel) return tmpc::SLOT_LAT1 + m - 1;
     // compact <-> fast kernels of a shape compute bit for bit the same, so the launch size may choose between them: the fast kernel while it
     // holds the whole launch resident (lower latency per trajectory), the compact one (twice the residency) above that
-    const bool any_lat = k.lat || k.lat2 || k.lat3;
-    k.cp2 = h->kernel_cp2 && !any_lat && h->B > h->cp2_min_B;
-    k.small = h->compact && h->kernel_small && !any_lat && h->B <= h->cp_min_B;
-    k.cp = (h->compact && !any_lat && !k.small) || k.cp2;
-    return k;
+    const tmpc::KernelSlot &cp2 = h->slot[tmpc::SLOT_CP2], &small = h->slot[tmpc::SLOT_SMALL];
+    if (cp2.kernel && h->B > cp2.bound) return tmpc::SLOT_CP2;
+    if (small.kernel && h->B <= small.bound) return tmpc::SLOT_SMALL;
+    return tmpc::SLOT_DEFAULT;
 }
 
 // One launch over the current batch: n_iter RTI iterations per trajectory + completeOneIteration.  st_flags: ST_* (0 = fresh
@@ -800,15 +790,13 @@ static int launch_solve(tmpc_handle *h, int n_iter, int st_flags)
         dd.n_sqp = n_iter;
         tmpc::StateIO io{h->st_z, h->st_pi, h->st_lamh, h->st_stopped, st_flags, h->ws, h->ticket, (h->slots_set && h->slots_B == h->B) ? h->d_slot : nullptr, h->st_has,
                          (h->share_B == h->B) ? h->d_share : nullptr};      // (a map given for another batch size is not applied)
-        const LaunchSlot k = launch_slot(h);
-        const bool lat3 = k.lat3, lat2 = k.lat2, lat = k.lat, cp2 = k.cp2, small = k.small, cp = k.cp;
-        dd.prio = cp2 ? h->prio_cp2 : (cp ? h->prio_cp : false);
-        dd.dpad = cp2 ? h->dpad_cp2 : (cp ? h->dpad_cp : 0);      // (layout only: results do not depend on it)
-        if (cp) TMPC_HIP_CHECK(h, hipMemsetAsync(h->ticket, 0, 8 * 4, h->stream));    // the persistent launch's work counters (one per XCD)
-        hipLaunchKernelGGL(lat3 ? h->kernel_quad : lat2 ? h->kernel_scan : lat ? h->kernel_lat : cp2 ? h->kernel_cp2 : small ? h->kernel_small : h->kernel,
-                           dim3(cp ? (h->B < h->grid_max ? h->B : h->grid_max) : h->B),   // (persistent launch: at most the resident workgroups)
-                           dim3(lat3 ? 256 : lat2 ? h->scan_threads : lat ? 128 : cp2 ? h->cp2_threads : ((cp || small) ? 64 : h->threads)),
-                           lat3 ? h->lds_bytes_quad : lat2 ? h->lds_bytes_scan : lat ? h->lds_bytes_fast2 : cp2 ? h->lds_bytes_cp2 : small ? h->lds_bytes_small : h->lds_bytes, h->stream, dd, h->B,
+        const tmpc::KernelSlot &k = h->slot[launch_slot(h)];
+        const bool persistent = k.kind == tmpc::KernelSlot::COMPACT;
+        dd.prio = k.prio;
+        dd.dpad = k.dpad;      // (layout only: results do not depend on it)
+        if (persistent) TMPC_HIP_CHECK(h, hipMemsetAsync(h->ticket, 0, 8 * 4, h->stream));    // the persistent launch's work counters (one per XCD)
+        hipLaunchKernelGGL(k.kernel, dim3(persistent ? (h->B < k.resident ? h->B : k.resident) : h->B),   // (persistent launch: at most the resident workgroups)
+                           dim3(k.threads), k.lds_bytes, h->stream, dd, h->B,
                            h->xinit, h->x0, h->params, h->xtraj, h->utraj, h->pobj, h->exit_code, h->qp_status,
                            h->sqp_iter, h->res_eq, h->qp_iter, (long long *)nullptr, io);
         TMPC_HIP_CHECK(h, hipGetLastError());
@@ -919,26 +907,21 @@ int tmpc_set_latency_mode(tmpc_handle *h, int32_t on)
     if (!h) return TMPC_ERR_INVALID;
     if (on < 0 || on > 3) return TMPC_ERR_INVALID;
     h->latency_mode = on;
-    if (on == 3) return h->kernel_quad ? TMPC_OK : 1;              // 1: accepted, but this shape has no such variant (mode 3 then runs as mode 2, mode 2 as mode 1, if those exist)
-    if (on == 2) return h->kernel_scan ? TMPC_OK : 1;
-    return (on == 1 && !h->kernel_lat) ? 1 : TMPC_OK;
+    // 1: accepted, but this shape has no such variant (mode 3 then runs as mode 2, mode 2 as mode 1, if those exist)
+    return (on == 0 || h->slot[tmpc::SLOT_LAT1 + on - 1].kernel) ? TMPC_OK : 1;
 }
 
 int tmpc_latency_mode_capacity(tmpc_handle *h, int32_t mode)
 {
     if (!h || mode < 0 || mode > 3) return TMPC_ERR_INVALID;
     if (hipSetDevice(h->device) != hipSuccess) return TMPC_ERR_HIP;
-    const void *k = nullptr; int threads = 64; size_t lds = 0;
-    if (mode == 3) { if (!h->kernel_quad) return 0; k = (const void *)h->kernel_quad; threads = 256; lds = h->lds_bytes_quad; }
-    else if (mode == 2) { if (!h->kernel_scan) return 0; k = (const void *)h->kernel_scan; threads = h->scan_threads; lds = h->lds_bytes_scan; }
-    else if (mode == 1) { if (!h->kernel_lat) return 0; k = (const void *)h->kernel_lat; threads = 128; lds = h->lds_bytes_fast2; }
-    else {
-        // the throughput kernels of the handle: the resident set of the persistent (compact) launch, or of the plain kernel
-        if (h->compact || h->kernel_cp2) return h->grid_max;
-        k = (const void *)h->kernel; threads = h->threads; lds = h->lds_bytes;
-    }
+    // mode 0: the throughput kernels of the handle -- the resident set of the persistent (compact) launch, or of the plain kernel
+    const int i = mode ? tmpc::SLOT_LAT1 + mode - 1 : h->slot[tmpc::SLOT_CP2].kernel ? tmpc::SLOT_CP2 : tmpc::SLOT_DEFAULT;
+    const tmpc::KernelSlot &k = h->slot[i];
+    if (!k.kernel) return 0;
+    if (k.kind == tmpc::KernelSlot::COMPACT) return k.resident;
     int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, threads, lds) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k.kernel, k.threads, k.lds_bytes) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) { h->err = "tmpc_latency_mode_capacity: occupancy query failed"; return TMPC_ERR_HIP; }
     // variant 3 is built for ONE workgroup per CU (a wave on every SIMD): a second one fits (LDS, registers) but shares the SIMDs, and the launch is then
     // slower than variant 2's (measured, cfg 4's share of 8 = 512 trajectories: 1.79 ms against 1.31 ms, profiles/round6_cfg4_share8_*): its capacity is what
@@ -1174,22 +1157,24 @@ int tmpc_get_stream(tmpc_handle *h, void **stream)
 int tmpc_kernel_info(const tmpc_handle *h, char *buf, int32_t capacity)
 {
     if (!h || !buf || capacity <= 0) return TMPC_ERR_INVALID;
-    const char *family = h->throughput_mode ? "lanes (one lane per trajectory)"
-                         : !h->fast        ? "generic (one wave per trajectory, rows in LDS)"
-                         : !h->compact     ? (h->threads == 128 ? "fast, two waves per trajectory" : "fast (one wave per trajectory)")
-                                           : "compact (one wave per trajectory, two waves per SIMD)";
-    const std::string sm = (h->compact && h->kernel_small && h->cp_min_B > 0) ? "; launches of at most " + std::to_string(h->cp_min_B) + " trajectories: fast one-wave variant (LDS " +
-                                                                                std::to_string(h->lds_bytes_small) + " B, one workgroup per trajectory)" : "";
-    const std::string cp2 = h->kernel_cp2 ? "; launches of more than " + std::to_string(h->cp2_min_B) + " trajectories: compact two-wave variant (LDS " +
-                                            std::to_string(h->lds_bytes_cp2) + " B, persistent launch, resident workgroups " + std::to_string(h->grid_max) + ")" : "";
-    // the instantiation of every filled slot (pick_*_kernel names): default (the compact kernel of a compact handle), small-launch twin, compact two-wave, latency modes 1-3
-    std::string names = "; kernels: default=" + h->name_default;
-    const std::pair<const char *, const std::string *> slots[] = {{"small", &h->name_small}, {"cp2", &h->name_cp2}, {"lat1", &h->name_lat1},
-                                                                  {"lat2", &h->name_lat2}, {"lat3", &h->name_lat3}};
-    for (const auto &sl : slots) if (!sl.second->empty()) names += std::string(", ") + sl.first + "=" + *sl.second;
+    using tmpc::KernelSlot;
+    const KernelSlot &def = h->slot[tmpc::SLOT_DEFAULT], &small = h->slot[tmpc::SLOT_SMALL], &cp2 = h->slot[tmpc::SLOT_CP2];
+    const bool compact = def.kind == KernelSlot::COMPACT;
+    const char *family = h->throughput_mode                ? "lanes (one lane per trajectory)"
+                         : def.kind == KernelSlot::GENERIC ? "generic (one wave per trajectory, rows in LDS)"
+                         : !compact                        ? (def.threads == 128 ? "fast, two waves per trajectory" : "fast (one wave per trajectory)")
+                                                           : "compact (one wave per trajectory, two waves per SIMD)";
+    const std::string sm = (small.kernel && small.bound > 0) ? "; launches of at most " + std::to_string(small.bound) + " trajectories: fast one-wave variant (LDS " +
+                                                               std::to_string(small.lds_bytes) + " B, one workgroup per trajectory)" : "";
+    const std::string cp = cp2.kernel ? "; launches of more than " + std::to_string(cp2.bound) + " trajectories: compact two-wave variant (LDS " +
+                                        std::to_string(cp2.lds_bytes) + " B, persistent launch, resident workgroups " + std::to_string(cp2.resident) + ")" : "";
+    // the instantiation of every filled slot, by the slot's label (tmpc::Slot)
+    static const char *const label[tmpc::SLOT_COUNT] = {"default", "small", "cp2", "lat1", "lat2", "lat3"};
+    std::string names = std::string("; kernels: default=") + def.name;
+    for (int i = tmpc::SLOT_SMALL; i < tmpc::SLOT_COUNT; i++) if (h->slot[i].kernel) names += std::string(", ") + label[i] + "=" + h->slot[i].name;
     const int n = snprintf(buf, (size_t)capacity, "%s; trajectories per workgroup %d; LDS %zu B per workgroup; %s%s%s", family, 1,
-                           h->lds_bytes, h->compact ? (std::string("persistent launch, resident workgroups ") + std::to_string(h->grid_max)).c_str()
-                                                    : "one workgroup per trajectory", (cp2 + sm).c_str(), names.c_str());
+                           def.lds_bytes, compact ? (std::string("persistent launch, resident workgroups ") + std::to_string(def.resident)).c_str()
+                                                  : "one workgroup per trajectory", (cp + sm).c_str(), names.c_str());
     return n < capacity ? n : capacity - 1;
 }
 
@@ -1484,32 +1469,20 @@ int tmpc_debug_profile(tmpc_handle *h, int64_t *cycles, int32_t n_phases)
     TMPC_HIP_CHECK(h, bufs.alloc(&dp_, n * 8));
     long long *dp = (long long *)dp_;
     TMPC_HIP_CHECK(h, hipMemset(dp, 0, n * 8));
-    // The instrumented twin of the instantiation a solve of the current batch runs (launch_slot): the generic kernel profiles itself, the fast kernels
-    // have profiled twins for some shapes, a compact kernel is profiled through the fast kernel of its shape (bitwise the same results, one wave per
-    // SIMD).  A slot without an exact twin is refused -- never another instantiation in its place.  LDS: what the twin's thread count needs.
-    const LaunchSlot k = launch_slot(h);
-    const std::string &running = k.lat3 ? h->name_lat3 : k.lat2 ? h->name_lat2 : k.lat ? h->name_lat1
-                               : h->compact ? h->name_small : h->name_default;  // (the fast kernel of a compact shape; cp2: the default slot holds it)
-    tmpc::SolveKernel pk = nullptr;
-    int thr = h->threads;
-    size_t lds = h->lds_bytes;
-    const char *twin = "";
-    if (!h->fast && !k.lat3) pk = h->kernel;
-#ifndef TMPC_GENERATED_STAGE
-    else if (k.lat3) { pk = tmpc::pick_quad_kernel(h->d, true, false, nullptr, &twin); thr = 256; lds = h->lds_bytes_quad; }
-    else if (k.lat2) { int sl = 3; pk = tmpc::pick_scan_kernel(h->d, &thr, &sl, true, &twin); lds = h->lds_bytes_scan; }
-    else if (k.lat) { pk = tmpc::pick_latency_kernel(h->d, true, &twin); thr = 128; lds = h->lds_bytes_fast2; }
-#endif
-    else if (h->d.riccati_form == TMPC_RICCATI_SCHUR) { pk = tmpc::pick_fast_kernel(h->d, &thr, true, &twin); lds = thr == 128 ? h->lds_bytes_fast2 : h->lds_bytes_fast; }
-    if (h->fast || k.lat3) {
-        if (!pk || running != twin) {
-            h->err = "tmpc_debug_profile: no profiled twin of " + (running.empty() ? std::string("this kernel") : running) + " (the launch of " + std::to_string(h->B) +
-                     " trajectories in latency mode " + std::to_string(h->latency_mode) + ")";
-            return TMPC_ERR_INVALID;
-        }
-        TMPC_HIP_CHECK(h, hipFuncSetAttribute((const void *)pk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // The instrumented twin of the instantiation a solve of the current batch runs (launch_slot), with that slot's threads and LDS: the generic kernel
+    // profiles itself, the fast kernels have profiled twins for some shapes, a compact slot is profiled through the fast kernel of its shape (bitwise the
+    // same results, one wave per SIMD): the small slot's, or for the two-wave one the default slot's.  A slot without a twin is refused -- never another
+    // instantiation in its place.
+    int slot = launch_slot(h);
+    if (h->slot[slot].kind == tmpc::KernelSlot::COMPACT) slot = slot == tmpc::SLOT_CP2 ? tmpc::SLOT_DEFAULT : tmpc::SLOT_SMALL;
+    const tmpc::KernelSlot &k = h->slot[slot];
+    if (!k.twin) {
+        h->err = std::string("tmpc_debug_profile: no profiled twin of ") + (*k.name ? k.name : "this kernel") + " (the launch of " + std::to_string(h->B) +
+                 " trajectories in latency mode " + std::to_string(h->latency_mode) + ")";
+        return TMPC_ERR_INVALID;
     }
-    hipLaunchKernelGGL(pk, dim3(h->B), dim3(thr), lds, h->stream, h->d, h->B,
+    TMPC_HIP_CHECK(h, hipFuncSetAttribute((const void *)k.twin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds_bytes));
+    hipLaunchKernelGGL(k.twin, dim3(h->B), dim3(k.threads), k.lds_bytes, h->stream, h->d, h->B,
                        h->xinit, h->x0, h->params, h->xtraj, h->utraj, h->pobj, h->exit_code, h->qp_status,
                        h->sqp_iter, h->res_eq, h->qp_iter, dp, tmpc::StateIO{nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr});
     TMPC_HIP_CHECK(h, hipGetLastError());
