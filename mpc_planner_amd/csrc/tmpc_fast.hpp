@@ -74,13 +74,8 @@ __device__ __forceinline__ Lds carve_fast(double *s, const Dims &d)
 // one-wave shapes; 3 -- 30 doubles, y inside the block, no y array -- for (12,12) (seven per CU with 69 bytes to spare: 29 does not fit, 30 minus the y array does);
 // 1 -- the bare 28 -- for the run-time shapes (their LDS size is not known here) and the two-wave instantiations: a wave of theirs holds 16 stages (two-way
 // conflicts at most), measured 0 ((20,8), cfg 3) and -2 % ((5,5), the jackal default) with the padded stride (profiles/round5_r_layout_check.jsonl).
-// (-DTMPC_EXP_Y_IN_BLOCK, A/B builds of the compact translation unit only: layout 3 for every tuned one-wave shape -- round-5 verdict next-2 (b): for (8,8)
-// the 30-double blocks cost 21 doubles and retire the 40-double y array, so the eight-per-CU budget holds; profiles/round6_saturated_levers_ab.jsonl)
-#ifdef TMPC_EXP_Y_IN_BLOCK
-__host__ __device__ constexpr int compact_layout(int NLIN, int MM, int NTH) { return (NLIN >= 0 && NTH == 64) ? 3 : 1; }
-#else
+// (Layout 3 for every tuned one-wave shape was measured and not taken: profiles/round6_saturated_levers_ab.jsonl.)
 __host__ __device__ constexpr int compact_layout(int NLIN, int MM, int NTH) { return (NLIN >= 0 && NTH == 64) ? ((NLIN == 12 && MM == 12) ? 3 : 2) : 1; }
-#endif
 __host__ __device__ constexpr int compact_hstride(int layout) { return layout == 2 ? NP28 + 1 : (layout == 3 ? NP28 + 2 : NP28); }
 __host__ __device__ inline int lds_doubles_compact(int N, int n_pair, int nh, int nth = 64, int dpad = 0, int layout = 1)
 {
@@ -143,7 +138,7 @@ struct SoloT {
     template <int NTH, int CP>
     __device__ __forceinline__ void solve(const Lds &L, const Dims &d, int tl, int sw, int, int phase, bool) const
     {
-        if (phase == 1) riccati_forward<NTH, CP, SQ>(L, d, tl, sw); else riccati_solve<NTH, CP, SQ>(L, d, tl, sw);
+        if (phase == 1) riccati_forward<NTH, CP>(L, d, tl, sw); else riccati_solve<NTH, CP, SQ>(L, d, tl, sw);
     }
 };
 using Solo = SoloT<false>;
@@ -225,16 +220,8 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
     constexpr bool OCC2 = CP;                       // compact instantiations are built for two waves per SIMD (<= 256 registers)
     // one-wave kernels (three lanes per stage; a stage may straddle two 16-lane rows): the same pre-reduction by two WAVE shifts (DPP wave_shl:1) -- the
     // saturated compact kernel +0.5 % (profiles/round6_one_wave_shift_prereduce_ab.jsonl: three-way same-address ds_add_f64 were 2.6 % of the LDS unit's cycles)
-#ifdef TMPC_EXP_NO_WSHL3
-    constexpr bool TSUM = false;
-#else
     constexpr bool TSUM = LPS == 3 || (LPS == 6 && NTH == 128);      // (six lanes per stage -- the two-wave latency kernels of N <= 21 --: two triples, two adds per entry)
-#endif
-#ifdef TMPC_EXP_NO_QSUM4
-    constexpr bool QSUM = NTH == 256;
-#else
     constexpr bool QSUM = NTH == 256 || (NTH == 128 && LPS == 4);      // four-wave kernels (12 or 8 lanes per stage), two-wave kernels at four: the stage sums are pre-reduced per aligned quad
-#endif
     static_assert(!QSUM || LPS % 4 == 0, "quad pre-reduction: whole quads per stage");
     // compile-time constants for the tuned shapes, kernel arguments for runtime-shape instantiations
     const int NH = C::RT ? L.nh : C::NH, NR = NH + 14, NLIN_ = C::RT ? d.n_up : NLIN;
@@ -353,11 +340,6 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
         if constexpr (C::template KIND<s> == 1) { c0 = 0.0; c1 = 0.0; c2 = 0.0; }
         else {
             const double *Dr_ = L.D + DIDX(s); c0 = Dr_[0]; c1 = Dr_[1];
-#ifdef TMPC_EXP_C2_LITERAL
-            // A/B (round 6): a slot whose rows are all packed topology rows has no third entry -- the load of the zero triple's 0.0 is an LDS instruction per slot
-            // and pass; the literal is the same value (valid only while n_lin == NLIN: the tuned shapes without scenario / decomp rows)
-            if constexpr (CP && !C::RT && C::template KIND<s> == 0 && LPS * s + LPS - 1 < NLIN) c2 = 0.0; else
-#endif
             c2 = L.D[DIDX2(s)];
         }
     };
@@ -663,12 +645,7 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
         // ---- corrector rhs: gh = rg + sum c (qt + d rd) ----
         // Round 6: the predictor's right-hand side is still in gh (the factorisation and the solves only read it) and differs from the corrector's by
         // sum c (qt - lam) -- gh_pred = rg0 + sum c d rd, gh_corr = rg0 - sum lam c + sum c (qt + d rd) --, so the row pass ADDS that difference in place: no
-        // copy of rg into gh, no barrier before the pass, no row residuals in it (-DTMPC_EXP_RHS_COPY rebuilds the copy form; the sums associate differently:
-        // rounding level)
-#ifdef TMPC_EXP_RHS_COPY
-        for (int e = tl; e < (N + 1) * NV; e += NT) L.gh[e] = L.rg[e];
-        team.sync();
-#endif
+        // copy of rg into gh, no barrier before the pass, no row residuals in it (the sums associate differently from the copy form: rounding level)
         ROW_PASS_BEGIN();
         {
             double cs0 = 0, cs1 = 0, cs2 = 0;
@@ -683,12 +660,7 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
                 qt[s] = a ? lam[s] + (dta * dl - sigma * mu) * INVT(s) : 0.0;
                 double c0s, c1s, c2s;
                 coef(s_, c0s, c1s, c2s);
-#ifdef TMPC_EXP_RHS_COPY
-                const double rr = rowdot(s_, c0s, c1s, c2s, vx, vy, vp, L.v + mul24(kk, NV)) - sb[s] - t[s];
-                const double w = qt[s] + lam[s] * INVT(s) * (a ? rr : 0.0);
-#else
                 const double w = a ? qt[s] - lam[s] : 0.0;
-#endif
                 if constexpr (K != 1) { cs0 += w * c0s; cs1 += w * c1s; cs2 += w * c2s; }
                 if constexpr (K != 0) { if (a && (K == 1 || (box >> s & 1))) lds_add(&L.gh[mul24(k, NV) + VARK(s_)], w * CUK(s_)); }
             });
@@ -785,7 +757,7 @@ void tmpc_solve_fast_kernel(Dims d, int B, const double *__restrict__ xinit,
     // loadWarmstart, or the iterate the handle holds; fresh or kept multipliers (StateIO, tmpc_solve.hip)
     for (int e = tid; e < (N + 1) * NV; e += NT) {
         const int k = e / NV, i = e - k * NV;
-        L.z[e] = (slot_flags(io, b) & ST_KEEP_ITERATE) ? io.z[(size_t)slot_of(io, b) * (N + 1) * NV + e] : TMPC_LD_IN(x0 + ((size_t)b * (N + 1) + k) * ext_nv(d) + i);
+        L.z[e] = (slot_flags(io, b) & ST_KEEP_ITERATE) ? io.z[(size_t)slot_of(io, b) * (N + 1) * NV + e] : *(x0 + ((size_t)b * (N + 1) + k) * ext_nv(d) + i);
     }
     for (int e = tid; e < (N + 1) * NX; e += NT) L.pi[e] = (slot_flags(io, b) & ST_KEEP_MULTIPLIERS) ? io.pi[(size_t)slot_of(io, b) * (N + 1) * NX + e] : 0.0;
     for (int e = tid; e < N * NHk; e += NT) L.lamh[e] = (slot_flags(io, b) & ST_KEEP_MULTIPLIERS) ? io.lamh[(size_t)slot_of(io, b) * N * NHk + e] : 0.0;
@@ -898,7 +870,7 @@ void tmpc_solve_compact_kernel(Dims d, int B, const double *__restrict__ xinit,
 
         for (int e = tid; e < (N + 1) * NV; e += NT) {
             const int k = e / NV, i = e - k * NV;
-            L.z[e] = (slot_flags(io, b) & ST_KEEP_ITERATE) ? io.z[(size_t)slot_of(io, b) * (N + 1) * NV + e] : TMPC_LD_IN(x0 + ((size_t)b * (N + 1) + k) * ext_nv(d) + i);
+            L.z[e] = (slot_flags(io, b) & ST_KEEP_ITERATE) ? io.z[(size_t)slot_of(io, b) * (N + 1) * NV + e] : *(x0 + ((size_t)b * (N + 1) + k) * ext_nv(d) + i);
         }
         for (int e = tid; e < (N + 1) * NX; e += NT) L.pi[e] = (slot_flags(io, b) & ST_KEEP_MULTIPLIERS) ? io.pi[(size_t)slot_of(io, b) * (N + 1) * NX + e] : 0.0;
         for (int e = tid; e < N * NHk; e += NT) L.lamh[e] = (slot_flags(io, b) & ST_KEEP_MULTIPLIERS) ? io.lamh[(size_t)slot_of(io, b) * N * NHk + e] : 0.0;

@@ -358,11 +358,7 @@ __device__ __forceinline__ void static_for(F &&f)
 // index, both far below 2^24 -> v_mul_u32_u24 / v_mad_u32_u24 (full rate).  uni: a wave-uniform product is kept in an SGPR (s_mul_i32) and only
 // added on the vector side.
 __device__ __forceinline__ int mul24(int a, int b) { return (int)__umul24((unsigned)a, (unsigned)b); }
-#ifdef TMPC_EXP_NO_UNI
-__device__ __forceinline__ int uni(int x) { return x; }
-#else
 __device__ __forceinline__ int uni(int x) { asm volatile("" : "+s"(x)); return x; }
-#endif
 // 1/sqrt(d) for d > 0: v_rsq_f64 seed (5e-8 relative, measured) + one third-order (Halley) step: with e = 1 - d y^2,
 // y (1 + e/2 + 3 e^2/8) leaves an error of order e^3 -- full double precision in five dependent operations, where two Newton steps
 // take eight (this sits on the critical chain of the Cholesky: seven pivots per stage)
@@ -614,20 +610,6 @@ __device__ int ipm_solve(const Lds &L, const Dims &d, int tid, int *iters_out, P
     return status;
 }
 
-// four-wave linearisation: parts of stage_linearise on wave 1 | waves 2, 3 (-DTMPC_EXP_QUAD_ROWS_ON_COST_WAVE: the first form, halfspace / scenario rows next to the cost)
-#ifdef TMPC_EXP_QUAD_ROWS_ON_COST_WAVE
-#define TMPC_QUAD_COST_PART 4
-#define TMPC_QUAD_ROWS_PART 5
-#else
-#define TMPC_QUAD_COST_PART 6
-#define TMPC_QUAD_ROWS_PART 7
-#endif
-// the latency kernels' (two / four waves per trajectory) 4 x 4 block: paired round-robin sweep (mirror_n, tmpc_stage.hpp)
-#ifdef TMPC_EXP_NO_PAIR4
-constexpr bool MIRROR_PAIR = false;
-#else
-constexpr bool MIRROR_PAIR = true;
-#endif
 // MIRROR of the one-wave kernels (round 5).  Lane k < N linearises stage k; the other lanes of the wave are idle copies.  With a zero disc
 // offset the Lagrangian Hessian is block diagonal under {a, w, psi, v} | {x, y, spline} (mirror7), and the two blocks' Jacobi iterations are
 // independent: lane k keeps the 4 x 4 block, lane N + k takes the 3 x 3 block of stage k -- padded to 4 x 4 with a zero row / column, which the
@@ -760,7 +742,7 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
                     for (int j = 0; j <= i; j++) W0s[pidx(i, j)] = W[i][j];
             }
         } else if (wv == 1) {                                    // the cost
-            stage_linearise<CM>(d, z, p, 1, 0.0, 0.0, lamh, sink, W, g, BA, xn, slack, nullptr, own_delta, TMPC_QUAD_COST_PART);
+            stage_linearise<CM>(d, z, p, 1, 0.0, 0.0, lamh, sink, W, g, BA, xn, slack, nullptr, own_delta, 6);
             if (owner) {
 #pragma unroll
                 for (int i = 0; i < NV; i++) L.g[k * NV + i] = g[i];
@@ -771,7 +753,7 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
             }
         } else {                                                 // the rows (halfspace, scenario / decomp, obstacle): lane (wave, group) takes rows first, first + 2 G, ... of each class
             const int first_ = (wv - 2) * G + grp;
-            stage_linearise<CM>(d, z, p, 1, 0.0, 0.0, lamh, sink, W, g, BA, xn, slack, nullptr, own_delta, TMPC_QUAD_ROWS_PART, [&]() { return first_; }, 2 * G, true);
+            stage_linearise<CM>(d, z, p, 1, 0.0, 0.0, lamh, sink, W, g, BA, xn, slack, nullptr, own_delta, 7, [&]() { return first_; }, 2 * G, true);
             if (rowlane) {
                 double *x = Wes + (first_ * N + k) * 6;
                 x[0] = W[ZX][ZX]; x[1] = W[ZX][ZY]; x[2] = W[ZY][ZY]; x[3] = W[ZX][ZPSI]; x[4] = W[ZY][ZPSI]; x[5] = W[ZPSI][ZPSI];
@@ -824,7 +806,7 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
                 for (int i = 0; i < 4; i++)
 #pragma unroll
                     for (int j = 0; j < 4; j++) Ba[i][j] = W[IA[i]][IA[j]];
-                mirror_n<4, MIRROR_PAIR>(Ba, d.reg_eps);
+                mirror_n<4, true>(Ba, d.reg_eps);
                 if (owner) {
 #pragma unroll
                     for (int i = 0; i < 4; i++)
@@ -952,7 +934,7 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
                 for (int i = 0; i < 4; i++)
 #pragma unroll
                     for (int j = 0; j < 4; j++) Ba[i][j] = W[IA[i]][IA[j]];
-                mirror_n<4, MIRROR_PAIR>(Ba, d.reg_eps);
+                mirror_n<4, true>(Ba, d.reg_eps);
                 if (owner) {
 #pragma unroll
                     for (int i = 0; i < 4; i++)
@@ -1136,11 +1118,11 @@ __device__ __forceinline__ void solve_epilogue(const Lds &L, const Dims &d, int 
     for (int e = tid_o; e < (N + 1) * nxe; e += nth) {
         const int k = d.slack ? e / (NX + 1) : e / NX, i = e - k * nxe;     // (two divisions by constants: a division by the run-time nxe keeps its
                                                                              //  reciprocal live across the persistent kernels' whole trajectory loop)
-        TMPC_ST_OUT(xtraj + (size_t)b * (N + 1) * nxe + e, i < NX ? L.z[k * NV + NU + i] : slack);      // the pinned slack state
+        *(xtraj + (size_t)b * (N + 1) * nxe + e) = i < NX ? L.z[k * NV + NU + i] : slack;      // the pinned slack state
     }
     for (int e = tid_o; e < N * NU; e += nth) {
         const int k = e / NU, i = e - k * NU;
-        TMPC_ST_OUT(utraj + (size_t)b * N * NU + e, L.z[k * NV + i]);
+        *(utraj + (size_t)b * N * NU + e) = L.z[k * NV + i];
     }
     if (tid == 0) {
         if (res > 1e-2 && status == 0) status = 4;

@@ -10,32 +10,26 @@ namespace tmpc {
 #ifdef TMPC_SWEEP_PROFILE
 enum { SP_FACTOR_TERM = 0, SP_FACTOR_LOOP, SP_SOLVE_PRE, SP_SOLVE_BWD, SP_SOLVE_FWD, SP_SOLVE_POST, SP_CALLS_FACTOR, SP_CALLS_SOLVE, SP_COUNT };
 __device__ unsigned long long g_sweep_prof[SP_COUNT];
-#define SWEEP_T0() long long sp_t = clock64()
-#define SWEEP_T(i) do { const long long sp_n = clock64(); if (tid == 0) atomicAdd(&g_sweep_prof[i], (unsigned long long)(sp_n - sp_t)); sp_t = sp_n; } while (0)
+#define SWEEP_T0(lead) long long sp_t = clock64(); const bool sp_lead = (lead)      // lead: the one lane that records
+#define SWEEP_T(i) do { const long long sp_n = clock64(); if (sp_lead) atomicAdd(&g_sweep_prof[i], (unsigned long long)(sp_n - sp_t)); sp_t = sp_n; } while (0)
 #define SWEEP_COUNT(i) do { if (tid == 0) atomicAdd(&g_sweep_prof[i], 1ull); } while (0)
 #else
-#define SWEEP_T0()
+#define SWEEP_T0(lead)
 #define SWEEP_T(i)
 #define SWEEP_COUNT(i)
 #endif
 
 // Issue priority of the wave (s_setprio, round 5).  Two waves share a SIMD; when both have an instruction ready the one with the higher priority issues.
 // A wave inside a SEQUENTIAL phase (the Riccati factorisation and sweeps: 8 of 64 lanes, every instruction on the trajectory's critical path) gets
-// TMPC_PRIO_SEQ, the rest of an interior-point iteration TMPC_PRIO_IPM, the linearisation 0 -- measured on the cfg 2 bench launch
+// priority 3, the rest of an interior-point iteration 2, the linearisation 0 -- measured on the cfg 2 bench launch
 // (profiles/round5_g_setprio_ab{,2}.jsonl): no priorities 27.53 ms, (3, 0) 27.15, (3, 1) 27.07, **(3, 2) 27.01** (+1.9 %), (3, 3) 27.20, (1, 1) 27.19,
 // the reverse assignment (0, 3) 27.63; at 2-4 rounds per launch the same shape gains 4-8 % (round5_k_prio_vs_launch_size.jsonl).  Results are
 // unaffected (it only orders issue between the waves of a SIMD).  Only where every SIMD hosts two waves: at 7 workgroups per CU (cfg 4's shape) one
 // SIMD hosts a single wave, the priorities make the launch 6 % SLOWER (round5_j_prio_other_configs.jsonl: the starved waves set the makespan) --
 // the host sets Dims::prio per launch (launch_solve) and the macros test it (a scalar branch).
-#ifndef TMPC_PRIO_SEQ
-#define TMPC_PRIO_SEQ 3
-#endif
-#ifndef TMPC_PRIO_IPM
-#define TMPC_PRIO_IPM 2
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
-#define TMPC_PRIO_HIGH() do { if (d.prio) __builtin_amdgcn_s_setprio(TMPC_PRIO_SEQ); } while (0)
-#define TMPC_PRIO_LOW() do { if (d.prio) __builtin_amdgcn_s_setprio(TMPC_PRIO_IPM); } while (0)
+#define TMPC_PRIO_HIGH() do { if (d.prio) __builtin_amdgcn_s_setprio(3); } while (0)
+#define TMPC_PRIO_LOW() do { if (d.prio) __builtin_amdgcn_s_setprio(2); } while (0)
 #define TMPC_PRIO_LINEARISE() do { if (d.prio) __builtin_amdgcn_s_setprio(0); } while (0)
 #else
 #define TMPC_PRIO_HIGH()
@@ -56,14 +50,10 @@ __device__ unsigned long long g_sweep_prof[SP_COUNT];
 // bench scenes -- at the reference's qp_tol = 1e-5 no exit code, SQP or interior-point iteration count changes on 2560 trajectories and the
 // iterates agree to 4e-11 (the level of the kernels' rounding differences); profiles/round5_riccati_form_study.json.
 // In place of Hh_k the "factor block" (28 doubles) is written for the vector solves:
-//   [0..9]  Lxu (5x2, row-major)   [10] L10   [11] 1/L00   [12] 1/L11   [13..27] P_k (packed lower 5x5)
-#ifdef TMPC_EXP_UNIFORM_PIVOTS
-constexpr int FB_LXU = 0, FB_L10 = 10, FB_R0 = 11, FB_R1 = 12, FB_P = 13;
-#else
-// (round 6: [10] 1/L00  [11] L10  [12] 1/L11 -- the vector sweeps apply Luu on lanes 0 and 1 only and broadcast the result: lane 0 needs (1/L00, L10), lane 1
-//  (L10, 1/L11), ONE two-double load with a per-lane base where every lane loaded all three, two instructions; the arithmetic is the same)
+//   [0..9]  Lxu (5x2, row-major)   [10] 1/L00   [11] L10   [12] 1/L11   [13..27] P_k (packed lower 5x5)
+// (round 6: the vector sweeps apply Luu on lanes 0 and 1 only and broadcast the result: lane 0 needs (1/L00, L10), lane 1 (L10, 1/L11),
+//  ONE two-double load with a per-lane base where every lane loaded all three, two instructions; the arithmetic is the same)
 constexpr int FB_LXU = 0, FB_R0 = 10, FB_L10 = 11, FB_R1 = 12, FB_P = 13;
-#endif
 
 // Offset of stage k's block in Hh.  A stride of 28 doubles (56 dwords) puts the stages k, k + 8, k + 16 on the same LDS banks: the stage-parallel loops
 // (one lane per stage: the node's 28 stores of Hh <- W, the 15 + 15 loads of P in the vector solves' prologue / epilogue, the row passes' ds_add_f64)
@@ -82,18 +72,6 @@ template <int CP> __device__ __forceinline__ double *ysl(const Lds &L, int k) { 
 // (The sequential sweeps use lanes 0..7 of the wave and rows 1..3 run along on copies.  Switching those rows off for the sweeps -- the LDS unit is
 // busy 70 % of the kernel time at eight trajectories per CU and the sweeps issue two thirds of its instructions -- was measured in round 5: 1.3 %
 // SLOWER, profiles/round5_o_sweep_rows_ab.jsonl; an LDS instruction costs the same with 16 lanes as with 64 and the EXEC changes are not free.)
-// The stage loop of the factorisation is unrolled by two in the one-wave-per-SIMD kernels and rolled in the two-waves-per-SIMD (compact) ones -- a
-// property of the INSTANTIATION (its layout parameter CP: 0 = fast / generic layouts, >= 1 = compact), so that every translation unit -- the four
-// instantiation units, a generated solver's single unit, experiment builds -- gives a kernel the same body (round-5 advisor: a per-unit macro made
-// the same template differ between units).  -DTMPC_FACTOR_UNROLL=0/1 forces one form everywhere (A/B builds only).
-template <int CP> __host__ __device__ constexpr bool factor_unrolled()
-{
-#ifdef TMPC_FACTOR_UNROLL
-    return TMPC_FACTOR_UNROLL != 0;
-#else
-    return CP == 0;
-#endif
-}
 
 // right-looking elimination of columns C0 .. C1-1 of the row-per-lane matrix
 template <int C0, int C1 = NV>
@@ -180,11 +158,12 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
     bool bad = false;
     // Operands of a stage.  The operands of stage k - 1 are loaded while stage k still needs some of its own (the scheduler computes rows 2..6 of
     // F after the pivots), so two register sets are live and the compiler copies the shadow set over at the back edge: 11 v_mov_b64 of the loop's
-    // 138 instructions.  TMPC_FACTOR_UNROLL = 1 names the two sets and unrolls the stage loop by two (like the vector sweeps): no copies, 129
-    // instructions per stage, 4 % fewer cycles per factorisation on a lone wave -- and 0.7 % LESS throughput on the saturated compact kernel
-    // (profiles/round5_m_factor_unroll_rotation_ab.jsonl).  So the translation units of the one-wave-per-SIMD kernels (fast, profiled twins)
-    // build the unrolled loop, those of the compact kernels (two waves per SIMD) the rolled one; the arithmetic is the same.
-    struct Opnd { double hk[NV], ba[NX], dn[8]; };
+    // 138 instructions.  Naming the two sets and unrolling the stage loop by two (like the vector sweeps): no copies, 129 instructions per stage,
+    // 4 % fewer cycles per factorisation on a lone wave -- and 0.7 % LESS throughput on the saturated compact kernel
+    // (profiles/round5_m_factor_unroll_rotation_ab.jsonl).  So the one-wave-per-SIMD kernels (fast, profiled twins, CP == 0) run the unrolled
+    // loop, the compact kernels (two waves per SIMD) the rolled one; the arithmetic is the same.  A property of the INSTANTIATION, so that every
+    // translation unit gives a kernel the same body (round-5 advisor: a per-unit macro made the same template differ between units).
+    struct Opnd { double hk[NV], ba[NX]; };
     double f[NV];
     const BaLane bc = ba_column(N, ls);
     double bac[NX];
@@ -199,21 +178,18 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
     // (the same for ba[] -- running offsets or pointers, five more values live across the stage loop -- pushed the compact kernels into scratch
     // twice: ba[] keeps its (base + k * stride) form, which the compiler rematerialises; mul24: tmpc_kernels.hpp)
     const double *hrow = nullptr;
-    int hstep = 0;
     const double *bbase = CP ? L.tab : L.BA;
     int bo[NX], bst[NX];
     if constexpr (VEC) {
         hrow = vec ? L.gh : L.Hh + pidx(ls, 0);       // (row start inside a stage's block; the block's offset is added per stage: hoff<CP>)
-        hstep = 0;
 #pragma unroll
         for (int m = 0; m < NX; m++) {
             if constexpr (CP) { bo[m] = vec ? (int)(L.rb - L.tab) + m : ba_off(N, 0, m, ls); bst[m] = vec ? NX : (bo[m] < 8 ? 8 : 0); }
             else { bo[m] = vec ? (int)(L.rb - L.BA) + m : m * NV + ls; bst[m] = vec ? NX : NX * NV; }
         }
     }
-    // (the running pointers are positioned by seek_stage and stepped by load_stage: stage k, then k - 1, ...; the last call re-loads stage 0)
-    auto seek_stage = [&](int) {};
-    auto load_stage = [&](Opnd &o, int k, bool step) {
+    // (load_stage reads stage k, then k - 1, ...; the last call re-loads stage 0)
+    auto load_stage = [&](Opnd &o, int k) {
         // unconditional loads (clamped indices): entries above the diagonal / of idle lanes are never used
         if constexpr (VEC) {
             const double *hr = hrow + (vec ? k * NV : hoff<CP>(k));          // (two wave-uniform offsets, one select per stage)
@@ -221,11 +197,6 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
             for (int j = 0; j < NV; j++) o.hk[j] = hr[j];
 #pragma unroll
             for (int m = 0; m < NX; m++) o.ba[m] = bbase[bo[m] + mul24(k, bst[m])];
-#ifdef TMPC_EXP_DN_LOADS
-#pragma unroll
-            for (int q = 0; q < 8; q++) o.dn[q] = (CP ? L.tab : L.dyn8)[k * 8 + q];
-#endif
-            (void)step;
         } else {
             const double *Hk = L.Hh + hoff<CP>(k);
 #pragma unroll
@@ -234,18 +205,10 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
                 o.ba[0] = L.tab[bc.o0 + mul24(k, bc.st)]; o.ba[1] = L.tab[bc.o1 + mul24(k, bc.st)];
 #pragma unroll
                 for (int m = 2; m < NX; m++) o.ba[m] = bac[m];
-#ifdef TMPC_EXP_DN_LOADS
-#pragma unroll
-                for (int q = 0; q < 8; q++) o.dn[q] = L.tab[k * 8 + q];
-#endif
             } else {
                 const double *BA = L.BA + k * NX * NV;
 #pragma unroll
                 for (int m = 0; m < NX; m++) o.ba[m] = BA[m * NV + ls];
-#ifdef TMPC_EXP_DN_LOADS
-#pragma unroll
-                for (int q = 0; q < 8; q++) o.dn[q] = L.dyn8[k * 8 + q];
-#endif
             }
         }
     };
@@ -253,41 +216,22 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
 #pragma unroll
     for (int j = 0; j < NV; j++) f[j] = (j >= NU) ? (vec ? L.gh[N * NV + j] : L.Hh[hoff<CP>(N) + pidx(ls, j <= ls ? j : ls)]) : 0.0;
     Opnd oa, ob;
-    seek_stage(N - 1);
-    load_stage(oa, N - 1, true);
+    load_stage(oa, N - 1);
     if constexpr (SQ) bad |= chol_rows<NU>(f, li, nullptr, nullptr);       // square-root form: Cholesky of the xx block of node N
-#ifdef TMPC_EXP_NO_MERGE_FACTOR
-    if (vec && wr) {
-#pragma unroll
-        for (int l = 0; l < NX; l++) L.pr[N * NX + l] = f[NU + l];          // p_N (square-root form: lx of node N)
-    }
-#endif
-    // Store merging (round 6, A/B builds: -DTMPC_EXP_NO_MERGE_FACTOR / -DTMPC_EXP_MERGE_FWD / -DTMPC_EXP_MERGE_BWD).  Stores of disjoint lane sets that hold the same
-    // registers at the same point of the loop can leave in ONE LDS instruction with a per-lane address.  In the FACTORISATION -- p_{k+1} of the extra row with the rows
-    // of P_{k+1}, its [y0 y1] with the Lxu pairs: four LDS instructions per stage fewer, nothing else changes -- that is +1.4 % on the saturated cfg 2 launch and taken.
-    // In the vector sweeps (du of lanes 0, 1 with dx of lanes 2..6; y with p) the merged store's value needs a select on the END of the stage's dependent chain,
-    // which holds the store back: -3.4 % (forward) and -2.0 % (backward) -- not taken.  profiles/round6_saturated_levers_ab.jsonl; results are bitwise the same either way.
+    // Store merging (round 6).  Stores of disjoint lane sets that hold the same registers at the same point of the loop can leave in ONE LDS instruction
+    // with a per-lane address.  In the FACTORISATION -- p_{k+1} of the extra row with the rows of P_{k+1}, its [y0 y1] with the Lxu pairs: four LDS
+    // instructions per stage fewer -- that is +1.4 % on the saturated cfg 2 launch.  In the vector sweeps (du of lanes 0, 1 with dx of lanes 2..6; y with p)
+    // the merged store's value needs a select on the END of the stage's dependent chain, which holds the store back: -3.4 % (forward) and -2.0 %
+    // (backward), so the sweeps store separately.  profiles/round6_saturated_levers_ab.jsonl; results are bitwise the same either way.
     // End of stage k: the Lxu pairs of lanes 2..6 and the extra row's [y0 y1] are the registers f[0], f[1] of their lanes: ONE store for both (per-lane
     // address); lane 1 adds L10 and the two reciprocal pivots.  (p_k follows at the top of stage k - 1; p_0 is never read.)
     auto store_pairs = [&](int k, double r0, double r1) {
         double *Fb = L.Hh + hoff<CP>(k);
-#ifndef TMPC_EXP_NO_MERGE_FACTOR
         if ((rowl && li >= NU) || (vec && wr)) {
             double *pp = vec ? ysl<CP>(L, k) : Fb + FB_LXU + 2 * i5;
             pp[0] = f[0]; pp[1] = f[1];
         }
         if (rowl && li == 1) { Fb[FB_L10] = f[0]; Fb[FB_R0] = r0; Fb[FB_R1] = r1; }
-#else
-        if (rowl) {
-            if (li >= NU) { Fb[FB_LXU + 2 * i5] = f[0]; Fb[FB_LXU + 2 * i5 + 1] = f[1]; }
-            if (li == 1) { Fb[FB_L10] = f[0]; Fb[FB_R0] = r0; Fb[FB_R1] = r1; }
-        }
-        if (vec && wr) {                                           // [y0 y1 | p_k] of stage k (square-root form: lx)
-            ysl<CP>(L, k)[0] = f[0]; ysl<CP>(L, k)[1] = f[1];
-#pragma unroll
-            for (int l = 0; l < NX; l++) L.pr[k * NX + l] = f[NU + l];
-        }
-#endif
     };
     auto stage = [&](const Opnd &o, Opnd &nx, int k) {
         // broadcast P (lower triangle of the 5x5 cost-to-go Hessian of stage k+1: rows 2..6 after the elimination) to every lane of the row
@@ -300,20 +244,12 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
         // P_{k+1} (own row of lanes 2..6) is kept for the vector solves -- and the extra row's p_{k+1} (square-root form: lx) leaves in the SAME five store
         // instructions (round 6: the LDS unit is the busy one at eight trajectories per CU, and an LDS instruction costs the same with one lane as with six):
         // lane 7 holds it in the same registers f[2..6] at the same point of the loop; only the address differs per lane
-#ifndef TMPC_EXP_NO_MERGE_FACTOR
         if ((rowl && li >= NU) || (vec && wr)) {
             double *Ln = vec ? L.pr + (k + 1) * NX : L.Hh + hoff<CP>(k + 1) + FB_P + i5 * (i5 + 1) / 2;
             const int lim = vec ? NX : i5;
 #pragma unroll
             for (int l = 0; l < NX; l++) *(l <= lim ? Ln + l : L.scr + (CP ? 0 : 56) + l) = f[NU + l];   // (entries above the diagonal go to a dummy slot: a select on the address instead of five masked stores)
         }
-#else
-        if (rowl && li >= NU) {
-            double *Ln = L.Hh + hoff<CP>(k + 1) + FB_P;
-#pragma unroll
-            for (int l = 0; l < NX; l++) *(l <= i5 ? Ln + i5 * (i5 + 1) / 2 + l : L.scr + (CP ? 0 : 56) + l) = f[NU + l];   // (entries above the diagonal go to a dummy slot: a select on the address instead of five masked stores)
-        }
-#endif
         if constexpr (SQ) {
             // G = Lp^T [B A] (5 x 7), Lp = Pm (the lower triangle holds Lxx of stage k + 1).  Own column densely from ba[]; all columns (row-uniform)
             // from the sparse [B A]:  x: e0   y: e1   s: e4   psi: (Xp,Yp,1,0,0)   v: (Xv,Yv,0,1,sdt)   a: (Xa,Ya,0,dt,shdt2)   w: (Xw,Yw,dt,0,0)
@@ -326,13 +262,8 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
                 for (int m = l; m < NX; m++) acc += Pm[m][l] * o.ba[m];
                 Go[l] = VEC ? fma(vmask, f[NU + l], acc) : acc;
             }
-#ifdef TMPC_EXP_DN_LOADS
-            const double Xa = o.dn[D8_XA], Xw = o.dn[D8_XW], Xp = o.dn[D8_XP], Xv = o.dn[D8_XV];
-            const double Ya = o.dn[D8_YA], Yw = o.dn[D8_YW], Yp = o.dn[D8_YP], Yv = o.dn[D8_YV];
-#else
             const double Xa = bcast16<ZA>(o.ba[0]), Ya = bcast16<ZA>(o.ba[1]), Xw = bcast16<ZW>(o.ba[0]), Yw = bcast16<ZW>(o.ba[1]);
             const double Xp = bcast16<ZPSI>(o.ba[0]), Yp = bcast16<ZPSI>(o.ba[1]), Xv = bcast16<ZV>(o.ba[0]), Yv = bcast16<ZV>(o.ba[1]);
-#endif
             double Ga[NX], Gw[NX], Gp[3], Gv[NX];
             Ga[0] = ((Pm[0][0] * Xa + Pm[1][0] * Ya) + Pm[3][0] * dt) + Pm[4][0] * shdt2;
             Ga[1] = (Pm[1][1] * Ya + Pm[3][1] * dt) + Pm[4][1] * shdt2;
@@ -362,7 +293,7 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
                 a6 += Go[l] * Pm[4][l];
             }
             f[ZA] = a0; f[ZW] = a1; f[ZX] = a2; f[ZY] = a3; f[ZPSI] = a4; f[ZV] = a5; f[ZS] = a6;
-            load_stage(nx, k > 0 ? k - 1 : 0, k > 1);
+            load_stage(nx, k > 0 ? k - 1 : 0);
             double r0 = 0.0, r1 = 0.0;
             bad |= chol_rows<0>(f, li, &r0, &r1);                 // all seven columns: rows 2..6 now hold Lxx of stage k (the extra row: lx)
             store_pairs(k, r0, r1);
@@ -382,15 +313,10 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
         // F row `li`: F_ij = Hh_ij + sum_n w_n [B A]_nj with the sparse columns of [B A] (row-uniform):
         //   x: e0   y: e1   s: e4   psi: (Xp,Yp,1,0,0)   v: (Xv,Yv,0,1,dt)   a: (Xa,Ya,0,dt,dt^2/2)   w: (Xw,Yw,dt,0,0)
         {
-#ifdef TMPC_EXP_DN_LOADS
-            const double Xa = o.dn[D8_XA], Xw = o.dn[D8_XW], Xp = o.dn[D8_XP], Xv = o.dn[D8_XV];
-            const double Ya = o.dn[D8_YA], Yw = o.dn[D8_YW], Yp = o.dn[D8_YP], Yv = o.dn[D8_YV];
-#else
             // (round 6) the eight stage-dependent entries of [B A] are rows x, y of the columns a, w, psi, v -- which the lanes of those columns hold as
             // ba[0], ba[1] of their OWN column: eight row broadcasts instead of four row-uniform LDS loads of the dyn8 block (the LDS unit is the busy one)
             const double Xa = bcast16<ZA>(o.ba[0]), Ya = bcast16<ZA>(o.ba[1]), Xw = bcast16<ZW>(o.ba[0]), Yw = bcast16<ZW>(o.ba[1]);
             const double Xp = bcast16<ZPSI>(o.ba[0]), Yp = bcast16<ZPSI>(o.ba[1]), Xv = bcast16<ZV>(o.ba[0]), Yv = bcast16<ZV>(o.ba[1]);
-#endif
             f[ZA] = fma(w[4], shdt2, fma(w[3], dt, fma(w[1], Ya, fma(w[0], Xa, o.hk[ZA]))));
             f[ZW] = fma(w[2], dt, fma(w[1], Yw, fma(w[0], Xw, o.hk[ZW])));
             f[ZX] = o.hk[ZX] + w[0];
@@ -399,13 +325,13 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
             f[ZV] = fma(w[4], sdt, fma(w[1], Yv, fma(w[0], Xv, o.hk[ZV])) + w[3]);
             f[ZS] = o.hk[ZS] + w[4];
         }
-        load_stage(nx, k > 0 ? k - 1 : 0, k > 1);     // operands of the next stage, hidden under the elimination (unconditional, clamped;
+        load_stage(nx, k > 0 ? k - 1 : 0);            // operands of the next stage, hidden under the elimination (unconditional, clamped;
                                                       // the pointers stop at stage 0, which the last pass re-loads and discards)
         double r0 = 0.0, r1 = 0.0;
         bad |= chol_rows<0, NU>(f, li, &r0, &r1);     // the two input columns; rows 2..6 now hold P_k (lanes 2..6) / p_k (the extra row)
         store_pairs(k, r0, r1);
     };
-    if constexpr (factor_unrolled<CP>()) {
+    if constexpr (CP == 0) {
         int k = N - 1;
         for (; k >= 1; k -= 2) {
             stage(oa, ob, k);
@@ -425,7 +351,7 @@ __device__ __forceinline__ bool riccati_factor(const Lds &L, const Dims &d, int 
 {
     asm volatile("" : "+v"(tid));                    // opaque per call: lane-derived addresses are not shared with (kept live until) other phases
     bool anybad = false;
-    SWEEP_T0(); SWEEP_COUNT(SP_CALLS_FACTOR);
+    SWEEP_T0(tid == 0); SWEEP_COUNT(SP_CALLS_FACTOR);
     if (NTH == 64 || (tid >> 6) == sw) {
         const int lane = tid & 63;
         TMPC_PRIO_HIGH();
@@ -495,8 +421,8 @@ __device__ __forceinline__ void riccati_solve_pre(const Lds &L, const Dims &d, i
     }
 }
 // dpi_k = P_k dx_k + p_k, k = 1..N (L.pr holds p_k: from the backward sweep, or from the extra row of a VEC factorisation)
-// SQ: dpi_k = Lxx (Lxx^T dx_k) + p_k; LX (the fused predictor of the square-root form): L.pr holds lx with p_k = Lxx lx, so dpi_k = Lxx (Lxx^T dx_k + lx_k)
-template <int CP, bool SQ = false, bool LX = false>
+// SQ: dpi_k = Lxx (Lxx^T dx_k) + p_k
+template <int CP, bool SQ = false>
 __device__ __forceinline__ void riccati_solve_post(const Lds &L, const Dims &d, int tid, int nth)
 {
     const int N = d.N;
@@ -516,14 +442,14 @@ __device__ __forceinline__ void riccati_solve_post(const Lds &L, const Dims &d, 
                 double acc = 0.0;
 #pragma unroll
                 for (int m = l; m < NX; m++) acc += pp[m * (m + 1) / 2 + l] * rr[m];
-                tl[l] = LX ? acc + pk[l] : acc;
+                tl[l] = acc;
             }
 #pragma unroll
             for (int i = 0; i < NX; i++) {
                 double acc = 0.0;
 #pragma unroll
                 for (int l = 0; l <= i; l++) acc += pp[i * (i + 1) / 2 + l] * tl[l];
-                L.dpi[mul24(k, NX) + i] = LX ? acc : acc + pk[i];
+                L.dpi[mul24(k, NX) + i] = acc + pk[i];
             }
             continue;
         }
@@ -547,7 +473,7 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
     const bool rowl = li < NV && wr, xl = rowl && li >= NU;
     const int ls = li < NV ? li : 0;
     const int i5 = (li >= NU && li < NV) ? li - NU : 0;
-    SWEEP_T0();
+    SWEEP_T0(li == 0);
     if constexpr (BWD) {                                // (the fused predictor has done this part inside the factorisation)
     if (sweeper) {
     double p = L.gh[N * NV + ls];                       // p_N (lanes 2..6 meaningful)
@@ -558,7 +484,7 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         // Compact layout: L.pr aliases L.dpi -- p_k takes the slot of q_{k-1} = (P rb)_{k-1}, which stage k - 1's operand load
         // (always issued before stage k runs: the sets are filled at least one stage ahead, and LDS operations of a wave
         // execute in order) has fetched by then; the closing loop adds P dx in place.
-        struct Ops { double ghj, ba[NX], r0, l10, r1, lx0, lx1, q; };
+        struct Ops { double ghj, ba[NX], r0, r1, lx0, lx1, q; };
         const int l01 = li == 1 ? 1 : 0;                                   // (lanes >= 2 follow lane 0: their values are not used)
         const BaLane bc = ba_column(N, ls);
         double bac[NX];
@@ -578,11 +504,7 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
 #pragma unroll
                 for (int l = 0; l < NX; l++) o.ba[l] = BA[l * NV + ls];
             }
-#ifdef TMPC_EXP_UNIFORM_PIVOTS
-            o.r0 = Fb[FB_R0]; o.l10 = Fb[FB_L10]; o.r1 = Fb[FB_R1];
-#else
-            { const double *Pv = Fb + FB_R0 + l01; o.r0 = Pv[0]; o.r1 = Pv[1]; o.l10 = 0.0; }      // lane 0: (1/L00, L10); lane 1: (L10, 1/L11)
-#endif
+            { const double *Pv = Fb + FB_R0 + l01; o.r0 = Pv[0]; o.r1 = Pv[1]; }      // lane 0: (1/L00, L10); lane 1: (L10, 1/L11)
             o.lx0 = Fb[FB_LXU + 2 * i5]; o.lx1 = Fb[FB_LXU + 2 * i5 + 1];
             o.q = L.dpi[uni((k + 1) * NX) + i5];
         };
@@ -590,20 +512,11 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
             const double Pb = p + o.q;                                     // (P_{k+1} rb_k + p_{k+1}), lane 2+i
             double fj = o.ghj;
             static_for<0, NX>([&](auto l_) { constexpr int l = decltype(l_)::value; fj += o.ba[l] * bcast16<NU + l>(Pb); });
-#ifdef TMPC_EXP_UNIFORM_PIVOTS
-            const double y0 = bcast16<0>(fj) * o.r0;
-            const double y1 = (bcast16<1>(fj) - o.l10 * y0) * o.r1;
-#else
             const double y0 = bcast16<0>(fj * o.r0);                       // lane 0: fj 1/L00
             const double y1 = bcast16<1>((fj - o.r0 * y0) * o.r1);         // lane 1: (fj - L10 y0) 1/L11   (its o.r0 is L10)
-#endif
             p = fj - o.lx0 * y0 - o.lx1 * y1;
-#ifdef TMPC_EXP_MERGE_BWD
-            if (rowl) *(li < NU ? ysl<CP>(L, k) + ls : L.pr + k * NX + i5) = li == 0 ? y0 : (li == 1 ? y1 : p);      // (one store: y from lanes 0, 1, p_k from lanes 2..6)
-#else
             if (rowl && li == 0) { ysl<CP>(L, k)[0] = y0; ysl<CP>(L, k)[1] = y1; }
             if (xl) L.pr[k * NX + i5] = p;
-#endif
         };
         Ops oa, ob;
         load_stage(oa, N - 1);
@@ -625,22 +538,13 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
     // forward sweep; dx_0 = 0 (dx lives in lanes 2..6).  dx+ = A dx + B du + rb with A = I + E (E: columns psi, v).
     if (sweeper) {
         double dx = 0.0;
-        // Lxu^T dx (two sums over the state lanes 2..6): every lane holds the stage's ten Lxu entries (row-uniform LDS reads) and gets the five
-        // dx components by row broadcasts -- 5 broadcasts + 10 fma, where folding the two sums with DPP row shifts cost 12 32-bit DPP moves, 6
-        // adds, 4 selects and 2 more broadcasts (round 4: -15 of the stage's 49 instructions); dpsi and dv are two of the five broadcasts
-        // The ten Lxu entries have ONE register set, re-loaded for stage k + 1 right after their last use in stage k (two sets, like the other
+        // The lane's pair of Lxu has ONE register set, re-loaded for stage k + 1 right after its last use in stage k (two sets, like the other
         // operands, pushed the compact kernels into scratch); the loads pass underneath the rest of the stage.
-        struct Ops { double y0, y1, r0, l10, r1, a_psi, a_v, b_a, b_w, rbi; };
-        double lxu[2 * NX];
+        struct Ops { double y0, y1, r0, r1, a_psi, a_v, b_a, b_w, rbi; };
+        double lxu[2];
         auto load_lxu = [&](int k) {
-#ifndef TMPC_EXP_LXU_ALL
             const double *Fb = L.Hh + hoff<CP>(k) + FB_LXU + 2 * i5;       // the lane's own pair
             lxu[0] = Fb[0]; lxu[1] = Fb[1];
-#else
-            const double *Fb = L.Hh + hoff<CP>(k) + FB_LXU;
-#pragma unroll
-            for (int e = 0; e < 2 * NX; e++) lxu[e] = Fb[e];
-#endif
         };
         const double i_psi = li == ZPSI ? 1.0 : 0.0, i_v = li == ZV ? 1.0 : 0.0;
         const int l01f = li == 1 ? 1 : 0;
@@ -649,11 +553,7 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         auto load_stage = [&](Ops &o, int k) {
             const double *Fb = L.Hh + hoff<CP>(k);
             o.y0 = ysl<CP>(L, k)[0]; o.y1 = ysl<CP>(L, k)[1];
-#ifdef TMPC_EXP_UNIFORM_PIVOTS
-            o.r0 = Fb[FB_R0]; o.l10 = Fb[FB_L10]; o.r1 = Fb[FB_R1];
-#else
-            { const double *Pv = Fb + FB_R0 + l01f; o.r0 = Pv[0]; o.r1 = Pv[1]; o.l10 = 0.0; }     // lane 0: (1/L00, L10); lane 1: (L10, 1/L11)
-#endif
+            { const double *Pv = Fb + FB_R0 + l01f; o.r0 = Pv[0]; o.r1 = Pv[1]; }     // lane 0: (1/L00, L10); lane 1: (L10, 1/L11)
             if constexpr (CP) {
                 const double *Tr = L.tab + br.o0 + mul24(k, br.st);              // own row of [B A] as (b_a, b_w, a_psi, a_v)
                 o.a_psi = Tr[2]; o.a_v = Tr[3];
@@ -667,11 +567,10 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         };
         auto stage = [&](const Ops &o, int k) {
             // du = -Luu^-T (Lxu^T dx + y)
-#ifndef TMPC_EXP_LXU_ALL
             // Round 6 (round-5 verdict next-2 (a)): a lane keeps ITS OWN pair of Lxu -- one LDS load per stage instead of the five row-uniform ones that gave
             // every lane all ten entries --, multiplies it by its own dx, and the ten products are summed by row broadcasts: 22 VALU instructions where the
-            // product form (round 4; -DTMPC_EXP_LXU_ALL rebuilds it) has 13, four LDS instructions fewer.  At eight trajectories per CU the LDS unit is the
-            // busier one (65 % of the kernel time, most of it these sweeps): cfg 2 1.288 -> 1.343 M solves/s (+4.3 %, profiles/round6_saturated_levers_ab.jsonl).
+            // product form (round 4) has 13, four LDS instructions fewer.  At eight trajectories per CU the LDS unit is the busier one (65 % of the kernel
+            // time, most of it these sweeps): cfg 2 1.288 -> 1.343 M solves/s (+4.3 %, profiles/round6_saturated_levers_ab.jsonl).
             // Every kernel family takes it (the fast and the compact kernel of a shape stay bitwise equal); the sums associate differently: rounding level.
             const double xm = (li >= NU && li < NV) ? 1.0 : 0.0;
             const double p0 = xm * (lxu[0] * dx), p1 = xm * (lxu[1] * dx);
@@ -679,28 +578,11 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
             static_for<0, NX>([&](auto m_) { constexpr int m = decltype(m_)::value; s0 += bcast16<NU + m>(p0); s1 += bcast16<NU + m>(p1); });
             double dxs[NX];
             dxs[ZPSI - NU] = bcast16<ZPSI>(dx); dxs[ZV - NU] = bcast16<ZV>(dx);
-            load_lxu(k + 1 < N ? k + 1 : N - 1);
-#else
-            double dxs[NX];
-            static_for<0, NX>([&](auto m_) { constexpr int m = decltype(m_)::value; dxs[m] = bcast16<NU + m>(dx); });
-            double s0 = o.y0, s1 = o.y1;
-#pragma unroll
-            for (int m = 0; m < NX; m++) { s0 = fma(lxu[2 * m], dxs[m], s0); s1 = fma(lxu[2 * m + 1], dxs[m], s1); }
             load_lxu(k + 1 < N ? k + 1 : N - 1);                           // (unconditional, clamped)
-#endif
-#ifdef TMPC_EXP_UNIFORM_PIVOTS
-            const double u1 = -s1 * o.r1;
-            const double u0 = (-s0 - o.l10 * u1) * o.r0;
-#else
             const double u1 = bcast16<1>(-s1 * o.r1);                      // lane 1: -s1 1/L11
             const double u0 = bcast16<0>((-s0 - o.r1 * u1) * o.r0);        // lane 0: (-s0 - L10 u1) 1/L00   (its o.r1 is L10)
-#endif
-#ifdef TMPC_EXP_MERGE_FWD
-            if (rowl) dv_own[k * NV] = li == 0 ? u0 : (li == 1 ? u1 : dx);      // (one store: lane j writes component j of dv_k -- du from lanes 0, 1, dx from lanes 2..6)
-#else
             if (rowl && li == 0) { L.dv[k * NV] = u0; L.dv[k * NV + 1] = u1; }
             if (xl) dv_own[k * NV] = dx;
-#endif
             const double dpsi = dxs[ZPSI - NU], dvv = dxs[ZV - NU];
             const double e_psi = o.a_psi - i_psi, e_v = o.a_v - i_v;
             dx = dx + e_psi * dpsi + e_v * dvv + o.b_a * u0 + o.b_w * u1 + o.rbi;   // lanes 2..6 meaningful
@@ -736,12 +618,12 @@ __device__ __forceinline__ void riccati_solve(const Lds &L, const Dims &d, int t
     riccati_sweeps_rows<CP, true>(L, d, lane, true, sweeper, [] { __syncthreads(); });
     TMPC_PRIO_LOW();
     __syncthreads();
-    riccati_solve_post<CP, SQ, false>(L, d, tid, NTH);
+    riccati_solve_post<CP, SQ>(L, d, tid, NTH);
     __syncthreads();
 }
 
-// The rest of the predictor solve after a VEC factorisation: forward sweep + stage-parallel closing loop.
-template <int NTH, int CP = 0, bool SQ = false>
+// The rest of the predictor solve after a VEC factorisation: the forward sweep.
+template <int NTH, int CP = 0>
 __device__ __forceinline__ void riccati_forward(const Lds &L, const Dims &d, int tid, int sw = 1)
 {
     asm volatile("" : "+v"(tid));
@@ -752,10 +634,6 @@ __device__ __forceinline__ void riccati_forward(const Lds &L, const Dims &d, int
     riccati_sweeps_rows<CP, false>(L, d, lane, true, sweeper, [] {});
     TMPC_PRIO_LOW();
     __syncthreads();
-#ifdef TMPC_EXP_PREDICTOR_POST
-    riccati_solve_post<CP, SQ, SQ>(L, d, tid, NTH);      // (square-root form: the extra row left lx, not p)
-    __syncthreads();
-#endif
     // (round 6: no closing loop here.  dpi = P dx + p is the step of the dynamics multipliers, and the PREDICTOR's is never used -- the row passes between
     //  predictor and corrector read dv only, the update takes the corrector's dpi: one stage-parallel pass and one barrier per interior-point iteration less)
 }

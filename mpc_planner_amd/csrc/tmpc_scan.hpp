@@ -411,19 +411,14 @@ __device__ __forceinline__ bool reduce(const ViewT<SL> &V, int lane)
 {
     const int N = V.N;
     bool bad = false;
-#ifndef TMPC_SCAN_FORCE_CPL3
     if constexpr (SL == 3) {                                 // N <= 20: ten blocks at level 0 (two columns per lane), at most five afterwards
         bad = cr_level<2>(V, lane, 1);
 #pragma unroll 1
         for (int s = 2; s < N; s *= 2) bad |= cr_level<1>(V, lane, s);
     } else
-#endif
 #pragma unroll 1
     for (int s = 1; s < N; s *= 2) {
         const int ne = (N - s + 2 * s - 1) / (2 * s);        // blocks o = s (2 m + 1) < N
-#ifdef TMPC_SCAN_FORCE_CPL3                                  // (tools/scan_vs_riccati_bench.hip: the three-column path on N = 20 systems)
-        if (ne * 4 <= 64 && s == 1) { bad |= cr_level<3>(V, lane, s); continue; }
-#endif
         if (ne * 10 <= 64) bad |= cr_level<1>(V, lane, s);
         else if (ne * 5 <= 64) bad |= cr_level<2>(V, lane, s);
         else bad |= cr_level<3>(V, lane, s);

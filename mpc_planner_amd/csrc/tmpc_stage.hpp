@@ -41,25 +41,8 @@
 #define TMPC_RCP_SEED(x) (1.0 / (x))
 #endif
 
-// ---- cache policy of the read-once / write-once global streams (round-4 verdict, next-5; tools/traffic_ab.sh builds the variants) ----
-// TMPC_EXP_NT = 0 (product): plain loads and stores.  1: the warm start, xinit and the output arrays -- touched once per solve -- go through
-// non-temporal accesses (`nt`: streaming, low retention priority in the L2), so that they do not compete with the per-workgroup NLP workspace
-// for L2 lines.  2: the parameter rows as well (read once per RTI iteration).  Measured: profiles/round5_c_traffic_nontemporal_ab.json.
-#ifndef TMPC_EXP_NT
-#define TMPC_EXP_NT 0
-#endif
-#if TMPC_EXP_NT >= 1 && defined(__HIP_DEVICE_COMPILE__)
-#define TMPC_LD_IN(ptr) __builtin_nontemporal_load(ptr)
-#define TMPC_ST_OUT(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define TMPC_LD_IN(ptr) (*(ptr))
-#define TMPC_ST_OUT(ptr, val) (*(ptr) = (val))
-#endif
-#if TMPC_EXP_NT >= 2 && defined(__HIP_DEVICE_COMPILE__)
-#define TMPC_LDP(ptr) __builtin_nontemporal_load(ptr)
-#else
-#define TMPC_LDP(ptr) (*(ptr))
-#endif
+// The read-once / write-once global streams (warm start, xinit, parameter rows, outputs) use plain loads and stores: non-temporal
+// accesses for them were measured and not taken (round-4 verdict, next-5; profiles/round5_c_traffic_nontemporal_ab.json).
 
 namespace tmpc {
 
@@ -269,7 +252,7 @@ struct CostOut { double val; double g[NV]; double Hxx, Hxy, Hyy, Hxs, Hys, Hss, 
 TMPC_HD void cost_eval(const Dims &d, const double *z, const double *p, int pstride, CostOut &o,
                                           bool derivs, double slack = 0.0)
 {
-    auto P = [&](int i) { return TMPC_LDP(p + (size_t)i * pstride); };
+    auto P = [&](int i) { return p[(size_t)i * pstride]; };
     const int ws = d.slack;
     const double w_a = P(0), w_w = P(1), w_v = P(2 + ws), v_ref = P(3 + ws), w_contour = P(4 + ws), w_lag = P(5 + ws);
     const double a = z[ZA], w = z[ZW], x = z[ZX], y = z[ZY], v = z[ZV], s = z[ZS];
@@ -365,7 +348,7 @@ struct CostOutCA { double val; double g[NV]; double Haa, Hww; double H[15]; };
 
 TMPC_HD void cost_eval_ca(const Dims &d, const double *z, const double *p, int pstride, CostOutCA &o, bool derivs, double slack = 0.0)
 {
-    auto P = [&](int i) { return TMPC_LDP(p + (size_t)i * pstride); };
+    auto P = [&](int i) { return p[(size_t)i * pstride]; };
     const int ws = d.slack;
     const double w_a = P(0), w_w = P(1), w_v = P(2 + ws), v_ref = P(3 + ws), w_contour = P(4 + ws);
     const double a = z[ZA], w = z[ZW], x = z[ZX], y = z[ZY], psi = z[ZPSI], v = z[ZV], s = z[ZS];
@@ -476,8 +459,8 @@ struct RowOut { double h; double gx, gy, gp; double Hxx, Hxy, Hyy, Hxp, Hyp, Hpp
 
 TMPC_HD void lin_row_eval(const Dims &d, const double *z, const double *p, int pstride, int j, RowOut &o)
 {
-    const double a1 = TMPC_LDP(p + (size_t)ip_lin(d, j, 0) * pstride), a2 = TMPC_LDP(p + (size_t)ip_lin(d, j, 1) * pstride);
-    const double b = TMPC_LDP(p + (size_t)ip_lin(d, j, 2) * pstride);
+    const double a1 = p[(size_t)ip_lin(d, j, 0) * pstride], a2 = p[(size_t)ip_lin(d, j, 1) * pstride];
+    const double b = p[(size_t)ip_lin(d, j, 2) * pstride];
     o.h = a1 * z[ZX] + a2 * z[ZY] - b;
     o.gx = a1; o.gy = a2; o.gp = 0.0;
     o.Hxx = o.Hxy = o.Hyy = o.Hxp = o.Hyp = o.Hpp = 0.0;
@@ -486,7 +469,7 @@ TMPC_HD void lin_row_eval(const Dims &d, const double *z, const double *p, int p
 TMPC_HD void ellipsoid_row_eval(const Dims &d, const double *z, const double *p, int pstride, int j,
                                                    double r_disc, double off, double spsi, double cpsi, RowOut &o)
 {
-    auto P = [&](int w) { return TMPC_LDP(p + (size_t)ip_ellipsoid(d, j, w) * pstride); };
+    auto P = [&](int w) { return p[(size_t)ip_ellipsoid(d, j, w) * pstride]; };
     const double ox = P(0), oy = P(1), opsi = P(2), chi = P(5), r = P(6);
     const double sq = sqrt(chi);
     const double major = P(3) * sq, minor = P(4) * sq;                    // ellipsoid_constraints.py:94-95
@@ -525,7 +508,7 @@ TMPC_HD double gauss_quantile(double risk)
 TMPC_HD void gauss_row_eval(const Dims &d, const double *z, const double *p, int pstride, int j,
                             double r_disc, double off, double spsi, double cpsi, double ye, RowOut &o)
 {
-    auto P = [&](int w) { return TMPC_LDP(p + (size_t)ip_gauss(d, j, w) * pstride); };
+    auto P = [&](int w) { return p[(size_t)ip_gauss(d, j, w) * pstride]; };
     const double ox = P(0), oy = P(1), s0 = P(2) * P(2), s1 = P(3) * P(3), R = r_disc + P(5);
     const double px = z[ZX] + off * cpsi - ox, py = z[ZY] + off * spsi - oy;
     const double qx = -off * spsi, qy = off * cpsi;                        // d(px,py)/dpsi
@@ -552,8 +535,8 @@ TMPC_HD void gauss_row_eval(const Dims &d, const double *z, const double *p, int
 TMPC_HD void slk_row_eval(const Dims &d, const double *z, const double *p, int pstride, int j, double off,
                                              double spsi, double cpsi, double slack, RowOut &o)
 {
-    const double a1 = TMPC_LDP(p + (size_t)ip_slk(d, j, 0) * pstride), a2 = TMPC_LDP(p + (size_t)ip_slk(d, j, 1) * pstride);
-    const double b = TMPC_LDP(p + (size_t)ip_slk(d, j, 2) * pstride);
+    const double a1 = p[(size_t)ip_slk(d, j, 0) * pstride], a2 = p[(size_t)ip_slk(d, j, 1) * pstride];
+    const double b = p[(size_t)ip_slk(d, j, 2) * pstride];
     o.h = a1 * (z[ZX] + off * cpsi) + a2 * (z[ZY] + off * spsi) - (b + slack);
     o.gx = a1; o.gy = a2; o.gp = off * (a2 * cpsi - a1 * spsi);
     o.Hxx = o.Hxy = o.Hyy = o.Hxp = o.Hyp = 0.0;
@@ -588,16 +571,14 @@ TMPC_HD double st_rcp(double x)
 }
 
 // MIRROR of an n x n symmetric matrix held in registers (fully unrolled cyclic Jacobi): A <- V max(|e|, eps) V^T.
-// A sweep starts while the squared off-diagonal norm exceeds TMPC_MIRROR_TOL2 times the squared Frobenius norm (1e-32: the oracle's; looser
+// A sweep starts while the squared off-diagonal norm exceeds MIRROR_TOL2 times the squared Frobenius norm (1e-32: the oracle's; looser
 // thresholds were measured in round 5 and buy 0.1-0.2 %: profiles/round5_h_mirror_tol_ab.jsonl -- not taken).
-#ifndef TMPC_MIRROR_TOL2
-#define TMPC_MIRROR_TOL2 1e-32
-#endif
+constexpr double MIRROR_TOL2 = 1e-32;
 // One Jacobi rotation's parameters from the pivot block (a_pp, a_qq, a_pq): c = cos, s = sin, t = tan of the angle |theta| <= pi / 4 that annihilates a_pq:
 // t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), theta = (a_qq - a_pp) / (2 a_pq), written division-free:
 // t = a_pq sgn(tau) / (|tau| + sqrt(tau^2 + a_pq^2)), tau = (a_qq - a_pp) / 2;  c = 1 / sqrt(t^2 + 1), s = t c.
 // (Round 6 measured a form with TWO reciprocal square roots on the dependent chain instead of rsqrt -> reciprocal -> rsqrt -- cos^2 = (1 + |tau| / h) / 2 =: x,
-// c = x rsqrt(x), s = g rsqrt(x), t = g rsqrt(x)^2, g = sgn(tau) a_pq / (2 h): -DTMPC_EXP_ROT2 -- the same rotation to rounding, every parity test green, and
+// c = x rsqrt(x), s = g rsqrt(x), t = g rsqrt(x)^2, g = sgn(tau) a_pq / (2 h) -- the same rotation to rounding, every parity test green, and
 // 0.4 % SLOWER on the saturated compact kernel, +-0.5 % on the ticks: profiles/round6_mirror_rotation_ab.jsonl.  Not taken.)
 // `live` false (|a_pq| <= 1e-150): the identity (c = 1, s = t = 0) -- by selects, for the branch-free callers.
 struct JacobiRot { double c, s, t; };
@@ -608,17 +589,9 @@ TMPC_HD JacobiRot jacobi_rot(double app, double aqq, double apq, bool live)
     double h2 = tau * tau + apq * apq;
     if (SELECT) h2 = live ? h2 : 1.0;                       // (keeps the reciprocal square root finite)
     JacobiRot r;
-#ifndef TMPC_EXP_ROT2
     const double hyp = h2 * st_rsqrt(h2);
     r.t = (tau >= 0.0 ? apq : -apq) * st_rcp(fabs(tau) + hyp);
     r.c = st_rsqrt(r.t * r.t + 1.0); r.s = r.t * r.c;
-#else
-    const double rh = st_rsqrt(h2);
-    const double g = (tau >= 0.0 ? 0.5 : -0.5) * apq * rh;
-    const double x = fma(0.5 * fabs(tau), rh, 0.5);
-    const double rc = st_rsqrt(x);
-    r.c = x * rc; r.s = g * rc; r.t = r.s * rc;
-#endif
     if (SELECT) { r.c = live ? r.c : 1.0; r.s = live ? r.s : 0.0; r.t = live ? r.t : 0.0; }
     return r;
 }
@@ -663,7 +636,7 @@ TMPC_HD void mirror_n(double (&A)[NN][NN], double eps)
 #pragma unroll
             for (int j = i + 1; j < NN; j++) off += A[i][j] * A[i][j];
         }
-        if (off <= TMPC_MIRROR_TOL2 * (dg + off) || off == 0.0) break;
+        if (off <= MIRROR_TOL2 * (dg + off) || off == 0.0) break;
         if constexpr (PAIR) {
             constexpr int RR[3][4] = {{0, 1, 2, 3}, {0, 2, 1, 3}, {0, 3, 1, 2}};
 #pragma unroll
@@ -778,9 +751,8 @@ TMPC_HD void stage_linearise(const Dims &d, const double *z, const double *p, in
     // rows (W = their share, g; BA, xn untouched).  The two-wave kernels run 1 and 2 on different waves at the same time and add the two W
     // (linearise, tmpc_solve.hip).  Measured shares of a stage's 46 k cycles (cfg 2): dynamics 5.5 k, eight ellipsoid rows 10.2 k, cost and
     // halfspace rows 8.3 k -- and 22.3 k for MIRROR, which needs the complete W and stays on one wave.
-    // Round 6, the four-wave kernels: 3 = dynamics alone; 4 = cost, topology and scenario / decomp rows (no obstacle rows); 5 = obstacle rows alone
-    // (this lane's share of them: ell_first / ell_step; call with rows_only); 6 = the cost alone; 7 = every row class alone (this lane's share of each:
-    // ell_first / ell_step; call with rows_only) -- the four-wave linearisation runs 3 | 6 | 7 | 7: the halfspace and scenario rows leave the cost's wave.
+    // Round 6, the four-wave kernels: 3 = dynamics alone; 6 = the cost alone; 7 = every row class alone (this lane's share of each: ell_first / ell_step;
+    // call with rows_only) -- the four-wave linearisation runs 3 | 6 | 7 | 7: the halfspace and scenario rows are not on the cost's wave.
     // own_delta (doubles, wave-uniform): distance from `p` to the trajectory's OWN parameter row when `p` is a row it shares with others
     // (tmpc_set_param_sharing): the topology and scenario halfspaces (ip_lin / ip_slk) are read from p + own_delta, everything else
     // from p.  A delta, not a second pointer: the second address then lives only across the halfspace loads (the linearisation is the
@@ -802,7 +774,7 @@ TMPC_HD void stage_linearise(const Dims &d, const double *z, const double *p, in
 #pragma unroll
         for (int j = 0; j < NV; j++) W[i][j] = 0.0;
 #ifndef TMPC_GENERATED_STAGE
-    if (part != 2 && part != 4 && part != 5 && part != 6 && part != 7)
+    if (part != 2 && part != 6 && part != 7)
 #endif
     {
         DynOut dy;
@@ -837,7 +809,7 @@ TMPC_HD void stage_linearise(const Dims &d, const double *z, const double *p, in
 #else
     RowOut ro;
     if (part == 3) return;
-    if (part != 1 && part != 5 && part != 7) {
+    if (part != 1 && part != 7) {
         if constexpr (cm_curvature_aware(CM)) {
             CostOutCA co;
             cost_eval_ca(d, z, p, pstride, co, true, slack);
@@ -854,39 +826,37 @@ TMPC_HD void stage_linearise(const Dims &d, const double *z, const double *p, in
         }
     }
     if (part == 6) return;
-    if (part != 1 && part != 5) {
+    if (part != 1) {
         for (int j = ell_first(); j < d.n_lin; j += ell_step) {   // (halfspace rows have no curvature: nothing of them enters W)
             lin_row_eval(d, z, p + own_delta, pstride, j, ro);
             sink(j, ro);
         }
     }
     if (d.M == 0 && d.n_slk == 0) return;
-    const double r_disc = d.M > 0 ? TMPC_LDP(p + (size_t)ip_disc_radius(d) * pstride) : 0.0, off = TMPC_LDP(p + (size_t)ip_disc_offset(d) * pstride);
+    const double r_disc = d.M > 0 ? p[(size_t)ip_disc_radius(d) * pstride] : 0.0, off = p[(size_t)ip_disc_offset(d) * pstride];
     double spsi, cpsi;
     sincos(z[ZPSI], &spsi, &cpsi);
-    if (part != 1 && part != 5) {
-        for (int j = (part == 4 ? 0 : ell_first()); j < d.n_slk; j += (part == 4 ? 1 : ell_step)) {
+    if (part != 1) {
+        for (int j = ell_first(); j < d.n_slk; j += ell_step) {
             slk_row_eval(d, z, p + own_delta, pstride, j, off, spsi, cpsi, slack, ro);
             W[ZPSI][ZPSI] += lamh(d.n_lin + j) * ro.Hpp;          // the row is linear in (x, y); psi enters through the disc offset
             sink(d.n_lin + j, ro);
         }
     }
-    if (part != 4) {
-        // the two parts share the ellipsoid rows (part 1 the first half, next to the dynamics)
-        const int j0 = part == 2 ? d.M / 2 : 0, j1 = part == 1 ? d.M / 2 : d.M;
-        double risk_of = -1.0, ye = 0.0;                      // (Gaussian rows) the quantile of the last risk level seen: one level per configuration
-        (void)risk_of; (void)ye;                              // in the reference (CONFIG probabilistic/risk), so it is evaluated once per stage, not once per row
-        for (int j = j0 + ell_first(); j < j1; j += ell_step) {
-            if constexpr (cm_gaussian_rows(CM)) {
-                const double risk = TMPC_LDP(p + (size_t)ip_gauss(d, j, 4) * pstride);
-                if (risk != risk_of) { ye = gauss_quantile(risk); risk_of = risk; }
-                gauss_row_eval(d, z, p, pstride, j, r_disc, off, spsi, cpsi, ye, ro);
-            } else {
-                ellipsoid_row_eval(d, z, p, pstride, j, r_disc, off, spsi, cpsi, ro);
-            }
-            row_add_hessian(ro, lamh(d.n_up + j), W);
-            sink(d.n_up + j, ro);
+    // the two parts share the ellipsoid rows (part 1 the first half, next to the dynamics)
+    const int j0 = part == 2 ? d.M / 2 : 0, j1 = part == 1 ? d.M / 2 : d.M;
+    double risk_of = -1.0, ye = 0.0;                      // (Gaussian rows) the quantile of the last risk level seen: one level per configuration
+    (void)risk_of; (void)ye;                              // in the reference (CONFIG probabilistic/risk), so it is evaluated once per stage, not once per row
+    for (int j = j0 + ell_first(); j < j1; j += ell_step) {
+        if constexpr (cm_gaussian_rows(CM)) {
+            const double risk = p[(size_t)ip_gauss(d, j, 4) * pstride];
+            if (risk != risk_of) { ye = gauss_quantile(risk); risk_of = risk; }
+            gauss_row_eval(d, z, p, pstride, j, r_disc, off, spsi, cpsi, ye, ro);
+        } else {
+            ellipsoid_row_eval(d, z, p, pstride, j, r_disc, off, spsi, cpsi, ro);
         }
+        row_add_hessian(ro, lamh(d.n_up + j), W);
+        sink(d.n_up + j, ro);
     }
 #endif
 }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B libraries that differ only in one solve translation unit (TU=TMPC_TU_COMPACT by default, or TMPC_TU_CP2): build/exp/libtmpc_hip_<name>.so for every "name:flags" argument
-# (the other objects are the product build's, the C-ABI unit the lab one -- it reads the TMPC_* switches --: run __graft_entry__.build() first).  Usage: tools/build_compact_variants.sh "u1r0:-DTMPC_FACTOR_UNROLL=1 -DTMPC_ROT_BRANCH=0" ...
+# (the other objects are the product build's, the C-ABI unit the lab one -- it reads the TMPC_* switches --: run __graft_entry__.build() first).  Usage: tools/build_compact_variants.sh "<name>:<extra hipcc flags>" ...
 R=$(cd $(dirname $0)/.. && pwd); mkdir -p $R/build/exp
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Full library variant (every translation unit recompiled with extra flags): build/exp/libtmpc_hip_<name>.so, lab C-ABI unit (TMPC_* switches read).
-#   tools/build_full_variant.sh <name> [-DTMPC_EXP_...]
+#   tools/build_full_variant.sh <name> [extra hipcc flags ...]
 set -e
 name=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd); D=$R/build/exp/full_$name; mkdir -p $D
