@@ -307,10 +307,36 @@ int tmpc_linearize_topology(tmpc_handle *h, const void *d_obstacle_pos, const vo
  *   remaining rows up to n_lin       dummies (1, 0, state_x + 100) (:181-187); n_obstacles + n_static <= n_lin
  * d_obstacle_radius == NULL: guidance mode, every obstacle disc has radius 1e-3 + robot_radius (:99, :140).  Otherwise the
  * `_use_guidance == false` branch (:63-73): f64 [n_scenes][n_obstacles], obstacle j's own radius + robot_radius in the projection and
- * in b.  One disc at the robot's centre (n_discs = 1, offset 0: the Jackal configurations); rows of further discs are not generated. */
+ * in b.  One disc at the robot's centre (n_discs = 1, offset 0: the Jackal configurations); rows of further discs are not generated.
+ * A non-guided planner (d_is_original) is updated with empty data in the reference (guidance_constraints.cpp:301-305): zero obstacles, so its
+ * static halfspaces are its rows 0 .. n_static-1 (:113-124, :173-179) and every row behind them is a dummy. */
 int tmpc_linearize_topology_ex(tmpc_handle *h, const void *d_obstacle_pos, int32_t n_obstacles, const void *d_obstacle_radius,
                                const void *d_static_halfspaces, int32_t n_static, const void *d_scene_of, const void *d_state_x,
                                double robot_radius, const void *d_is_original);
+
+/* ---- rows a5 / f-1: Contouring's road constraints on device (`contouring/add_road_constraints`; Contouring::constructRoadConstraints,
+ * mpc_planner_modules/src/contouring.cpp:181-262).  For every scene q < n_scenes and stage k = 1..N-1 (stage 0 gets nothing) two halfspaces
+ * a.p <= b that keep the robot between the road's edges, built at s_k = the spline state of the warm start of batch entry d_main_of[q] -- the
+ * entry of the CURRENT batch that stands for the scene's main solver (`_solver->getEgoPrediction(k, "spline")`, :208, :250): its warm start in
+ * the handle's x0 buffer (after tmpc_set_batch* or tmpc_warmstart; both models' strides), the path window (spline_x{i}_{a..d}, spline_y{i}_{a..d},
+ * spline{i}_start) of its parameter row of stage k.  With P(s) the point and A(s) the unit normal of a spline at s:
+ *   d_bound_segments == NULL, centreline mode (:191-235):  row 0 (A, A.(P + A offset_first)),  row 1 (-A, -A.(P - A offset_second))  of the path;
+ *       offset_first = times * road/width / 2 - r (times = road/two_way ? 3 : 1), offset_second = road/width / 2 - r, r = robot_area[0].radius
+ *   otherwise, bounds mode (:237-262):  row 0 (-A_l, -A_l.(P_l + A_l offset_first)),  row 1 (A_r, A_r.(P_r - A_r offset_second))  of the left /
+ *       right bound spline at the same s_k, offset_first = offset_second = r;  d_bound_segments f64 [n_scenes][2][S][8] = (left, right) x segment x
+ *       (ax bx cx dx ay by cy dy) on the centreline's knots (the bound splines are built on its knot vector, :142-149).
+ * RosTools::Spline2D is not in the reference tree.  ASSUMED: (1) getOrthogonal(s) = (y'(s), -x'(s)) / |.|, the normal to the RIGHT
+ * of travel -- the only sign for which bounds mode is a corridor between the two bounds; in centreline mode it puts the `times = 3` side on the
+ * right; (2) P, x', y' are the plain piecewise cubics (no sigmoid glue: that belongs to the NLP) of segment i = max{j : start_j <= s}, i = 0 below
+ * the first knot, and the last segment's cubic continues beyond the window.
+ * Writes rows first_row and first_row + 1 of d_static_halfspaces f64 [n_scenes][N][n_static][3] -- the buffer tmpc_linearize_topology_ex reads --
+ * for k >= 1 and touches nothing else (other rows, stage 0).  Stream-ordered on the handle's stream: no synchronisation, no allocation, so a
+ * closed loop tmpc_warmstart -> tmpc_road_halfspaces -> tmpc_init_with_guidance -> tmpc_linearize_topology_ex -> tmpc_solve has no host round
+ * trip.  Equal bit for bit to mpc_planner_amd.modules.road_halfspaces / road_halfspaces_from_bounds (no FMA contraction, same operation order).
+ * d_main_of i32 [n_scenes] (device); an entry outside [0, B) leaves its scene's rows untouched.  TMPC_ERR_INVALID: no batch, NULL d_main_of /
+ * d_static_halfspaces, n_scenes <= 0, first_row < 0, n_static < first_row + 2, S = 0, a generated solver. */
+int tmpc_road_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scenes, const void *d_bound_segments, double offset_first,
+                         double offset_second, void *d_static_halfspaces, int32_t n_static, int32_t first_row);
 
 /* ---- scenario -> polygon construction of SH-MPC on device.  Replaces what the reference gets from the
  * external scenario_module (scenario_constraints.cpp:47 update, :76-79 setParameters; source absent -> restated, see

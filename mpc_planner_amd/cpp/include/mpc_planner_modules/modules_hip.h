@@ -3,7 +3,7 @@
  * the reference's modules so that the batched optimize() of INTEGRATION.md section 4 exists as compiled, tested code:
  *
  *   MPCBaseModule::setParameters          mpc_planner_modules/src/mpc_base.cpp:23-35
- *   Contouring::setParameters             mpc_planner_modules/src/contouring.cpp:50-124
+ *   Contouring::update / setParameters / constructRoadConstraints      mpc_planner_modules/src/contouring.cpp:28-124, 181-262
  *   EllipsoidConstraints::update / setParameters      ellipsoid_constraints.cpp:23-90
  *   LinearizedConstraints::update / projectToSafety / setParameters      linearized_constraints.cpp:49-189
  *   GuidanceConstraints::optimize / initializeSolverWithGuidance / FindBestPlanner      guidance_constraints.cpp:264-434
@@ -51,6 +51,10 @@ namespace MPCPlanner
         std::map<std::string, double> weights;               /* weights/<name> */
         bool dynamic_velocity_reference{false};              /* contouring/dynamic_velocity_reference */
         int num_segments{5};                                 /* contouring/num_segments */
+        bool add_road_constraints{false};                    /* contouring/add_road_constraints (true in every settings.yaml the reference ships; false here so
+                                                                that a caller who did not generate the two extra rows sees none: INTEGRATION.md section 2) */
+        bool two_way_road{false};                            /* road/two_way */
+        double road_width{6.0};                              /* road/width */
         bool use_tmpcpp{true};                               /* t-mpc/use_t-mpc++ */
         bool enable_constraints{true};                       /* t-mpc/enable_constraints */
         bool warmstart_with_mpc_solution{false};             /* t-mpc/warmstart_with_mpc_solution */
@@ -77,12 +81,17 @@ namespace MPCPlanner
         std::vector<std::string> _weight_names;
     };
 
-    /* ---- contouring.cpp:50-124 ---- */
+    /* ---- contouring.cpp:28-124, 181-262 ---- */
     class Contouring
     {
     public:
         Contouring(std::shared_ptr<Solver> solver, const ModuleConfig &cfg) : _solver(solver), _cfg(cfg) {}
-        void update(State &, const RealTimeData &, ModuleData &module_data) { _segments = module_data.path; }
+        /* (:28-48; findClosestPoint and the choice of the segment window are the caller's: module_data.path IS the window) */
+        void update(State &, const RealTimeData &data, ModuleData &module_data)
+        {
+            _segments = module_data.path;
+            if (_cfg.add_road_constraints) constructRoadConstraints(data, module_data);
+        }
         void setParameters(const RealTimeData &, const ModuleData &, int k)
         {
             setSolverParameterContour(k, _solver->_params, _cfg.weights.at("contour"));
@@ -98,8 +107,74 @@ namespace MPCPlanner
                 setSolverParameterSplineStart(k, _solver->_params, sg.start, i);
             }
         }
+        /* ---- road constraints (:181-262).  RosTools::Spline2D is not in the reference tree; ASSUMED: getOrthogonal(s) =
+         * (y'(s), -x'(s)) / |.| (the normal to the right of travel), getPoint / the derivative = the plain piecewise cubic of the segment
+         * i = max{j : start_j <= s} of the window (i = 0 below the first knot, the last cubic continues beyond it).  Same arithmetic, in the same
+         * order, as modules.py::road_halfspaces / road_halfspaces_from_bounds and tmpc_road_halfspaces_kernel. ---- */
+        void constructRoadConstraints(const RealTimeData &data, ModuleData &module_data)
+        {
+            if (data.left_bound.empty() || data.right_bound.empty()) constructRoadConstraintsFromCenterline(data, module_data);
+            else constructRoadConstraintsFromBounds(data, module_data);
+        }
+        void constructRoadConstraintsFromCenterline(const RealTimeData &data, ModuleData &module_data)
+        {
+            prepareStaticObstacles(module_data);
+            const bool two_way = _cfg.two_way_road;
+            const double road_width_half = _cfg.road_width / 2.;
+            const double width_times = two_way ? 3.0 : 1.0;                     /* 3w for double lane */
+            const double offset_first = width_times * road_width_half - data.robot_area[0].radius;
+            const double offset_second = road_width_half - data.robot_area[0].radius;
+            for (int k = 1; k < _solver->N; k++) {
+                module_data.static_obstacles[k].clear();
+                const double cur_s = _solver->getEgoPrediction(k, "spline");
+                Vector2d path_point(0., 0.), A(0., 0.);
+                evaluateSegments(_segments, cur_s, path_point, A);
+                const double b_left = A(0) * (path_point(0) + A(0) * offset_first) + A(1) * (path_point(1) + A(1) * offset_first);
+                module_data.static_obstacles[k].emplace_back(A, b_left);
+                const double b_right = A(0) * (path_point(0) - A(0) * offset_second) + A(1) * (path_point(1) - A(1) * offset_second);
+                module_data.static_obstacles[k].emplace_back(Vector2d(-A(0), -A(1)), -b_right);
+            }
+        }
+        void constructRoadConstraintsFromBounds(const RealTimeData &data, ModuleData &module_data)
+        {
+            prepareStaticObstacles(module_data);
+            const double r = data.robot_area[0].radius;
+            for (int k = 1; k < _solver->N; k++) {
+                module_data.static_obstacles[k].clear();
+                const double cur_s = _solver->getEgoPrediction(k, "spline");
+                Vector2d Pl(0., 0.), Al(0., 0.), Pr(0., 0.), Ar(0., 0.);
+                evaluateSegments(data.left_bound, cur_s, Pl, Al);
+                const double bl = Al(0) * (Pl(0) + Al(0) * r) + Al(1) * (Pl(1) + Al(1) * r);
+                module_data.static_obstacles[k].emplace_back(Vector2d(-Al(0), -Al(1)), -bl);
+                evaluateSegments(data.right_bound, cur_s, Pr, Ar);
+                const double br = Ar(0) * (Pr(0) - Ar(0) * r) + Ar(1) * (Pr(1) - Ar(1) * r);
+                module_data.static_obstacles[k].emplace_back(Ar, br);
+            }
+        }
         std::shared_ptr<Solver> _solver;
     private:
+        void prepareStaticObstacles(ModuleData &module_data) const
+        {
+            if (module_data.static_obstacles.empty()) {
+                module_data.static_obstacles.resize(_solver->N);
+                for (auto &obstacle : module_data.static_obstacles) obstacle.reserve(2);
+            }
+        }
+        /* point and right-hand unit normal at s of the cubics `coef`, on the knots of the path window (`_segments[i].start`) */
+        void evaluateSegments(const std::vector<PathSegment> &coef, double s, Vector2d &point, Vector2d &orthogonal) const
+        {
+            size_t i = 0;
+            for (size_t j = 0; j < _segments.size() && j < coef.size(); j++) if (_segments[j].start <= s) i = j;
+            const PathSegment &c = coef.at(i);
+            const double t = s - _segments[i].start;
+            const double px = ((c.ax * t + c.bx) * t + c.cx) * t + c.dx;
+            const double py = ((c.ay * t + c.by) * t + c.cy) * t + c.dy;
+            const double dx = (3.0 * c.ax * t + 2.0 * c.bx) * t + c.cx;
+            const double dy = (3.0 * c.ay * t + 2.0 * c.by) * t + c.cy;
+            const double n = std::sqrt(dx * dx + dy * dy);
+            point = Vector2d(px, py);
+            orthogonal = Vector2d(dy / n, -dx / n);
+        }
         ModuleConfig _cfg;
         std::vector<PathSegment> _segments;
     };
@@ -276,14 +351,22 @@ namespace MPCPlanner
                         const double radius = _use_guidance ? 1e-3 : copied_obstacle.radius;
                         _b[d][k][obs_id] = _a1[d][k][obs_id] * obstacle_pos(0) + _a2[d][k][obs_id] * obstacle_pos(1) - (radius + _cfg.robot_radius);
                     }
+                    int num_halfspaces = 0;
                     if (!module_data.static_obstacles.empty()) {
-                        const int num_halfspaces = std::min((int)module_data.static_obstacles[k].size(), _n_other_halfspaces);
+                        num_halfspaces = std::min((int)module_data.static_obstacles[k].size(), _n_other_halfspaces);
                         for (int h = 0; h < num_halfspaces; h++) {
                             const int obs_id = (int)copied_obstacles.size() + h;
                             _a1[d][k][obs_id] = module_data.static_obstacles[k][h].A(0);
                             _a2[d][k][obs_id] = module_data.static_obstacles[k][h].A(1);
                             _b[d][k][obs_id] = module_data.static_obstacles[k][h].b;
                         }
+                    }
+                    /* halfspaces the solver has rows for but nobody supplied (`add_road_constraints: false` with `add_halfspaces: 2`): the
+                     * reference sends whatever its unset Eigen arrays hold (:33-35, :173-179); here the dummy row, the only defined choice --
+                     * what tmpc_linearize_topology_ex writes into the rows behind n_obstacles + n_static, too */
+                    for (int h = num_halfspaces; h < _n_other_halfspaces; h++) {
+                        const int obs_id = (int)copied_obstacles.size() + h;
+                        _a1[d][k][obs_id] = _dummy_a1; _a2[d][k][obs_id] = _dummy_a2; _b[d][k][obs_id] = _dummy_b;
                     }
                 }
             }

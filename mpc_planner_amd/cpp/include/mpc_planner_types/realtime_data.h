@@ -1,8 +1,10 @@
 /*
  * mpc_planner_types/realtime_data.h (HIP flavour) -- what the accelerated path reads of the per-tick sensor data; written
  * after mpc_planner_types/include/mpc_planner_types/realtime_data.h:16-51 (member names and reset() semantics kept so that module
- * code compiles unchanged; costmap, reference path, road bounds and the past trajectory are not on this path and stay with the
- * reference's own header in a full tree).
+ * code compiles unchanged; costmap, reference path and the past trajectory are not on this path and stay with the reference's own
+ * header in a full tree).  The road bounds ARE on the path (Contouring::constructRoadConstraintsFromBounds, contouring.cpp:237-262): the
+ * reference keeps them as point lists and fits RosTools::Spline2D objects on the centreline's knot vector (:142-149); ros_tools is absent, so
+ * here they are the fitted cubics themselves, one PathSegment per segment of ModuleData::path (same window, same knots).
  */
 #ifndef MPC_REALTIME_DATA_HIP_H
 #define MPC_REALTIME_DATA_HIP_H
@@ -24,6 +26,7 @@ namespace MPCPlanner
         Vector2d goal;                                                        // GoalModule (generated solvers)
         bool goal_received{false};
         double intrusion{0.};                                                 // feedback value published by the ROS wrappers
+        std::vector<PathSegment> left_bound, right_bound;                     // Contouring's road constraints; aligned with ModuleData::path, empty = not supplied
 
         // Everything but the robot's disc model is per-tick data (reference :37-47).
         void reset()

@@ -95,7 +95,10 @@ __global__ void tmpc_linearize_topology_kernel(Dims d, int B, const double *x0, 
     const int sc = scene_of[b];
     double *p = params + ((size_t)b * N + k) * d.npar;
     const double dummy_b = state_x[sc] + 100.0;                         // _dummy_b (:54)
-    const bool dummy = (k == 0) || (is_original && is_original[b]);
+    const bool dummy = k == 0;
+    // the non-guided T-MPC++ planner is updated with empty_data_ (guidance_constraints.cpp:301-305): ZERO obstacles, so its static halfspaces
+    // sit in rows 0 .. n_static-1 (:113-124, :173-179) and everything behind them is a dummy; without static halfspaces: dummies only
+    if (is_original && is_original[b]) n_obs = 0;
     auto radius_of = [&](int j) { return (obst_radius ? obst_radius[(size_t)sc * n_obs + j] : 1e-3) + robot_radius; };   // (:99, :140)
     double px = x0[((size_t)b * (N + 1) + k) * ext_nv(d) + ZX], py = x0[((size_t)b * (N + 1) + k) * ext_nv(d) + ZY];
     const double *ob = obst + (size_t)sc * n_obs * N * 2;
@@ -140,6 +143,63 @@ __global__ void tmpc_linearize_topology_kernel(Dims d, int B, const double *x0, 
             a1 = hs[0]; a2 = hs[1]; bb = hs[2];
         }
         p[ip_lin(d, j, 0)] = a1; p[ip_lin(d, j, 1)] = a2; p[ip_lin(d, j, 2)] = bb;
+    }
+}
+
+// ---- a5 / f-1: Contouring's road constraints on device (contouring.cpp:181-262, `contouring/add_road_constraints`) ----------------
+// one thread per (scene, stage).  For stage k = 1 .. N-1 of scene q (stage 0 gets nothing, :204, :247) with b = main_of[q] the batch entry
+// that stands for the scene's MAIN solver, s_k = its warm start's spline state (`_solver->getEgoPrediction(k, "spline")`, :208, :250) and the
+// path window of its parameter row of stage k (spline_x{i}_{a..d}, spline_y{i}_{a..d}, spline{i}_start):
+//   centreline mode (bounds == nullptr; :191-235): P, A = point and normal of the path at s_k,
+//       row 0 (A, A.(P + A off_first)), row 1 (-A, -A.(P - A off_second));  off_first = times half - r, off_second = half - r
+//   bounds mode (:237-262): P_l, A_l / P_r, A_r of the left / right bound spline at the same s_k -- bounds [n_scenes][2][S][8] =
+//       (ax bx cx dx ay by cy dy), on the centreline's knots (:142-149) --, off_first = off_second = r:
+//       row 0 (-A_l, -A_l.(P_l + A_l off_first)), row 1 (A_r, A_r.(P_r - A_r off_second)).
+// RosTools::Spline2D is not in the reference tree; ASSUMED: getOrthogonal(s) = (y'(s), -x'(s)) / |.| (to the right of travel:
+// the only sign for which bounds mode is a corridor between the bounds), and P, x', y' are the plain piecewise cubics of segment
+// i = max{j : start_j <= s} (0 below the first knot; the last segment's cubic continues beyond the window), no sigmoid glue.
+// Rows first_row, first_row + 1 of stat [n_scenes][N][n_static][3] -- what tmpc_linearize_topology_kernel copies -- and nothing else.
+// No FMA contraction, the operation order of modules.py::road_halfspaces / road_halfspaces_from_bounds: bit-equal to the host mirrors.
+__global__ void tmpc_road_halfspaces_kernel(Dims d, int B, int n_scenes, const double *x0, const double *params, const int *main_of,
+                                            const double *bounds, double off_first, double off_second, double *stat, int n_static, int first_row)
+{
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = d.N, S = d.S;
+    if (e >= n_scenes * N) return;
+    const int sc = e / N, k = e - sc * N;
+    const int b = main_of[sc];
+    if (k == 0 || b < 0 || b >= B) return;                              // (an entry outside the batch: nothing is read, nothing written)
+    const double *p = params + ((size_t)b * N + k) * d.npar;
+    const double s = x0[((size_t)b * (N + 1) + k) * ext_nv(d) + ZS];
+    int i = 0;
+    for (int j = 0; j < S; j++) if (p[ip_spline(d, j, 8)] <= s) i = j;
+    const double t = s - p[ip_spline(d, i, 8)];
+    // point and unit normal of one 2-D cubic c = (ax bx cx dx ay by cy dy) at t
+    auto frame = [&](const double *c, double &px, double &py, double &ax, double &ay) {
+        px = ((c[0] * t + c[1]) * t + c[2]) * t + c[3];
+        py = ((c[4] * t + c[5]) * t + c[6]) * t + c[7];
+        const double dx = (3.0 * c[0] * t + 2.0 * c[1]) * t + c[2];
+        const double dy = (3.0 * c[4] * t + 2.0 * c[5]) * t + c[6];
+        const double n = sqrt(dx * dx + dy * dy);
+        ax = dy / n; ay = -dx / n;
+    };
+    double *row = stat + (((size_t)sc * N + k) * n_static + first_row) * 3;
+    double px, py, ax, ay;
+    if (bounds == nullptr) {
+        frame(p + ip_spline(d, i, 0), px, py, ax, ay);
+        const double b0 = ax * (px + ax * off_first) + ay * (py + ay * off_first);
+        const double b1 = ax * (px - ax * off_second) + ay * (py - ay * off_second);
+        row[0] = ax; row[1] = ay; row[2] = b0;
+        row[3] = -ax; row[4] = -ay; row[5] = -b1;
+    } else {
+        const double *bl = bounds + (((size_t)sc * 2 + 0) * S + i) * 8, *br = bounds + (((size_t)sc * 2 + 1) * S + i) * 8;
+        frame(bl, px, py, ax, ay);
+        const double vl = ax * (px + ax * off_first) + ay * (py + ay * off_first);
+        row[0] = -ax; row[1] = -ay; row[2] = -vl;
+        frame(br, px, py, ax, ay);
+        const double vr = ax * (px - ax * off_second) + ay * (py - ay * off_second);
+        row[3] = ax; row[4] = ay; row[5] = vr;
     }
 }
 

@@ -1249,6 +1249,28 @@ int tmpc_linearize_topology(tmpc_handle *h, const void *d_obstacle_pos, const vo
     return tmpc_linearize_topology_ex(h, d_obstacle_pos, h->d.n_lin, nullptr, nullptr, 0, d_scene_of, d_state_x, robot_radius, d_is_original);
 }
 
+int tmpc_road_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scenes, const void *d_bound_segments, double offset_first,
+                         double offset_second, void *d_static_halfspaces, int32_t n_static, int32_t first_row)
+{
+#ifdef TMPC_GENERATED_STAGE
+    if (h) h->err = "tmpc_road_halfspaces: not available in a generated solver (its parameter layout is the module stack's)";
+    return TMPC_ERR_INVALID;
+#endif
+    if (!h) return TMPC_ERR_INVALID;
+    if (h->B <= 0 || !h->x0 || !h->params) { h->err = "tmpc_road_halfspaces: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
+    if (!d_main_of || !d_static_halfspaces || n_scenes <= 0) { h->err = "tmpc_road_halfspaces: bad argument (d_main_of, d_static_halfspaces, n_scenes > 0)"; return TMPC_ERR_INVALID; }
+    if (first_row < 0 || n_static < first_row + 2) { h->err = "tmpc_road_halfspaces: the two road rows do not fit (n_static < first_row + 2)"; return TMPC_ERR_INVALID; }
+    if (h->d.S <= 0) { h->err = "tmpc_road_halfspaces: the problem has no path segments (S = 0)"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    const int64_t n = (int64_t)n_scenes * h->d.N;
+    if (n > 0x7fffffff) { h->err = "tmpc_road_halfspaces: n_scenes x N too large"; return TMPC_ERR_INVALID; }
+    hipLaunchKernelGGL(tmpc::tmpc_road_halfspaces_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B, n_scenes, h->x0,
+                       h->params, (const int *)d_main_of, (const double *)d_bound_segments, offset_first, offset_second,
+                       (double *)d_static_halfspaces, n_static, first_row);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
 int tmpc_scenario_halfspaces(tmpc_handle *h, const void *d_samples, int32_t n_pts, int32_t n_rows, const void *d_scene_of,
                              const void *d_state_x, double radius, double disc_offset)
 {

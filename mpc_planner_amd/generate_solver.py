@@ -28,17 +28,20 @@ def _yaml_dump_flat(d):
 
 
 def generate_solver(out_dir, N=20, max_obstacles=8, num_segments=5, guidance=True, n_sqp=10, dt=0.2, slack=False,
-                    ellipsoids=True, n_scenario=0, n_decomp=0, curvature_aware=False, gaussian=False):
+                    ellipsoids=True, n_scenario=0, n_decomp=0, curvature_aware=False, gaussian=False, add_halfspaces=0):
     """slack / n_scenario / n_decomp select the slack-model configurations (configuration_safe_horizon,
     generate_jackalsimulator_solver.py:67-90; rosnavigation configuration_tmpc, generate_rosnavigation_solver.py:86-108).
     curvature_aware: CurvatureAwareContouringModule instead of ContouringModule (same parameter map: its define_parameters adds
     contour, lag, terminal_*, the spline rows and leaves velocity / reference_velocity to MPCBaseModule,
     curvature_aware_contouring.py:22-46) -> SOLVER_COST_MODEL 1 (tmpc_dims::cost_model).
     gaussian: GaussianConstraintModule as the collision-avoidance module instead of the ellipsoids (mpc_planner_jackal's default,
-    generate_jackal_solver.py:53-73; gaussian_constraints.py:40-52 parameter layout) -> SOLVER_ROW_MODEL 1 (tmpc_dims::row_model)."""
+    generate_jackal_solver.py:53-73; gaussian_constraints.py:40-52 parameter layout) -> SOLVER_ROW_MODEL 1 (tmpc_dims::row_model).
+    add_halfspaces: `linearized_constraints/add_halfspaces` (guidance_constraints.py:73-78: max_obstacles + add_halfspaces topology rows; 2 = the road
+    constraints of Contouring, contouring.cpp:181-262) -> SOLVER_NLIN = max_obstacles + add_halfspaces, SOLVER_MAX_OBSTACLES unchanged."""
+    add_halfspaces = int(add_halfspaces) if guidance else 0
     pm = define_parameters(num_segments, max_obstacles, guidance=guidance, slack=slack, ellipsoids=ellipsoids and not gaussian,
-                           n_scenario=n_scenario, n_decomp=n_decomp, gaussian=gaussian)
-    return _write_host_side(out_dir, pm, N, slack, n_sqp, dt, n_lin=(max_obstacles if guidance else 0),
+                           n_scenario=n_scenario, n_decomp=n_decomp, gaussian=gaussian, add_halfspaces=add_halfspaces)
+    return _write_host_side(out_dir, pm, N, slack, n_sqp, dt, n_lin=(max_obstacles + add_halfspaces if guidance else 0),
                             M=(max_obstacles if (ellipsoids or gaussian) else 0), n_slk=n_scenario + n_decomp, num_segments=num_segments,
                             max_obstacles=max_obstacles, cost_model=int(bool(curvature_aware)), row_model=int(bool(gaussian)))
 

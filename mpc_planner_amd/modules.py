@@ -109,6 +109,79 @@ def _project_to_safety(pos, obstacles_k, radii):
     return np.array([px, py])
 
 
+def _road_segment_eval(coef, starts, s):
+    """Point and derivative of the plain piecewise cubic at s (DESIGN.md U12, assumption 2): the segment i = max{j : start_j <= s}
+    (i = 0 below the first knot; beyond the last knot the last segment's cubic continues), t = s - start_i, Horner form -- no sigmoid
+    glue, that belongs to the NLP's spline.  coef [S][8] = (ax bx cx dx ay by cy dy); starts [S].  Same operation order as
+    tmpc_road_halfspaces_kernel and the C++ Contouring::evaluateSegments."""
+    i = 0
+    for j in range(len(starts)):
+        if starts[j] <= s:
+            i = j
+    t = s - starts[i]
+    c = coef[i]
+    px = ((c[0] * t + c[1]) * t + c[2]) * t + c[3]
+    py = ((c[4] * t + c[5]) * t + c[6]) * t + c[7]
+    dx = (3.0 * c[0] * t + 2.0 * c[1]) * t + c[2]
+    dy = (3.0 * c[4] * t + 2.0 * c[5]) * t + c[6]
+    return px, py, dx, dy
+
+
+def _road_orthogonal(dx, dy):
+    """getOrthogonal (assumption 1): the unit normal pointing to the RIGHT of travel, (y', -x') / |(x', y')|."""
+    n = np.sqrt(dx * dx + dy * dy)
+    return dy / n, -dx / n
+
+
+def road_offsets(width, radius, two_way=False):
+    """(offset_first, offset_second) of the centreline mode (contouring.cpp:203,216-220,229-230): times * width / 2 - r with
+    times = 3 on a two-way road (the side row 0 bounds, the right of travel under U12), and width / 2 - r."""
+    half = width / 2.0
+    return (3.0 if two_way else 1.0) * half - radius, half - radius
+
+
+def road_halfspaces(segments, s_of_k, offset_first, offset_second):
+    """Contouring::constructRoadConstraintsFromCenterline (contouring.cpp:191-235): for stage k = 1 .. N-1 (N = len(s_of_k); stage 0
+    gets nothing and stays zero here) with s_k = the MAIN solver's warm-start spline state, P the path point and A the unit normal
+    (_road_orthogonal) at s_k:  row 0 (A, A.(P + A offset_first)),  row 1 (-A, -A.(P - A offset_second)),  each meaning a.p <= b;
+    offsets from road_offsets.  segments [S][9] = (ax bx cx dx ay by cy dy start), the window the parameter rows carry.
+    RosTools::Spline2D is not in the reference tree: normal direction and spline evaluation are the assumptions U12 of DESIGN.md.
+    Returns [N][2][3] = (a1, a2, b), directly usable as linearized_update(static=...)."""
+    segments = np.asarray(segments, float)
+    N = len(s_of_k)
+    out = np.zeros((N, 2, 3))
+    for k in range(1, N):
+        px, py, dx, dy = _road_segment_eval(segments[:, :8], segments[:, 8], float(s_of_k[k]))
+        ax, ay = _road_orthogonal(dx, dy)
+        b0 = ax * (px + ax * offset_first) + ay * (py + ay * offset_first)
+        b1 = ax * (px - ax * offset_second) + ay * (py - ay * offset_second)
+        out[k, 0] = (ax, ay, b0)
+        out[k, 1] = (-ax, -ay, -b1)
+    return out
+
+
+def road_halfspaces_from_bounds(segments, left, right, s_of_k, radius):
+    """Contouring::constructRoadConstraintsFromBounds (contouring.cpp:237-262): P_l, A_l / P_r, A_r point and normal of the left /
+    right bound spline at the same s_k -- the bound splines live on the centreline's knot vector (:142-149), so only `segments`'
+    start column is used --:  row 0 (-A_l, -A_l.(P_l + A_l r)),  row 1 (A_r, A_r.(P_r - A_r r)).
+    left, right [S][8] = (ax bx cx dx ay by cy dy).  Returns [N][2][3]."""
+    starts = np.asarray(segments, float)[:, 8]
+    left = np.asarray(left, float); right = np.asarray(right, float)
+    N = len(s_of_k)
+    out = np.zeros((N, 2, 3))
+    for k in range(1, N):
+        s = float(s_of_k[k])
+        px, py, dx, dy = _road_segment_eval(left[:, :8], starts, s)
+        ax, ay = _road_orthogonal(dx, dy)
+        bl = ax * (px + ax * radius) + ay * (py + ay * radius)
+        out[k, 0] = (-ax, -ay, -bl)
+        px, py, dx, dy = _road_segment_eval(right[:, :8], starts, s)
+        ax, ay = _road_orthogonal(dx, dy)
+        br = ax * (px - ax * radius) + ay * (py - ay * radius)
+        out[k, 1] = (ax, ay, br)
+    return out
+
+
 def linearized_update(x0, obstacle_pos, robot_radius, obstacle_radius=None, static=None):
     """LinearizedConstraints::update (linearized_constraints.cpp:49-123).  x0: warm start [N+1][nvar]; obstacle_pos [M][N][2].
     obstacle_radius None: guidance mode, radius 1e-3 (:99); else [M], the `_use_guidance == false` branch with each obstacle's own radius.

@@ -331,6 +331,43 @@ def make_scene(scene_idx, N=20, M=8, B=64, S=5, tmpc_pp=False, gaussian=False, g
                 inside=inside, inside_at=inside_at)
 
 
+def add_road_constraints(sc, width, two_way=False, radius=ROBOT_RADIUS, left=None, right=None):
+    """A make_scene() T-MPC scene with `contouring/add_road_constraints` on and `linearized_constraints/add_halfspaces: 2`: the parameter map
+    widened by two topology rows (define_parameters(add_halfspaces=2)), every other column copied, and the two rows filled like the reference
+    fills them -- Contouring::update builds them once from the MAIN solver's warm start (centreline mode, modules.road_halfspaces; every
+    planner's copy of the main solver carries the same spline states) and LinearizedConstraints::setParameters appends them behind the
+    obstacle rows of every guided planner (the non-guided planner, updated with zero obstacles, gets them as its rows 0 and 1); stage 0 and
+    every unused row are the dummies (1, 0, x + 100).  Returns a new dict
+    (make_scene's output is left as it is) with pm, params, n_lin = M + 2, road_rows [N][2][3] and road_offsets.
+    left, right [S][8]: the road's bound cubics on the path's knots -- bounds mode (modules.road_halfspaces_from_bounds; `width` is not used)."""
+    pm0 = sc["pm"]; N, M, S = sc["N"], sc["n_lin"], sc["S"]
+    assert M > 0 and not sc["slack"] and not sc["n_slk"], "a T-MPC scene with topology rows"
+    pm = define_parameters(S, M, guidance=True, add_halfspaces=2, ellipsoids=sc["M"] > 0, gaussian=sc["n_gauss"] > 0)
+    Bt = len(sc["xinit"])
+    params = np.zeros((Bt, N, pm.length()))
+    for name, idx in pm0._params.items():
+        params[:, :, pm.index(name)] = sc["params"][:, :, idx]
+    s_of_k = sc["x0"][0, :N, md.IDX["spline"]]
+    if left is None or right is None:
+        offsets = md.road_offsets(width, radius, two_way)
+        rows = md.road_halfspaces(sc["segments"], s_of_k, *offsets)
+    else:
+        offsets = (radius, radius)
+        rows = md.road_halfspaces_from_bounds(sc["segments"], left, right, s_of_k, radius)
+    guided = sc["guidance_id"] < Bt                     # (guided planners are numbered 0 .. B-1; the non-guided one's id is 2 B, guidance_constraints.cpp:349)
+    for j in range(2):
+        ia = [pm.index(f"lin_constraint_{M + j}_{f}") for f in ("a1", "a2", "b")]
+        params[:, :, ia] = (1.0, 0.0, sc["xinit"][0, 0] + 100.0)
+        params[np.ix_(np.nonzero(guided)[0], np.arange(1, N), ia)] = rows[None, 1:, j, :]
+        # the non-guided planner is updated with empty data (guidance_constraints.cpp:301-305): zero obstacles, so the static halfspaces are
+        # its rows 0 and 1 (linearized_constraints.cpp:113-124, 173-179) and every row behind them stays a dummy
+        i0 = [pm.index(f"lin_constraint_{j}_{f}") for f in ("a1", "a2", "b")]
+        params[np.ix_(np.nonzero(~guided)[0], np.arange(1, N), i0)] = rows[None, 1:, j, :]
+    out = dict(sc)
+    out.update(pm=pm, params=params, n_lin=M + 2, road_rows=rows, road_offsets=offsets)
+    return out
+
+
 def _make_scene_kw(args):
     idx, kw = args
     return make_scene(idx, **kw)

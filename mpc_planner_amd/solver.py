@@ -47,7 +47,8 @@ EXPORTS = ["tmpc_default_dims", "tmpc_default_dims_ex", "tmpc_create", "tmpc_des
            "tmpc_debug_get_x0", "tmpc_debug_get_params", "tmpc_set_throughput_mode", "tmpc_solve_iterations",
            "tmpc_reset_multipliers", "tmpc_get_stream", "tmpc_kernel_info", "tmpc_set_slots", "tmpc_set_param_sharing", "tmpc_copy_state", "tmpc_scenario_empty_stages", "tmpc_sample_scenarios",
            "tmpc_scenario_discard", "tmpc_scenario_discarded", "tmpc_linearize_topology_ex", "tmpc_clear_slot", "tmpc_gather_best",
-           "tmpc_create_v2", "tmpc_set_param_sharing_ex", "tmpc_latency_mode_capacity", "tmpc_has_lane_kernels", "tmpc_debug_lds_passes", "tmpc_debug_poison_lds", "tmpc_has_lab_switches"]
+           "tmpc_create_v2", "tmpc_set_param_sharing_ex", "tmpc_latency_mode_capacity", "tmpc_has_lane_kernels", "tmpc_debug_lds_passes", "tmpc_debug_poison_lds", "tmpc_has_lab_switches",
+           "tmpc_road_halfspaces"]
 
 class TmpcError(RuntimeError):
     pass
@@ -112,6 +113,8 @@ def load_library(path=None):
         lib.tmpc_scenario_discard.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_double]
     if hasattr(lib, "tmpc_linearize_topology_ex"):
         lib.tmpc_linearize_topology_ex.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_double, vp]
+    if hasattr(lib, "tmpc_road_halfspaces"):
+        lib.tmpc_road_halfspaces.argtypes = [vp, vp, C.c_int32, vp, C.c_double, C.c_double, vp, C.c_int32, C.c_int32]
     if hasattr(lib, "tmpc_scenario_discarded"):        # (absent from reference builds of earlier rounds used in A/B runs)
         lib.tmpc_scenario_discarded.argtypes = [vp, vp]
     if hasattr(lib, "tmpc_copy_state"):        # (absent from reference builds of earlier rounds used in A/B runs)
@@ -382,6 +385,19 @@ class BatchedSolver:
         self._check(self.lib.tmpc_linearize_topology_ex(self._h, vp(d_obstacle_pos), int(n_obstacles), vp(d_obstacle_radius),
                                                         vp(d_static_halfspaces), int(n_static), C.c_void_p(d_scene_of), C.c_void_p(d_state_x),
                                                         float(robot_radius), vp(d_is_original)), "tmpc_linearize_topology_ex")
+
+    def road_halfspaces(self, d_main_of, n_scenes, offset_first, offset_second, d_static_halfspaces, n_static, first_row=0,
+                        d_bound_segments=None):
+        """Contouring's road constraints on device (tmpc_road_halfspaces; raw device pointers): rows first_row, first_row + 1 of
+        d_static_halfspaces [n_scenes][N][n_static][3] -- the buffer linearize_topology_ex reads -- from the warm start and path window of batch
+        entry d_main_of[scene].  d_bound_segments None: centreline mode, offsets = modules.road_offsets(width, radius, two_way); else
+        [n_scenes][2][S][8] left / right bound cubics and offsets = (radius, radius).  Stream-ordered, no synchronisation."""
+        if not hasattr(self.lib, "tmpc_road_halfspaces"):
+            raise TmpcError("this library has no tmpc_road_halfspaces (a missing kernel is an error, there is no host fallback)")
+        self._check(self.lib.tmpc_road_halfspaces(self._h, C.c_void_p(d_main_of) if d_main_of else None, int(n_scenes),
+                                                  C.c_void_p(d_bound_segments) if d_bound_segments else None, float(offset_first),
+                                                  float(offset_second), C.c_void_p(d_static_halfspaces) if d_static_halfspaces else None,
+                                                  int(n_static), int(first_row)), "tmpc_road_halfspaces")
 
     def scenario_halfspaces(self, d_samples, n_pts, n_rows, d_scene_of, d_state_x, radius, disc_offset=0.0):
         """Device scenario -> halfspace reduction of SH-MPC (raw device pointers; samples [n_scenes][N][n_pts][2]);
