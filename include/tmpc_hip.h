@@ -338,6 +338,69 @@ int tmpc_linearize_topology_ex(tmpc_handle *h, const void *d_obstacle_pos, int32
 int tmpc_road_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scenes, const void *d_bound_segments, double offset_first,
                          double offset_second, void *d_static_halfspaces, int32_t n_static, int32_t first_row);
 
+/* ---- obstacle preparation on device: what a wrapper's obstacle callback does before Planner::solveMPC (mpc_planner/src/data_preparation.cpp;
+ * mpc_planner_jackal/src/ros1_jackal.cpp:313-332, mpc_planner_jackalsimulator/src/ros1_jackalsimulator.cpp:298-347).  For every scene q < n_scenes
+ * the raw obstacle list becomes exactly max_obstacles prepared obstacles, in the layout tmpc_linearize_topology_ex and
+ * tmpc_set_obstacle_parameters read.  Uses N, dt and the stream of the handle only: no batch is needed.  Stream-ordered, no allocation, no
+ * synchronisation.  Inputs (device):
+ *   d_count      i32 [n_scenes]                 raw obstacles of the scene, clipped to [0, n_slots]
+ *   d_state      f64 [n_scenes][4]              (x, y, psi, v)
+ *   d_raw_pos    f64 [n_scenes][n_slots][2]     current positions;  d_raw_radius f64 [n_scenes][n_slots]
+ *   d_raw_vel    f64 [n_scenes][n_slots][2]     or NULL: constant-velocity mode -- prediction step i = pos + (vel dt) i, i < N, angle 0,
+ *                                               major = minor = (probabilistic ? noise : 0), GAUSSIAN iff probabilistic
+ *                                               (getConstantVelocityPrediction, data_preparation.cpp:58-79)
+ *   d_raw_pred   f64 [n_scenes][n_slots][N][5]  or NULL: given predictions (x, y, angle, major, minor), taken as they are; GAUSSIAN iff
+ *                                               probabilistic and the last step's major != 0 (ros1_jackalsimulator.cpp:331-334)
+ * exactly one of d_raw_vel / d_raw_pred; n_slots <= 1024.  Then, restated from the cited lines:
+ *   distance filter  max_obstacle_distance > 0: an obstacle whose CURRENT position is not closer to the robot than it is dropped
+ *                    (removeDistantObstacles, :81-93; no wrapper the reference ships calls it: off by default)
+ *   closest M        more than max_obstacles left: the max_obstacles with the smallest min_k ((k + 1) 0.6) |pred_k - (p + (v k)(cos psi, sin psi))|,
+ *                    k < N, from min_dist = 1e5, in ascending order of it (ensureObstacleSize, :104-150; `v k` has no dt in the reference: kept).
+ *                    std::sort leaves ties unspecified: here the lower raw index wins.  The device's cos / sin may differ from
+ *                    libm's in the last bits; they enter this ranking only, never an output value.
+ *   or fewer         the obstacles in raw order, then dummies at (x + 100, y + 100), radius 0, zero velocity, with the constant-velocity
+ *                    prediction in either input mode (getDummyObstacle :49-56, :151-165)
+ *   propagation      propagatePredictionUncertainty (:170-186) `propagate_passes` times over GAUSSIAN predictions, dummies included:
+ *                    major_k = sqrt(major_{k-1}^2 + (sigma_k dt)^2) sequentially over k, the same for minor.  TWO passes is what ros1_jackal.cpp:324-332
+ *                    really does in probabilistic mode (one inside getConstantVelocityPrediction, one in the wrapper); ONE is the simulator wrapper
+ *                    with probabilistic/propagate_uncertainty (ros1_jackalsimulator.cpp:345-346).
+ * Outputs (device, caller-owned, every entry written):
+ *   d_obstacle_pos      f64 [n_scenes][max_obstacles][N][2]
+ *   d_obstacle_shape    f64 [n_scenes][max_obstacles][N][3]   (angle, major, minor)
+ *   d_obstacle_radius   f64 [n_scenes][max_obstacles]
+ *   d_obstacle_gaussian u8  [n_scenes][max_obstacles]         1 = PredictionType::GAUSSIAN
+ *   d_selected          i32 [n_scenes][max_obstacles]         raw slot, -1 = dummy
+ * Equal bit for bit to mpc_planner_amd.modules.prepare_obstacles (no FMA contraction, same operation order).  options == NULL: the defaults below.
+ * TMPC_ERR_INVALID: a NULL required pointer, both or neither of d_raw_vel / d_raw_pred, n_scenes <= 0, n_slots outside [0, 1024], max_obstacles
+ * outside [1, 4096], propagate_passes outside 0..2, probabilistic outside 0 / 1, noise < 0, an options->size this library cannot honour (shorter
+ * than its struct, or longer with a non-zero tail, like tmpc_create_v2), a generated solver. */
+typedef struct tmpc_obstacle_options {
+    uint32_t size;                 /* sizeof(tmpc_obstacle_options) of the caller's header */
+    int32_t probabilistic;         /* probabilistic/enable: 0 (default) / 1 */
+    int32_t propagate_passes;      /* 0 (default), 1 or 2 */
+    int32_t reserved;              /* 0 */
+    double noise;                  /* the reference's 0.3 (data_preparation.cpp:65); used in probabilistic mode only */
+    double max_obstacle_distance;  /* <= 0 (default): no distance filter */
+} tmpc_obstacle_options;
+int tmpc_prepare_obstacles(tmpc_handle *h, int32_t n_scenes, int32_t n_slots, int32_t max_obstacles, const void *d_count, const void *d_state,
+                           const void *d_raw_pos, const void *d_raw_radius, const void *d_raw_vel, const void *d_raw_pred,
+                           const tmpc_obstacle_options *options, void *d_obstacle_pos, void *d_obstacle_shape, void *d_obstacle_radius,
+                           void *d_obstacle_gaussian, void *d_selected);
+/* The collision columns of the CURRENT batch's parameter rows, in place, from those four buffers (max_obstacles = dims.M obstacles per scene):
+ * d_scene_of i32 [B], d_state f64 [n_scenes][4].  One thread per (trajectory, stage, obstacle); both models' parameter strides.
+ *   row_model 0  EllipsoidConstraints::update + setParameters (ellipsoid_constraints.cpp:24-90): stage 0 the dummies (x + 50, y + 50, 0, 0, 0, 1, 0.1)
+ *                in the column order x, y, psi, major, minor, chi, r; stage k >= 1 prediction step k - 1 and the obstacle's own radius; a
+ *                DETERMINISTIC obstacle gets major = minor = 0, chi = 1 whatever the shape buffer holds (:72-77), a GAUSSIAN one its radii and
+ *                `chi` = ExponentialQuantile(0.5, 1 - risk) = -log(risk) / 0.5, evaluated by the CALLER (no device logarithm enters)
+ *   row_model 1  GaussianConstraints (gaussian_constraints.cpp:22-79) as mpc_planner_amd.modules.gaussian_set_parameters has it: stage 0
+ *                (x + 100, y + 100, 0.1, 0.1, 0.05, 0.1), then x, y, major, minor (0 for a DETERMINISTIC obstacle), `risk`, and in the r column
+ *                `obstacle_radius`, the CONFIGURED radius (CONFIG["obstacle_radius"], :74), not the prepared obstacle's own
+ * and ego_disc_radius = robot_radius, ego_disc_0_offset = disc_offset at every stage.  No other column is touched.  Stream-ordered, no allocation,
+ * no synchronisation.  TMPC_ERR_INVALID: no batch, a problem without obstacle rows (M = 0), a NULL pointer, a generated solver. */
+int tmpc_set_obstacle_parameters(tmpc_handle *h, const void *d_obstacle_pos, const void *d_obstacle_shape, const void *d_obstacle_radius,
+                                 const void *d_obstacle_gaussian, const void *d_scene_of, const void *d_state, double robot_radius,
+                                 double disc_offset, double risk, double chi, double obstacle_radius);
+
 /* ---- scenario -> polygon construction of SH-MPC on device.  Replaces what the reference gets from the
  * external scenario_module (scenario_constraints.cpp:47 update, :76-79 setParameters; source absent -> restated, see
  * mpc_planner_amd/modules.py::scenario_halfspaces): for every trajectory b and stage k >= 1, each of the n_pts sampled

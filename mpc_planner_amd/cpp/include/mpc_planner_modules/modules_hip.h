@@ -47,6 +47,12 @@ namespace MPCPlanner
         double risk{0.05};                                   /* probabilistic/risk */
         double obstacle_radius{0.35};                        /* obstacle_radius (GaussianConstraints uses the configured value, not the obstacle's own) */
         int max_obstacles{8};
+        int N{SOLVER_N};                                     /* N (mpc_planner/data_preparation.h: the steps of a prediction) */
+        double integrator_step{0.2};                         /* integrator_step */
+        double max_obstacle_distance{0.};                    /* max_obstacle_distance; read by removeDistantObstacles only, which no wrapper the reference ships
+                                                                calls (<= 0: the batched twin applies no filter) */
+        bool probabilistic_enable{false};                    /* probabilistic/enable */
+        bool propagate_uncertainty{false};                   /* probabilistic/propagate_uncertainty (ros1_jackalsimulator.cpp:345-346) */
         int n_other_halfspaces{0};                           /* linearized_constraints/add_halfspaces */
         std::map<std::string, double> weights;               /* weights/<name> */
         bool dynamic_velocity_reference{false};              /* contouring/dynamic_velocity_reference */

@@ -88,6 +88,8 @@ __global__ void tmpc_linearize_topology_kernel(Dims d, int B, const double *x0, 
                                                const int *scene_of, const double *state_x, double robot_radius,
                                                const uint8_t *is_original, int n_obs, const double *obst_radius, const double *stat, int n_static)
 {
+#pragma clang fp contract(off)                                          // the rows too are the mirror's (modules.py::linearized_update) bit for bit: a batch whose rows
+                                                                        // were built here solves exactly like the same batch built on the host (tests/test_gpu_obstacles.py)
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const int N = d.N;
     if (e >= B * N) return;
@@ -200,6 +202,146 @@ __global__ void tmpc_road_halfspaces_kernel(Dims d, int B, int n_scenes, const d
         frame(br, px, py, ax, ay);
         const double vr = ax * (px - ax * off_second) + ay * (py - ay * off_second);
         row[3] = ax; row[4] = ay; row[5] = vr;
+    }
+}
+
+// ---- obstacle preparation on device (mpc_planner/src/data_preparation.cpp; what a wrapper's obstacle callback does before solveMPC) -----------
+// one workgroup per scene q: the scene's raw obstacle list (count[q] clipped to [0, R] of R slots) becomes exactly M prepared obstacles.
+//   predictions   raw_vel: step i = pos + (vel dt) i, angle 0, major = minor = (probabilistic ? noise : 0), GAUSSIAN iff probabilistic
+//                 (getConstantVelocityPrediction, :58-79);  raw_pred [R][N][5] = (x, y, angle, major, minor): as given, GAUSSIAN iff probabilistic
+//                 and the last step's major != 0 (ros1_jackalsimulator.cpp:331-334)
+//   filter        max_dist > 0: a slot whose current position is not closer to the robot than max_dist does not exist (removeDistantObstacles, :81-93)
+//   selection     more than M left: the M with the smallest key  min_k ((k + 1) 0.6) |pred_k - (p + (v k) (cos psi, sin psi))|, from 1e5, in
+//                 ascending (key, raw index) order (ensureObstacleSize, :104-150; the lower raw index wins a tie);
+//                 M or fewer: raw order, then dummies at (x + 100, y + 100), radius 0, zero velocity, with the constant-velocity prediction
+//                 whatever the input mode (:49-56, :151-165)
+//   propagation   `passes` times over GAUSSIAN predictions: major_k = sqrt(major_{k-1}^2 + (sigma_k dt)^2) sequentially over k, the same for
+//                 minor (propagatePredictionUncertainty, :170-186) -- one lane per (obstacle, axis), the passes fused: pass p + 1 consumes step k
+//                 of pass p as soon as it exists, so no intermediate prediction is stored.
+// Slot i's key and validity go into LDS (slots [0, count) only: the only ones read); a slot's rank is the number of smaller (key, index)
+// pairs, O(R^2) per scene, which at R <= 1024 is nothing and needs no sort network; then all lanes write the M x N prediction entries.
+// cos / sin of the device may differ from libm's in the last bits: they enter the ranking key only, never an output value.
+// No FMA contraction, the operation order of modules.py::prepare_obstacles: every output is bit-equal to the host mirror.
+constexpr int PREP_MAX_SLOTS = 1024, PREP_THREADS = 256;
+__global__ __launch_bounds__(PREP_THREADS) void tmpc_prepare_obstacles_kernel(int N, double dt, int R, int M, const int *count, const double *state,
+                                                                            const double *raw_pos, const double *raw_radius, const double *raw_vel,
+                                                                            const double *raw_pred, int probabilistic, double noise, int passes,
+                                                                            double max_dist, double *out_pos, double *out_shape, double *out_radius,
+                                                                            uint8_t *out_gauss, int *out_sel)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_key[PREP_MAX_SLOTS];
+    __shared__ unsigned char s_valid[PREP_MAX_SLOTS];
+    __shared__ int s_nvalid;
+    extern __shared__ int s_sel[];                                       // [M]: raw slot of prepared obstacle m, -1 = dummy
+    const int q = blockIdx.x, tid = threadIdx.x;
+    int cnt = count[q];
+    cnt = cnt < 0 ? 0 : (cnt > R ? R : cnt);
+    const double x = state[(size_t)q * 4], y = state[(size_t)q * 4 + 1], psi = state[(size_t)q * 4 + 2], v = state[(size_t)q * 4 + 3];
+    const double *rp = raw_pos + (size_t)q * R * 2, *rv = raw_vel ? raw_vel + (size_t)q * R * 2 : nullptr;
+    const double *pr = raw_pred ? raw_pred + (size_t)q * R * N * 5 : nullptr;
+    const double sigma = probabilistic ? noise : 0.0;
+    if (tid == 0) s_nvalid = 0;
+    for (int m = tid; m < M; m += PREP_THREADS) s_sel[m] = -1;
+    __syncthreads();
+    const double c = cos(psi), s = sin(psi);
+    for (int i = tid; i < cnt; i += PREP_THREADS) {
+        const double px = rp[i * 2], py = rp[i * 2 + 1];
+        bool valid = true;
+        if (max_dist > 0.0) { const double dx = px - x, dy = py - y; valid = sqrt(dx * dx + dy * dy) < max_dist; }
+        double best = 1e5;
+        for (int k = 0; k < N; k++) {
+            const double ox = pr ? pr[((size_t)i * N + k) * 5] : px + (rv[i * 2] * dt) * (double)k;
+            const double oy = pr ? pr[((size_t)i * N + k) * 5 + 1] : py + (rv[i * 2 + 1] * dt) * (double)k;
+            const double vk = v * (double)k;
+            const double dx = ox - (x + vk * c), dy = oy - (y + vk * s);
+            const double dist = ((double)(k + 1) * 0.6) * sqrt(dx * dx + dy * dy);
+            if (dist < best) best = dist;
+        }
+        s_key[i] = best; s_valid[i] = valid ? 1 : 0;
+        if (valid) atomicAdd(&s_nvalid, 1);
+    }
+    __syncthreads();
+    const bool closest = s_nvalid > M;
+    for (int i = tid; i < cnt; i += PREP_THREADS) {
+        if (!s_valid[i]) continue;
+        const double ki = s_key[i];
+        int rank = 0;
+        if (closest) { for (int j = 0; j < cnt; j++) if (s_valid[j] && (s_key[j] < ki || (s_key[j] == ki && j < i))) rank++; }    // (counted to the end: stopping at M smaller pairs was measured 30 % slower at R = 1024 -- the exit test breaks up the LDS reads)
+        else for (int j = 0; j < i; j++) rank += s_valid[j];
+        if (rank < M) s_sel[rank] = i;
+    }
+    __syncthreads();
+    auto is_gaussian = [&](int i) { return probabilistic && (i < 0 || !pr || pr[((size_t)i * N + (N - 1)) * 5 + 3] != 0.0); };
+    for (int e = tid; e < M * N; e += PREP_THREADS) {
+        const int m = e / N, k = e - m * N, i = s_sel[m];
+        const size_t o = ((size_t)q * M + m) * N + k;
+        double ox, oy, ang = 0.0, major = sigma, minor = sigma;
+        if (i < 0) { ox = x + 100.0; oy = y + 100.0; }
+        else if (pr) { const double *g = pr + ((size_t)i * N + k) * 5; ox = g[0]; oy = g[1]; ang = g[2]; major = g[3]; minor = g[4]; }
+        else { ox = rp[i * 2] + (rv[i * 2] * dt) * (double)k; oy = rp[i * 2 + 1] + (rv[i * 2 + 1] * dt) * (double)k; }
+        out_pos[o * 2] = ox; out_pos[o * 2 + 1] = oy;
+        out_shape[o * 3] = ang;
+        if (passes == 0 || !is_gaussian(i)) { out_shape[o * 3 + 1] = major; out_shape[o * 3 + 2] = minor; }     // (else: the chain below writes them)
+        if (k == 0) {
+            out_radius[(size_t)q * M + m] = i < 0 ? 0.0 : raw_radius[(size_t)q * R + i];
+            out_gauss[(size_t)q * M + m] = is_gaussian(i) ? 1 : 0;
+            out_sel[(size_t)q * M + m] = i;
+        }
+    }
+    if (passes > 0)
+        for (int t = tid; t < 2 * M; t += PREP_THREADS) {
+            const int m = t >> 1, axis = t & 1, i = s_sel[m];
+            if (!is_gaussian(i)) continue;
+            double acc0 = 0.0, acc1 = 0.0;
+            for (int k = 0; k < N; k++) {
+                double val = (i < 0 || !pr) ? sigma : pr[((size_t)i * N + k) * 5 + 3 + axis];
+                const double s0 = val * dt;
+                acc0 = sqrt(acc0 * acc0 + s0 * s0); val = acc0;
+                if (passes > 1) { const double s1 = val * dt; acc1 = sqrt(acc1 * acc1 + s1 * s1); val = acc1; }
+                out_shape[(((size_t)q * M + m) * N + k) * 3 + 1 + axis] = val;
+            }
+        }
+}
+
+// ---- the collision columns of the current batch's parameter rows from prepared obstacles (tmpc_prepare_obstacles' four buffers) --------------
+// one thread per (trajectory, stage, obstacle).  row_model 0: EllipsoidConstraints::update + setParameters (ellipsoid_constraints.cpp:24-90) --
+// stage 0 the dummies (x + 50, y + 50, 0, 0, 0, 1, 0.1) in the column order x, y, psi, major, minor, chi, r; stage k >= 1 prediction step k - 1;
+// a DETERMINISTIC obstacle major = minor = 0, chi = 1 whatever the shape buffer holds (:72-77), a GAUSSIAN one its radii and chi =
+// ExponentialQuantile(0.5, 1 - risk), evaluated by the HOST (no device logarithm enters).  row_model 1: GaussianConstraints as
+// modules.py::gaussian_set_parameters has it (gaussian_constraints.cpp:22-79): stage 0 (x + 100, y + 100, 0.1, 0.1, 0.05, 0.1), then x, y,
+// major, minor (0 for a DETERMINISTIC obstacle, like the mirror fed by modules.py::prepare_obstacles), risk and the CONFIGURED obstacle radius.  ego_disc_radius / ego_disc_0_offset at every stage.  Nothing else is touched.
+__global__ void tmpc_set_obstacle_parameters_kernel(Dims d, int B, double *params, const double *opos, const double *oshape, const double *oradius,
+                                                    const uint8_t *ogauss, const int *scene_of, const double *state, double robot_radius,
+                                                    double disc_offset, double chi, double risk, double config_radius)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = d.N, M = d.M;
+    if (e >= B * N * M) return;
+    const int j = e % M, k = (e / M) % N, b = e / (M * N);
+    const int sc = scene_of[b];
+    double *p = params + ((size_t)b * N + k) * d.npar;
+    if (j == 0) { p[ip_disc_radius(d)] = robot_radius; p[ip_disc_offset(d)] = disc_offset; }
+    const double x = state[(size_t)sc * 4], y = state[(size_t)sc * 4 + 1];
+    const size_t o = (((size_t)sc * M + j) * N + (k > 0 ? k - 1 : 0));
+    const bool gaussian = ogauss[(size_t)sc * M + j] != 0;
+    if (d.row_model == 0) {
+        double val[7] = {x + 50.0, y + 50.0, 0.0, 0.0, 0.0, 1.0, 0.1};
+        if (k > 0) {
+            val[0] = opos[o * 2]; val[1] = opos[o * 2 + 1]; val[2] = oshape[o * 3];
+            val[3] = gaussian ? oshape[o * 3 + 1] : 0.0; val[4] = gaussian ? oshape[o * 3 + 2] : 0.0; val[5] = gaussian ? chi : 1.0;
+            val[6] = oradius[(size_t)sc * M + j];
+        }
+#pragma unroll
+        for (int w = 0; w < 7; w++) p[ip_ellipsoid(d, j, w)] = val[w];
+    } else {
+        double val[6] = {x + 100.0, y + 100.0, 0.1, 0.1, 0.05, 0.1};
+        if (k > 0) {
+            val[0] = opos[o * 2]; val[1] = opos[o * 2 + 1]; val[2] = gaussian ? oshape[o * 3 + 1] : 0.0; val[3] = gaussian ? oshape[o * 3 + 2] : 0.0;
+            val[4] = risk; val[5] = config_radius;
+        }
+#pragma unroll
+        for (int w = 0; w < 6; w++) p[ip_gauss(d, j, w)] = val[w];
     }
 }
 

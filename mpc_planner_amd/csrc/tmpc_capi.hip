@@ -1271,6 +1271,71 @@ int tmpc_road_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scenes
     return TMPC_OK;
 }
 
+int tmpc_prepare_obstacles(tmpc_handle *h, int32_t n_scenes, int32_t n_slots, int32_t max_obstacles, const void *d_count, const void *d_state,
+                           const void *d_raw_pos, const void *d_raw_radius, const void *d_raw_vel, const void *d_raw_pred,
+                           const tmpc_obstacle_options *options, void *d_obstacle_pos, void *d_obstacle_shape, void *d_obstacle_radius,
+                           void *d_obstacle_gaussian, void *d_selected)
+{
+#ifdef TMPC_GENERATED_STAGE
+    if (h) h->err = "tmpc_prepare_obstacles: not available in a generated solver (its parameter layout is the module stack's)";
+    return TMPC_ERR_INVALID;
+#endif
+    if (!h) return TMPC_ERR_INVALID;
+    tmpc_obstacle_options o{};                                        // NULL: the defaults (deterministic, no passes, no distance filter)
+    o.size = sizeof(o); o.noise = 0.3;
+    if (options) {
+        // like tmpc_create_v2: the caller's struct may be longer (a newer header) only with a zero tail; there is no shorter revision
+        if (options->size < sizeof(o)) { h->err = "tmpc_prepare_obstacles: options->size is smaller than tmpc_obstacle_options"; return TMPC_ERR_INVALID; }
+        const unsigned char *tail = reinterpret_cast<const unsigned char *>(options);
+        for (uint32_t i = sizeof(o); i < options->size; i++)
+            if (tail[i]) { h->err = "tmpc_prepare_obstacles: options holds a non-zero field this library does not know"; return TMPC_ERR_INVALID; }
+        o = *options;
+    }
+    if (n_scenes <= 0) { h->err = "tmpc_prepare_obstacles: n_scenes must be positive"; return TMPC_ERR_INVALID; }
+    if (n_slots < 0 || n_slots > tmpc::PREP_MAX_SLOTS) { h->err = "tmpc_prepare_obstacles: 0 <= n_slots <= 1024"; return TMPC_ERR_INVALID; }
+    if (max_obstacles <= 0 || max_obstacles > 4096) { h->err = "tmpc_prepare_obstacles: 1 <= max_obstacles <= 4096"; return TMPC_ERR_INVALID; }
+    if (!d_count || !d_state || !d_raw_pos || !d_raw_radius) { h->err = "tmpc_prepare_obstacles: NULL input (d_count, d_state, d_raw_pos, d_raw_radius)"; return TMPC_ERR_INVALID; }
+    if ((d_raw_vel == nullptr) == (d_raw_pred == nullptr)) { h->err = "tmpc_prepare_obstacles: exactly one of d_raw_vel and d_raw_pred"; return TMPC_ERR_INVALID; }
+    if (!d_obstacle_pos || !d_obstacle_shape || !d_obstacle_radius || !d_obstacle_gaussian || !d_selected) {
+        h->err = "tmpc_prepare_obstacles: NULL output buffer"; return TMPC_ERR_INVALID;
+    }
+    if (o.propagate_passes < 0 || o.propagate_passes > 2) { h->err = "tmpc_prepare_obstacles: propagate_passes is 0, 1 or 2"; return TMPC_ERR_INVALID; }
+    if ((o.probabilistic != 0 && o.probabilistic != 1) || !(o.noise >= 0.0)) { h->err = "tmpc_prepare_obstacles: probabilistic is 0 or 1, noise >= 0"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_prepare_obstacles_kernel, dim3((unsigned)n_scenes), dim3(tmpc::PREP_THREADS), (size_t)max_obstacles * sizeof(int), h->stream,
+                       h->d.N, h->d.dt, n_slots, max_obstacles, (const int *)d_count, (const double *)d_state, (const double *)d_raw_pos,
+                       (const double *)d_raw_radius, (const double *)d_raw_vel, (const double *)d_raw_pred, o.probabilistic, o.noise, o.propagate_passes,
+                       o.max_obstacle_distance, (double *)d_obstacle_pos, (double *)d_obstacle_shape, (double *)d_obstacle_radius,
+                       (uint8_t *)d_obstacle_gaussian, (int *)d_selected);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
+int tmpc_set_obstacle_parameters(tmpc_handle *h, const void *d_obstacle_pos, const void *d_obstacle_shape, const void *d_obstacle_radius,
+                                 const void *d_obstacle_gaussian, const void *d_scene_of, const void *d_state, double robot_radius,
+                                 double disc_offset, double risk, double chi, double obstacle_radius)
+{
+#ifdef TMPC_GENERATED_STAGE
+    if (h) h->err = "tmpc_set_obstacle_parameters: not available in a generated solver (its parameter layout is the module stack's)";
+    return TMPC_ERR_INVALID;
+#endif
+    if (!h) return TMPC_ERR_INVALID;
+    if (h->B <= 0 || !h->params) { h->err = "tmpc_set_obstacle_parameters: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
+    if (h->d.M <= 0) { h->err = "tmpc_set_obstacle_parameters: the problem has no obstacle rows (M = 0)"; return TMPC_ERR_INVALID; }
+    if (!d_obstacle_pos || !d_obstacle_shape || !d_obstacle_radius || !d_obstacle_gaussian || !d_scene_of || !d_state) {
+        h->err = "tmpc_set_obstacle_parameters: NULL argument"; return TMPC_ERR_INVALID;
+    }
+    const int64_t n = (int64_t)h->B * h->d.N * h->d.M;
+    if (n > 0x7fffffff) { h->err = "tmpc_set_obstacle_parameters: B x N x M too large"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_set_obstacle_parameters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B,
+                       const_cast<double *>(h->params), (const double *)d_obstacle_pos, (const double *)d_obstacle_shape,
+                       (const double *)d_obstacle_radius, (const uint8_t *)d_obstacle_gaussian, (const int *)d_scene_of, (const double *)d_state,
+                       robot_radius, disc_offset, chi, risk, obstacle_radius);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
 int tmpc_scenario_halfspaces(tmpc_handle *h, const void *d_samples, int32_t n_pts, int32_t n_rows, const void *d_scene_of,
                              const void *d_state_x, double radius, double disc_offset)
 {

@@ -572,3 +572,154 @@ def map_guidance_trajectories_to_planners(planner_guidance_ids, topology_classes
             if not taken[p]:
                 mapping[i] = p; taken[p] = True; existing[p] = False
     return mapping, taken, existing
+
+
+# ---- obstacle preparation: host mirror of mpc_planner/src/data_preparation.cpp and of tmpc_prepare_obstacles_kernel, bit for bit -----------
+# An obstacle set is a dict of arrays over n obstacles: position [n][2] (the current position), pos [n][N][2], angle / major / minor [n][N]
+# (mode 0 of the prediction), radius [n], gaussian [n] (bool: PredictionType::GAUSSIAN, else DETERMINISTIC).
+OBSTACLE_NOISE = 0.3            # getConstantVelocityPrediction's `noise` in probabilistic mode (data_preparation.cpp:65)
+OBSTACLE_KEYS = ("position", "pos", "angle", "major", "minor", "radius", "gaussian")
+
+
+def define_robot_area(length, width, n_discs):
+    """defineRobotArea (data_preparation.cpp:16-47): the discs that cover a length x width robot.  Returns (offsets [n_discs], radius):
+    one disc sits at offset 0; otherwise the first at the back, the last at the front, the others spread evenly, every radius width / 2."""
+    assert n_discs > 0, "Trying to create a collision region with less than a disc"          # (:23)
+    center_offset = length / 2.0
+    radius = width / 2.0
+    if n_discs == 1:
+        return np.array([0.0]), radius
+    off = np.zeros(n_discs)
+    for i in range(n_discs):
+        if i == 0:
+            off[i] = -center_offset + radius
+        elif i == n_discs - 1:
+            off[i] = -center_offset + length - radius
+        else:
+            off[i] = -center_offset + radius + float(i) * (length - 2.0 * radius) / (float(n_discs) - 1.0)
+    return off, radius
+
+
+def propagate_prediction_uncertainty(major, minor, dt):
+    """propagatePredictionUncertainty (data_preparation.cpp:170-186) on one GAUSSIAN prediction: major_k = sqrt(major_{k-1}^2 + (sigma_k dt)^2)
+    sequentially over k from 0, the same for minor; squares written x * x (what std::pow(x, 2.) evaluates to).  major, minor [N] -> new arrays."""
+    major = np.array(major, float); minor = np.array(minor, float)
+    a = 0.0; b = 0.0
+    for k in range(len(major)):
+        sa = major[k] * dt; sb = minor[k] * dt
+        a = np.sqrt(a * a + sa * sa); b = np.sqrt(b * b + sb * sb)
+        major[k] = a; minor[k] = b
+    return major, minor
+
+
+def constant_velocity_prediction(position, velocity, dt, steps, probabilistic=False, noise=OBSTACLE_NOISE, propagate=True):
+    """getConstantVelocityPrediction (data_preparation.cpp:58-79): step i = position + (velocity dt) i, angle 0, major = minor = noise
+    (0 unless probabilistic, :61-66); GAUSSIAN iff probabilistic, and then one propagatePredictionUncertainty pass (:75-76; propagate=False
+    leaves it to the caller, as prepare_obstacles counts the passes itself).  Returns dict(pos [steps][2], angle, major, minor [steps], gaussian)."""
+    position = np.asarray(position, float); velocity = np.asarray(velocity, float)
+    i = np.arange(steps, dtype=float)[:, None]
+    sigma = float(noise) if probabilistic else 0.0
+    major = np.full(steps, sigma); minor = np.full(steps, sigma)
+    if probabilistic and propagate:
+        major, minor = propagate_prediction_uncertainty(major, minor, dt)
+    return dict(pos=position[None, :] + (velocity[None, :] * dt) * i, angle=np.zeros(steps), major=major, minor=minor,
+                gaussian=bool(probabilistic))
+
+
+def _take_obstacles(obs, idx):
+    return {k: np.asarray(obs[k])[idx] for k in OBSTACLE_KEYS}
+
+
+def remove_distant_obstacles(obs, state, max_obstacle_distance):
+    """removeDistantObstacles (data_preparation.cpp:81-93): keeps the obstacles whose CURRENT position is closer to the robot than
+    max_obstacle_distance (strict '<'), in their order.  Returns (obstacle set, kept indices)."""
+    dx = np.asarray(obs["position"], float)[:, 0] - state[0]; dy = np.asarray(obs["position"], float)[:, 1] - state[1]
+    keep = np.flatnonzero(np.sqrt(dx * dx + dy * dy) < max_obstacle_distance)
+    return _take_obstacles(obs, keep), keep
+
+
+def obstacle_selection_distance(pred_pos, state):
+    """The ranking key of ensureObstacleSize (data_preparation.cpp:113-131) for predictions pred_pos [n][N][2] and state (x, y, psi, v):
+    min over k < N of ((k + 1) 0.6) |pred_k - (p + (v k) (cos psi, sin psi))|, starting from min_dist = 1e5.  `v k` carries no dt in the
+    reference; kept."""
+    pred_pos = np.asarray(pred_pos, float)
+    n, N, _ = pred_pos.shape
+    c, s = np.cos(state[2]), np.sin(state[2])
+    out = np.full(n, 1e5)
+    for k in range(N):
+        vk = state[3] * float(k)
+        dx = pred_pos[:, k, 0] - (state[0] + vk * c); dy = pred_pos[:, k, 1] - (state[1] + vk * s)
+        dist = (float(k + 1) * 0.6) * np.sqrt(dx * dx + dy * dy)
+        out = np.where(dist < out, dist, out)
+    return out
+
+
+def ensure_obstacle_size(obs, state, max_obstacles, dt, probabilistic=False, noise=OBSTACLE_NOISE):
+    """ensureObstacleSize (data_preparation.cpp:95-168): exactly max_obstacles obstacles.  More: the max_obstacles with the smallest
+    obstacle_selection_distance, in ascending order of it (:104-150) -- std::sort leaves ties unspecified, here the lower index wins
+    (DESIGN.md U13).  Fewer: the obstacles in their order, then dummies (getDummyObstacle, :49-56: position (x + 100, y + 100), radius 0)
+    with the constant-velocity prediction of zero velocity (:155-164; its uncertainty pass is left to the caller).
+    Returns (obstacle set, selected [max_obstacles]: index into `obs`, -1 = dummy)."""
+    n = len(obs["radius"]); M = int(max_obstacles)
+    N = np.asarray(obs["pos"]).shape[1]
+    if n > M:
+        dist = obstacle_selection_distance(obs["pos"], state)
+        sel = np.lexsort((np.arange(n), dist))[:M]                   # by distance, then index
+        return _take_obstacles(obs, sel), sel.astype(np.int32)
+    out = _take_obstacles(obs, np.arange(n))
+    out = {k: np.array(v) for k, v in out.items()}
+    for _ in range(M - n):
+        p = np.array([state[0] + 100.0, state[1] + 100.0])
+        cv = constant_velocity_prediction(p, np.zeros(2), dt, N, probabilistic, noise, propagate=False)
+        out["position"] = np.concatenate([out["position"].reshape(-1, 2), p[None]])
+        out["radius"] = np.concatenate([out["radius"], [0.0]])
+        out["gaussian"] = np.concatenate([out["gaussian"].astype(bool), [cv["gaussian"]]])
+        for key in ("pos", "angle", "major", "minor"):
+            out[key] = np.concatenate([out[key].reshape((-1,) + cv[key].shape), cv[key][None]])
+    return out, np.concatenate([np.arange(n), np.full(M - n, -1)]).astype(np.int32)
+
+
+def prepare_obstacles(state, raw_pos, raw_radius, M, N, dt, raw_vel=None, raw_pred=None, probabilistic=False, noise=OBSTACLE_NOISE,
+                      propagate_passes=0, max_obstacle_distance=0.0, risk=0.05):
+    """What a wrapper's obstacle callback does before Planner::solveMPC, for one scene (host mirror of tmpc_prepare_obstacles, bit for bit):
+    predictions -- constant velocity from raw_vel [n][2] (ros1_jackal.cpp:324-329) or given, raw_pred [n][N][5] = (x, y, angle, major,
+    minor), GAUSSIAN iff probabilistic and the last step's major != 0 (ros1_jackalsimulator.cpp:331-334) --, the optional distance filter
+    (removeDistantObstacles; no shipped wrapper calls it: off for max_obstacle_distance <= 0), ensureObstacleSize to exactly M, and
+    propagate_passes propagatePredictionUncertainty passes over the GAUSSIAN predictions (dummies included).  Two passes is what
+    ros1_jackal.cpp:324-332 does in probabilistic mode (one inside getConstantVelocityPrediction, one in the wrapper), one is
+    ros1_jackalsimulator.cpp:345-346.  state = (x, y, psi, v).
+    Returns the dict ellipsoid_set_parameters / gaussian_set_parameters take -- pos [M][N][2], angle, major, minor [M][N], radius [M],
+    chi [M]; a DETERMINISTIC obstacle carries major = minor = 0, chi = 1 (ellipsoid_constraints.cpp:72-77), a GAUSSIAN one
+    chi = -log(risk) / 0.5 (ExponentialQuantile(0.5, 1 - risk), :80) -- plus selected [M] (raw index, -1 = dummy), gaussian [M] and
+    shape [M][N][3] = (angle, major, minor) as predicted, whatever the type (the device's d_obstacle_shape)."""
+    assert (raw_vel is None) != (raw_pred is None), "exactly one of raw_vel / raw_pred"
+    raw_pos = np.asarray(raw_pos, float).reshape(-1, 2); raw_radius = np.asarray(raw_radius, float).reshape(-1)
+    n = len(raw_radius)
+    obs = dict(position=raw_pos, pos=np.zeros((n, N, 2)), angle=np.zeros((n, N)), major=np.zeros((n, N)), minor=np.zeros((n, N)),
+               radius=raw_radius, gaussian=np.zeros(n, bool))
+    for j in range(n):
+        if raw_vel is not None:
+            cv = constant_velocity_prediction(raw_pos[j], np.asarray(raw_vel, float)[j], dt, N, probabilistic, noise, propagate=False)
+            for key in ("pos", "angle", "major", "minor"):
+                obs[key][j] = cv[key]
+            obs["gaussian"][j] = cv["gaussian"]
+        else:
+            pr = np.asarray(raw_pred, float)[j]
+            obs["pos"][j] = pr[:, 0:2]; obs["angle"][j] = pr[:, 2]; obs["major"][j] = pr[:, 3]; obs["minor"][j] = pr[:, 4]
+            obs["gaussian"][j] = bool(probabilistic) and pr[N - 1, 3] != 0.0
+    raw_index = np.arange(n)
+    if max_obstacle_distance > 0.0:
+        obs, raw_index = remove_distant_obstacles(obs, state, max_obstacle_distance)
+    obs, sel = ensure_obstacle_size(obs, state, M, dt, probabilistic, noise)
+    selected = np.where(sel >= 0, raw_index[np.maximum(sel, 0)] if len(raw_index) else -1, -1).astype(np.int32)
+    major = np.array(obs["major"], float); minor = np.array(obs["minor"], float)
+    gauss = np.asarray(obs["gaussian"], bool)
+    for _ in range(int(propagate_passes)):
+        for j in range(M):
+            if gauss[j]:
+                major[j], minor[j] = propagate_prediction_uncertainty(major[j], minor[j], dt)
+    shape = np.stack([np.asarray(obs["angle"], float), major, minor], 2)
+    live = gauss[:, None]
+    return dict(pos=np.asarray(obs["pos"], float), angle=np.asarray(obs["angle"], float), radius=np.asarray(obs["radius"], float),
+                major=np.where(live, major, 0.0), minor=np.where(live, minor, 0.0),
+                chi=np.where(gauss, -np.log(risk) / 0.5, 1.0), selected=selected, gaussian=gauss, shape=shape)

@@ -48,7 +48,14 @@ EXPORTS = ["tmpc_default_dims", "tmpc_default_dims_ex", "tmpc_create", "tmpc_des
            "tmpc_reset_multipliers", "tmpc_get_stream", "tmpc_kernel_info", "tmpc_set_slots", "tmpc_set_param_sharing", "tmpc_copy_state", "tmpc_scenario_empty_stages", "tmpc_sample_scenarios",
            "tmpc_scenario_discard", "tmpc_scenario_discarded", "tmpc_linearize_topology_ex", "tmpc_clear_slot", "tmpc_gather_best",
            "tmpc_create_v2", "tmpc_set_param_sharing_ex", "tmpc_latency_mode_capacity", "tmpc_has_lane_kernels", "tmpc_debug_lds_passes", "tmpc_debug_poison_lds", "tmpc_has_lab_switches",
-           "tmpc_road_halfspaces"]
+           "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters"]
+
+
+class TmpcObstacleOptions(C.Structure):
+    """tmpc_obstacle_options (include/tmpc_hip.h)."""
+    _fields_ = [("size", C.c_uint32), ("probabilistic", C.c_int32), ("propagate_passes", C.c_int32), ("reserved", C.c_int32),
+                ("noise", C.c_double), ("max_obstacle_distance", C.c_double)]
+
 
 class TmpcError(RuntimeError):
     pass
@@ -115,6 +122,9 @@ def load_library(path=None):
         lib.tmpc_linearize_topology_ex.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_double, vp]
     if hasattr(lib, "tmpc_road_halfspaces"):
         lib.tmpc_road_halfspaces.argtypes = [vp, vp, C.c_int32, vp, C.c_double, C.c_double, vp, C.c_int32, C.c_int32]
+    if hasattr(lib, "tmpc_prepare_obstacles"):
+        lib.tmpc_prepare_obstacles.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 6 + [C.POINTER(TmpcObstacleOptions)] + [vp] * 5
+        lib.tmpc_set_obstacle_parameters.argtypes = [vp] + [vp] * 6 + [C.c_double] * 5
     if hasattr(lib, "tmpc_scenario_discarded"):        # (absent from reference builds of earlier rounds used in A/B runs)
         lib.tmpc_scenario_discarded.argtypes = [vp, vp]
     if hasattr(lib, "tmpc_copy_state"):        # (absent from reference builds of earlier rounds used in A/B runs)
@@ -398,6 +408,38 @@ class BatchedSolver:
                                                   C.c_void_p(d_bound_segments) if d_bound_segments else None, float(offset_first),
                                                   float(offset_second), C.c_void_p(d_static_halfspaces) if d_static_halfspaces else None,
                                                   int(n_static), int(first_row)), "tmpc_road_halfspaces")
+
+    def prepare_obstacles(self, n_scenes, n_slots, max_obstacles, d_count, d_state, d_raw_pos, d_raw_radius, d_obstacle_pos, d_obstacle_shape,
+                          d_obstacle_radius, d_obstacle_gaussian, d_selected, d_raw_vel=None, d_raw_pred=None, probabilistic=False, noise=0.3,
+                          propagate_passes=0, max_obstacle_distance=0.0):
+        """Obstacle preparation on device (tmpc_prepare_obstacles; raw device pointers): per scene the raw list d_raw_pos / d_raw_radius
+        [n_scenes][n_slots] (d_count of them) with velocities d_raw_vel or given predictions d_raw_pred becomes exactly max_obstacles prepared
+        obstacles -- distance filter, closest-M selection or dummies, uncertainty passes -- in d_obstacle_pos [n_scenes][M][N][2] (what
+        linearize_topology_ex reads), d_obstacle_shape [..][N][3], d_obstacle_radius, d_obstacle_gaussian (u8), d_selected (i32) [n_scenes][M].
+        Equal bit for bit to modules.prepare_obstacles.  Needs no batch.  Stream-ordered, no synchronisation."""
+        if not hasattr(self.lib, "tmpc_prepare_obstacles"):
+            raise TmpcError("this library has no tmpc_prepare_obstacles (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        opt = TmpcObstacleOptions(C.sizeof(TmpcObstacleOptions), int(probabilistic), int(propagate_passes), 0, float(noise),
+                                  float(max_obstacle_distance))
+        self._check(self.lib.tmpc_prepare_obstacles(self._h, int(n_scenes), int(n_slots), int(max_obstacles), vp(d_count), vp(d_state), vp(d_raw_pos),
+                                                    vp(d_raw_radius), vp(d_raw_vel), vp(d_raw_pred), C.byref(opt), vp(d_obstacle_pos),
+                                                    vp(d_obstacle_shape), vp(d_obstacle_radius), vp(d_obstacle_gaussian), vp(d_selected)),
+                    "tmpc_prepare_obstacles")
+
+    def set_obstacle_parameters(self, d_obstacle_pos, d_obstacle_shape, d_obstacle_radius, d_obstacle_gaussian, d_scene_of, d_state, robot_radius,
+                                disc_offset=0.0, risk=0.05, obstacle_radius=0.0):
+        """The collision columns of the current batch's parameter rows, in place, from prepare_obstacles' buffers (tmpc_set_obstacle_parameters;
+        raw device pointers): EllipsoidConstraints (row_model 0) or GaussianConstraints (row_model 1; obstacle_radius = the configured radius of
+        its r column), ego_disc_radius and ego_disc_0_offset.  chi = -log(risk) / 0.5 is evaluated here, on the host.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_set_obstacle_parameters"):
+            raise TmpcError("this library has no tmpc_set_obstacle_parameters (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        chi = float(-np.log(risk) / 0.5)                              # ExponentialQuantile(0.5, 1 - risk), ellipsoid_constraints.cpp:80
+        self._check(self.lib.tmpc_set_obstacle_parameters(self._h, vp(d_obstacle_pos), vp(d_obstacle_shape), vp(d_obstacle_radius),
+                                                          vp(d_obstacle_gaussian), vp(d_scene_of), vp(d_state), float(robot_radius),
+                                                          float(disc_offset), float(risk), chi, float(obstacle_radius)),
+                    "tmpc_set_obstacle_parameters")
 
     def scenario_halfspaces(self, d_samples, n_pts, n_rows, d_scene_of, d_state_x, radius, disc_offset=0.0):
         """Device scenario -> halfspace reduction of SH-MPC (raw device pointers; samples [n_scenes][N][n_pts][2]);

@@ -1,13 +1,57 @@
 """Launch the auxiliary device kernels (f-1 topology linearisation, f-2 warm start / guidance init, f-3 scenario reduction,
-records + selection, Contouring's road halfspaces) at the bench batch size; run under `rocprofv3 --kernel-trace --stats` to get their
-durations.  The road kernel works per (scene, stage): it is launched for 512 scenes (bench.py's default), the 64 generated ones repeated."""
-import os, sys
+records + selection, Contouring's road halfspaces, obstacle preparation) at the bench batch size; run under `rocprofv3 --kernel-trace --stats`
+to get their durations.  The road kernel works per (scene, stage): it is launched for 512 scenes (bench.py's default), the 64 generated ones repeated.
+Obstacle preparation (tmpc_prepare_obstacles, tmpc_set_obstacle_parameters) runs at bench.py's default launch, 512 scenes x 64 trajectories, with
+`--slots R` raw-obstacle slots per scene, all of them filled (default 64; `--slots 1024`, the cap, runs the obstacle kernels alone so that a
+profile of that run holds the R = 1024 durations only).  Besides the profile, one JSON line per obstacle kernel: the mean of 50 back-to-back
+launches between two HIP events on the handle's stream (launch gaps included: an upper bound of the kernel time)."""
+import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 torch.cuda.init()
 from mpc_planner_amd import scenes, solver
 dev = torch.device("cuda")
+slots = int(sys.argv[sys.argv.index("--slots") + 1]) if "--slots" in sys.argv else 64
+
+
+def obstacle_kernels(R, n_scenes=512, traj=64, M=8, N=20):
+    rng = np.random.default_rng(7)
+    B = n_scenes * traj
+    so = solver.BatchedSolver(solver.default_dims(), B_max=B)
+    f64 = dict(dtype=torch.float64, device=dev)
+    xinit = torch.zeros((B, 5), **f64); x0 = torch.zeros((B, N + 1, 7), **f64); params = torch.zeros((B, N, so.dims.npar), **f64)
+    so.set_batch_device(B, xinit.data_ptr(), x0.data_ptr(), params.data_ptr())
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    cnt = up(np.full(n_scenes, R, np.int32)); state = up(np.tile([0.0, 0.0, 0.1, 1.2], (n_scenes, 1)))
+    pos = up(np.stack([rng.uniform(1.0, 15.0, (n_scenes, R)), rng.uniform(-5.0, 5.0, (n_scenes, R))], 2)); rad = up(np.full((n_scenes, R), 0.4))
+    vel = up(rng.uniform(-1.0, 1.0, (n_scenes, R, 2)))
+    o_pos = torch.zeros((n_scenes, M, N, 2), **f64); o_shape = torch.zeros((n_scenes, M, N, 3), **f64); o_rad = torch.zeros((n_scenes, M), **f64)
+    o_g = torch.zeros((n_scenes, M), dtype=torch.uint8, device=dev); o_sel = torch.zeros((n_scenes, M), dtype=torch.int32, device=dev)
+    scene_of = up(np.repeat(np.arange(n_scenes, dtype=np.int32), traj))
+    prepare = lambda: so.prepare_obstacles(n_scenes, R, M, cnt.data_ptr(), state.data_ptr(), pos.data_ptr(), rad.data_ptr(), o_pos.data_ptr(), o_shape.data_ptr(),
+                                           o_rad.data_ptr(), o_g.data_ptr(), o_sel.data_ptr(), d_raw_vel=vel.data_ptr(), probabilistic=True, propagate_passes=2)
+    write = lambda: so.set_obstacle_parameters(o_pos.data_ptr(), o_shape.data_ptr(), o_rad.data_ptr(), o_g.data_ptr(), scene_of.data_ptr(), state.data_ptr(), 0.325)
+    hs = torch.cuda.ExternalStream(so.stream_ptr(), device=dev)
+    for name, call in (("tmpc_prepare_obstacles_kernel", prepare), ("tmpc_set_obstacle_parameters_kernel", write)):
+        for _ in range(10):
+            call()
+        so.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(hs):
+            e0.record()
+            for _ in range(50):
+                call()
+            e1.record()
+        so.synchronize()
+        print(json.dumps(dict(kernel=name, n_scenes=n_scenes, trajectories=B, slots=R, M=M, N=N, us_per_launch_events=e0.elapsed_time(e1) * 1e3 / 50)), flush=True)
+    so.close()
+
+
+if "--slots" in sys.argv:
+    obstacle_kernels(slots)
+    print("done")
+    sys.exit(0)
 batch = scenes.make_batch(range(64), N=20, M=8, B=64)
 B = batch["xinit"].shape[0]
 s = solver.BatchedSolver(solver.default_dims(), B_max=B)
@@ -27,4 +71,5 @@ for _ in range(10):
     s.pack_records(t["rec"].data_ptr(), None)
     s.select_best_records(t["rec"].data_ptr(), 1, 64, 64, t["best"].data_ptr())
 s.synchronize(); s.close()
+obstacle_kernels(slots)
 print("done")
