@@ -401,6 +401,60 @@ int tmpc_set_obstacle_parameters(tmpc_handle *h, const void *d_obstacle_pos, con
                                  const void *d_obstacle_gaussian, const void *d_scene_of, const void *d_state, double robot_radius,
                                  double disc_offset, double risk, double chi, double obstacle_radius);
 
+/* ---- the reference path on device: what Contouring::update does every tick (mpc_planner_modules/src/contouring.cpp:28-48) and the segment
+ * window setSplineParameters writes (:94-124).  RosTools::Spline2D::findClosestPoint is not in the reference tree: the search is restated, its
+ * assumptions are DESIGN.md U14.  tmpc_track_path uses S and the stream of the handle only: no batch is needed.  Stream-ordered, no allocation,
+ * no synchronisation.  Inputs (device):
+ *   d_path         f64 [n_scenes][n_seg_max][9]     cubic segments (ax bx cx dx ay by cy dy start), the 9-tuple of the parameter rows
+ *   d_path_count   i32 [n_scenes]                   segments of the scene's path, clipped to [0, n_seg_max];  n_seg_max <= 1024
+ *   d_path_length  f64 [n_scenes]                   the knot behind the last segment: L_i = start_{i+1} - start_i, L_last = length - start_last
+ *   d_bounds       f64 [n_scenes][2][n_seg_max][8]  or NULL: left / right bound cubics on the same knots (with d_bound_window, both or neither)
+ *   d_pos          f64 [n_scenes][pos_stride]       x and y first, pos_stride >= 2: the 4-wide state of tmpc_prepare_obstacles or the 5- / 6-wide
+ *                                                   state of tmpc_warmstart can be passed as they are
+ * In / out:
+ *   d_segment      i32 [n_scenes]                   the previous closest segment; < 0 requests the global search (a new path, a reset)
+ * Closest point on segment i to p, D(t) = |P_i(t) - p|^2, g(t) = (P_i(t) - p).P_i'(t), Horner forms: coarse samples t_j = L_i (j / 8), j = 0..8;
+ * j* = argmin D(t_j), the lowest j on ties; bracket lo = t_max(j*-1,0), hi = t_min(j*+1,8); g(lo) >= 0: t = lo; else g(hi) <= 0: t = hi; else
+ * exactly 40 bisections (mid = (lo + hi) / 2, g(mid) > 0 ? hi = mid : lo = mid) and t = (lo + hi) / 2; the coarse sample wins if D(t_j*) < D(t).
+ * Candidates (U14-1): every segment after a reset, else [max(0, prev - R), min(count - 1, prev + R)] with prev clamped into [0, count - 1]
+ * and R = search_range.  The smallest D wins, the lowest segment on ties; the comparison starts from the first candidate and replaces on
+ * strict `<`, so a NaN / inf position yields the first candidate, never an index out of range.
+ * Outputs (device, caller-owned; every entry of a scene with count > 0 is written, a scene with count <= 0 writes nothing and keeps its segment):
+ *   d_segment      the segment found
+ *   d_closest_s    f64 [n_scenes]                   start_segment + t
+ *   d_window       f64 [n_scenes][S][9]             slot w = segment + w as given (U14-2); beyond the last segment the path continues STRAIGHT
+ *                                                   ALONG ITS END TANGENT (U14-3): (0, 0, x'(end), X(end), 0, 0, y'(end), Y(end)), start = length,
+ *                                                   from the last cubic at t = L_last
+ *   d_bound_window f64 [n_scenes][2][S][8]          or NULL: the bound cubics of the same slots, padded the same way from their own last cubics;
+ *                                                   exactly what tmpc_road_halfspaces takes as d_bound_segments
+ *   d_reached      u8  [n_scenes]                   or NULL: 1 iff |p - P(length)| < 1.0 (Contouring::isObjectiveReached, :167-175)
+ * Equal bit for bit to mpc_planner_amd.modules.track_path (no FMA contraction, same operation order).  One wave per scene, one lane per
+ * candidate segment (strided beyond 64 candidates), a 64-lane argmin on (D, segment).  options == NULL: the defaults below.
+ * TMPC_ERR_INVALID: a NULL required pointer, one of d_bounds / d_bound_window without the other, n_scenes <= 0, n_seg_max outside [1, 1024],
+ * search_range outside [0, 31], pos_stride < 2, an options->size this library cannot honour (like tmpc_obstacle_options), a problem without
+ * path segments (S = 0), a generated solver. */
+typedef struct tmpc_path_options {
+    uint32_t size;                 /* sizeof(tmpc_path_options) of the caller's header */
+    int32_t search_range;          /* R: segments either side of the previous one that are searched; default 2, 0 .. 31 */
+} tmpc_path_options;
+int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const void *d_path, const void *d_path_count, const void *d_path_length,
+                    const void *d_bounds, const void *d_pos, int32_t pos_stride, const tmpc_path_options *options, void *d_segment,
+                    void *d_closest_s, void *d_window, void *d_bound_window, void *d_reached);
+/* The spline columns of the CURRENT batch's parameter rows, in place, from d_window [n_scenes][S][9] as tmpc_track_path wrote it: the 9 S
+ * columns spline_x{i}_{a..d}, spline_y{i}_{a..d}, spline{i}_start of every stage k < N of every entry b with d_scene_of[b] (i32 [B]) inside
+ * [0, n_scenes), and nothing else; an entry whose scene is outside that range is left untouched, so a caller with
+ * TMPC_SHARE_COPIES_NOT_MAINTAINED can name the lead entries only.  A parameter-sharing map stays valid when every entry of a set names the
+ * same scene: equal values go to all of them.  Both models' parameter strides.
+ * Optional d_closest_s (f64 [n_scenes]) with d_state (f64 [B][nx], the layout tmpc_warmstart reads; both or neither): the `spline` entry
+ * (index 4) of each named entry becomes its scene's closest_s -- state.set("spline", closest_s), contouring.cpp:42.
+ * ORDER.  In the reference setXinit(state) and initializeWarmstart(state) run BEFORE the modules' update (planner.cpp:81-96): the `spline`
+ * of xinit is the PREVIOUS tick's closest_s.  Call tmpc_warmstart(d_state) before tmpc_set_path_parameters(..., d_state) to reproduce that;
+ * call it after to start the solve from the fresh value.
+ * Stream-ordered, no allocation, no synchronisation.  TMPC_ERR_INVALID: no batch, a NULL d_window / d_scene_of, n_scenes <= 0, one of
+ * d_closest_s / d_state without the other, a problem without path segments, a generated solver. */
+int tmpc_set_path_parameters(tmpc_handle *h, const void *d_window, const void *d_scene_of, int32_t n_scenes, const void *d_closest_s,
+                             void *d_state);
+
 /* ---- scenario -> polygon construction of SH-MPC on device.  Replaces what the reference gets from the
  * external scenario_module (scenario_constraints.cpp:47 update, :76-79 setParameters; source absent -> restated, see
  * mpc_planner_amd/modules.py::scenario_halfspaces): for every trajectory b and stage k >= 1, each of the n_pts sampled

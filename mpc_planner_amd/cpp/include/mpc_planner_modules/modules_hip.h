@@ -11,7 +11,7 @@
  *
  * Same class and method names, same member semantics; what the reference takes from packages that are not in its tree
  * is an explicit input here: CONFIG[...] (mpc_planner_util, yaml-cpp) -> ModuleConfig; guidance_planner::GlobalGuidance ->
- * std::vector<GuidanceTrajectory>; RosTools::Spline2D -> ModuleData::path segments; scenario_module's sampler / polygon
+ * std::vector<GuidanceTrajectory>; RosTools::Spline2D -> fitted cubic segments (RealTimeData::reference_path = the whole path, reference_path.h; ModuleData::path = the window); scenario_module's sampler / polygon
  * construction -> halfspaces handed in per scenario solver.  The OpenMP loop over local planners becomes: prepare every planner's
  * parameters on the host (same statements, same order), ONE Solver::solveBatch launch, then the reference's bookkeeping.
  * Header-only: everything is small and is compiled against the generated setSolverParameter* functions.
@@ -35,6 +35,7 @@
 #include <mpc_planner_solver/solver_interface.h>
 #include <mpc_planner_types/data_types.h>
 #include <mpc_planner_types/module_data.h>
+#include <mpc_planner_modules/reference_path.h>
 #include <mpc_planner_types/realtime_data.h>
 
 namespace MPCPlanner
@@ -54,6 +55,7 @@ namespace MPCPlanner
         bool probabilistic_enable{false};                    /* probabilistic/enable */
         bool propagate_uncertainty{false};                   /* probabilistic/propagate_uncertainty (ros1_jackalsimulator.cpp:345-346) */
         int n_other_halfspaces{0};                           /* linearized_constraints/add_halfspaces */
+        int path_search_range{2};                            /* segments either side of the previous closest one that Contouring::update searches */
         std::map<std::string, double> weights;               /* weights/<name> */
         bool dynamic_velocity_reference{false};              /* contouring/dynamic_velocity_reference */
         int num_segments{5};                                 /* contouring/num_segments */
@@ -92,11 +94,40 @@ namespace MPCPlanner
     {
     public:
         Contouring(std::shared_ptr<Solver> solver, const ModuleConfig &cfg) : _solver(solver), _cfg(cfg) {}
-        /* (:28-48; findClosestPoint and the choice of the segment window are the caller's: module_data.path IS the window) */
-        void update(State &, const RealTimeData &data, ModuleData &module_data)
+        /* (:28-48) Two modes.  PATH MODE, data.reference_path non-empty (the whole path, mpc_planner_modules/reference_path.h):
+         * what the reference does -- findClosestPoint from _closest_segment, state.set("spline", closest_s), module_data.current_path_segment,
+         * and module_data.path = the window of num_segments segments from the segment found; data.left_bound / right_bound are then cubics of
+         * the WHOLE path (one per segment of data.reference_path; another size: not supplied) and are sliced with the window.  WINDOW MODE,
+         * data.reference_path empty: module_data.path IS the window and the bounds are aligned with it, the state is left alone. */
+        void update(State &state, const RealTimeData &data, ModuleData &module_data)
         {
+            _path_mode = !data.reference_path.empty();
+            if (_path_mode) {
+                ReferencePathSpline path;
+                path.segments = data.reference_path; path.length = data.reference_path_length;
+                if (data.left_bound.size() == data.reference_path.size() && data.right_bound.size() == data.reference_path.size()) {
+                    path.left_bound = data.left_bound; path.right_bound = data.right_bound;
+                }
+                double closest_s = 0.;
+                path.findClosestPoint(state.getPos(), _closest_segment, closest_s, _cfg.path_search_range);
+                state.set("spline", closest_s);                                 /* We need to initialize the spline state here (:42) */
+                module_data.current_path_segment = _closest_segment;
+                path.window(_closest_segment, _cfg.num_segments, module_data.path, &_left_window, &_right_window);
+            }
             _segments = module_data.path;
             if (_cfg.add_road_constraints) constructRoadConstraints(data, module_data);
+        }
+        /* (:126-157) a new path: the next update searches every segment.  (Fitting the spline to waypoints is not on this path: the cubics
+         * arrive fitted, in data.reference_path.) */
+        void onDataReceived(RealTimeData &, std::string &&data_name) { if (data_name == "reference_path") _closest_segment = -1; }
+        void reset() { _closest_segment = -1; }
+        /* (:167-175) */
+        bool isObjectiveReached(const State &state, const RealTimeData &data) const
+        {
+            if (data.reference_path.empty()) return false;
+            ReferencePathSpline path;
+            path.segments = data.reference_path; path.length = data.reference_path_length;
+            return path.reached(state.getPos());
         }
         void setParameters(const RealTimeData &, const ModuleData &, int k)
         {
@@ -119,7 +150,8 @@ namespace MPCPlanner
          * order, as modules.py::road_halfspaces / road_halfspaces_from_bounds and tmpc_road_halfspaces_kernel. ---- */
         void constructRoadConstraints(const RealTimeData &data, ModuleData &module_data)
         {
-            if (data.left_bound.empty() || data.right_bound.empty()) constructRoadConstraintsFromCenterline(data, module_data);
+            const std::vector<PathSegment> &left = _path_mode ? _left_window : data.left_bound, &right = _path_mode ? _right_window : data.right_bound;
+            if (left.empty() || right.empty()) constructRoadConstraintsFromCenterline(data, module_data);
             else constructRoadConstraintsFromBounds(data, module_data);
         }
         void constructRoadConstraintsFromCenterline(const RealTimeData &data, ModuleData &module_data)
@@ -149,10 +181,10 @@ namespace MPCPlanner
                 module_data.static_obstacles[k].clear();
                 const double cur_s = _solver->getEgoPrediction(k, "spline");
                 Vector2d Pl(0., 0.), Al(0., 0.), Pr(0., 0.), Ar(0., 0.);
-                evaluateSegments(data.left_bound, cur_s, Pl, Al);
+                evaluateSegments(_path_mode ? _left_window : data.left_bound, cur_s, Pl, Al);
                 const double bl = Al(0) * (Pl(0) + Al(0) * r) + Al(1) * (Pl(1) + Al(1) * r);
                 module_data.static_obstacles[k].emplace_back(Vector2d(-Al(0), -Al(1)), -bl);
-                evaluateSegments(data.right_bound, cur_s, Pr, Ar);
+                evaluateSegments(_path_mode ? _right_window : data.right_bound, cur_s, Pr, Ar);
                 const double br = Ar(0) * (Pr(0) - Ar(0) * r) + Ar(1) * (Pr(1) - Ar(1) * r);
                 module_data.static_obstacles[k].emplace_back(Ar, br);
             }
@@ -183,6 +215,9 @@ namespace MPCPlanner
         }
         ModuleConfig _cfg;
         std::vector<PathSegment> _segments;
+        std::vector<PathSegment> _left_window, _right_window;       /* path mode: the bound cubics of the window */
+        int _closest_segment{-1};
+        bool _path_mode{false};
     };
 
 #ifndef SOLVER_ROW_MODEL          /* (dims headers written before the Gaussian rows existed) */

@@ -1,0 +1,143 @@
+/*
+ * mpc_planner_modules/reference_path_batch.h -- the batched device twin of mpc_planner_modules/reference_path.h, next to
+ * mpc_planner/data_preparation_batch.h: the whole paths of several scenes (and their bound cubics) are uploaded ONCE; per tick track()
+ * enqueues tmpc_track_path -- closest point from the previous segment, the window of S segments, the bound window, the objective-reached flag
+ * -- and setParameters() enqueues tmpc_set_path_parameters, which writes the spline columns of the handle's current batch and, optionally,
+ * the `spline` entry of a device state buffer: what Contouring::update / setSplineParameters do per scene on the host (contouring.cpp:28-48,
+ * :94-124), bit for bit.  boundWindow() is then ready for tmpc_road_halfspaces (d_bound_segments).  For callers of the C-ABI
+ * (include/tmpc_hip.h) that keep a launch of many scenes on the device; needs the HIP runtime header (compile with -D__HIP_PLATFORM_AMD__
+ * and the ROCm include directory).  Everything is enqueued on the handle's stream; setPaths() and setParameters() wait for their own uploads
+ * (the staging memory is their own), not for the kernels.
+ */
+#ifndef MPC_REFERENCE_PATH_BATCH_HIP_H
+#define MPC_REFERENCE_PATH_BATCH_HIP_H
+
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include <hip/hip_runtime_api.h>
+
+#include "tmpc_hip.h"
+#include <mpc_planner_modules/reference_path.h>
+
+namespace MPCPlanner
+{
+    class BatchedPathTracking
+    {
+    public:
+        /* n_scenes paths of up to n_seg_max (<= 1024) segments each; S = the solver's window (tmpc_dims::S) */
+        BatchedPathTracking(tmpc_handle *handle, int n_scenes, int n_seg_max, int S, bool with_bounds)
+            : _h(handle), _Q(n_scenes), _R(n_seg_max), _S(S), _with_bounds(with_bounds)
+        {
+            const size_t Q = (size_t)_Q, R = (size_t)_R, W = (size_t)_S;
+            alloc(_d_path, Q * R * 9 * 8); alloc(_d_count, Q * sizeof(int)); alloc(_d_length, Q * 8); alloc(_d_segment, Q * sizeof(int));
+            alloc(_d_closest_s, Q * 8); alloc(_d_window, Q * W * 9 * 8); alloc(_d_reached, Q);
+            if (_with_bounds) { alloc(_d_bounds, Q * 2 * R * 8 * 8); alloc(_d_bound_window, Q * 2 * W * 8 * 8); }
+        }
+        ~BatchedPathTracking()
+        {
+            for (void *p : {_d_path, _d_count, _d_length, _d_segment, _d_closest_s, _d_window, _d_reached, _d_bounds, _d_bound_window, _d_scene_of}) if (p) (void)hipFree(p);
+        }
+        BatchedPathTracking(const BatchedPathTracking &) = delete;
+        BatchedPathTracking &operator=(const BatchedPathTracking &) = delete;
+
+        /* New paths for every scene (segments beyond n_seg_max are not seen; with_bounds: left_bound / right_bound one cubic per segment).
+         * Like Contouring::onDataReceived("reference_path") (:126-157): every scene's previous segment goes back to -1, the next track()
+         * searches every segment. */
+        void setPaths(const std::vector<ReferencePathSpline> &paths)
+        {
+            const size_t Q = (size_t)_Q, R = (size_t)_R;
+            if (paths.size() != Q) fail("setPaths: one path per scene");
+            std::vector<double> path(Q * R * 9, 0.), length(Q, 0.), bounds(_with_bounds ? Q * 2 * R * 8 : 0, 0.);
+            std::vector<int> count(Q), segment(Q, -1);
+            for (size_t q = 0; q < Q; q++) {
+                const ReferencePathSpline &p = paths[q];
+                count[q] = (int)(p.segments.size() < R ? p.segments.size() : R);
+                length[q] = p.length;
+                if (_with_bounds && (p.left_bound.size() < (size_t)count[q] || p.right_bound.size() < (size_t)count[q])) fail("setPaths: a bound cubic per segment");
+                for (size_t i = 0; i < (size_t)count[q]; i++) {
+                    put(&path[(q * R + i) * 9], p.segments[i]); path[(q * R + i) * 9 + 8] = p.segments[i].start;
+                    if (_with_bounds) { put(&bounds[((q * 2 + 0) * R + i) * 8], p.left_bound[i]); put(&bounds[((q * 2 + 1) * R + i) * 8], p.right_bound[i]); }
+                }
+            }
+            void *stream = this->stream();
+            copy(_d_path, path.data(), path.size() * 8, stream); copy(_d_count, count.data(), Q * sizeof(int), stream);
+            copy(_d_length, length.data(), Q * 8, stream); copy(_d_segment, segment.data(), Q * sizeof(int), stream);
+            if (_with_bounds) copy(_d_bounds, bounds.data(), bounds.size() * 8, stream);
+            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");   // the staging vectors end with this call
+        }
+        /* Contouring::reset() for every scene: the next track() searches every segment */
+        void reset()
+        {
+            const std::vector<int> segment((size_t)_Q, -1);
+            void *stream = this->stream();
+            copy(_d_segment, segment.data(), segment.size() * sizeof(int), stream);
+            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");
+        }
+
+        /* One tick of Contouring::update for every scene: d_pos f64 [n_scenes][pos_stride] on the device, x and y first (a state buffer as
+         * tmpc_prepare_obstacles or tmpc_warmstart read it can be passed as it is).  Enqueued; nothing is read back. */
+        void track(const void *d_pos, int pos_stride, int search_range = 2)
+        {
+            tmpc_path_options opt{};
+            opt.size = sizeof(opt); opt.search_range = search_range;
+            if (tmpc_track_path(_h, _Q, _R, _d_path, _d_count, _d_length, _d_bounds, d_pos, pos_stride, &opt, _d_segment, _d_closest_s, _d_window, _d_bound_window,
+                                _d_reached)) fail(tmpc_last_error(_h));
+        }
+
+        /* The spline columns of the handle's CURRENT batch (tmpc_set_batch* first): scene_of[b] = scene of batch entry b, outside [0, n_scenes):
+         * the entry is left alone.  d_state != nullptr (device, [B][nx], the layout tmpc_warmstart reads): its `spline` entry becomes the
+         * scene's closest_s -- before tmpc_warmstart(d_state) the solve starts from the fresh value, after it from the previous tick's, as in
+         * the reference (planner.cpp:81-96). */
+        void setParameters(const std::vector<int> &scene_of, void *d_state = nullptr)
+        {
+            void *stream = this->stream();
+            if (scene_of.size() > _n_scene_of) {
+                if (_d_scene_of) (void)hipFree(_d_scene_of);
+                alloc(_d_scene_of, scene_of.size() * sizeof(int)); _n_scene_of = scene_of.size();
+            }
+            copy(_d_scene_of, scene_of.data(), scene_of.size() * sizeof(int), stream);
+            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");   // (the caller's vector may end with this call)
+            if (tmpc_set_path_parameters(_h, _d_window, _d_scene_of, _Q, d_state ? _d_closest_s : nullptr, d_state)) fail(tmpc_last_error(_h));
+        }
+
+        /* device buffers, valid after track(): the window [n_scenes][S][9], the bound window [n_scenes][2][S][8] (what tmpc_road_halfspaces takes
+         * as d_bound_segments; nullptr without bounds), closest_s [n_scenes], the segment found (i32) and the reached flag (u8) per scene */
+        const void *window() const { return _d_window; }
+        const void *boundWindow() const { return _d_bound_window; }
+        const void *closestS() const { return _d_closest_s; }
+        const void *segments() const { return _d_segment; }
+        const void *reached() const { return _d_reached; }
+        /* ModuleData::current_path_segment and closest_s of every scene; synchronises the handle's stream */
+        void current(std::vector<int> &segment, std::vector<double> &closest_s) const
+        {
+            segment.assign((size_t)_Q, -1); closest_s.assign((size_t)_Q, 0.);
+            if (tmpc_synchronize(_h)) fail(tmpc_last_error(_h));
+            if (hipMemcpy(segment.data(), _d_segment, segment.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) fail("hipMemcpy");
+            if (hipMemcpy(closest_s.data(), _d_closest_s, closest_s.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) fail("hipMemcpy");
+        }
+
+    private:
+        static void fail(const char *what) { std::fprintf(stderr, "BatchedPathTracking: %s\n", what); std::exit(1); }
+        static void alloc(void *&p, size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) fail("hipMalloc"); }
+        static void copy(void *dst, const void *src, size_t bytes, void *stream)
+        {
+            if (bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) fail("hipMemcpyAsync");
+        }
+        static void put(double *o, const PathSegment &c) { o[0] = c.ax; o[1] = c.bx; o[2] = c.cx; o[3] = c.dx; o[4] = c.ay; o[5] = c.by; o[6] = c.cy; o[7] = c.dy; }
+        void *stream() const
+        {
+            void *s = nullptr;
+            if (tmpc_get_stream(_h, &s)) fail(tmpc_last_error(_h));
+            return s;
+        }
+        tmpc_handle *_h;
+        int _Q, _R, _S;
+        bool _with_bounds;
+        void *_d_path{nullptr}, *_d_count{nullptr}, *_d_length{nullptr}, *_d_segment{nullptr}, *_d_closest_s{nullptr}, *_d_window{nullptr}, *_d_reached{nullptr};
+        void *_d_bounds{nullptr}, *_d_bound_window{nullptr}, *_d_scene_of{nullptr};
+        size_t _n_scene_of{0};
+    };
+}
+#endif

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include <mpc_planner_solver/solver_interface.h>
+#include <mpc_planner_types/path_segment.h>
 
 namespace MPCPlanner
 {
@@ -75,9 +76,8 @@ namespace MPCPlanner
             : index(_index), position(_position), angle(_angle), radius(_radius), type(_type) {}
     };
 
-    /* One cubic segment of the contouring reference (contouring.cpp:94-124 reads these numbers out of RosTools::Spline2D, which
-     * is not in the reference tree): x(t) = ax t^3 + bx t^2 + cx t + dx, same for y, t = s - start. */
-    struct PathSegment { double ax, bx, cx, dx, ay, by, cy, dy, start; };
+    /* PathSegment, one cubic segment of the contouring reference: mpc_planner_types/path_segment.h (shared with the Solver-free
+     * mpc_planner_modules/reference_path.h) */
 
     /* What GuidanceConstraints reads from the (external) guidance_planner per trajectory (guidance_constraints.cpp:340-360,
      * 390-414): position / velocity of its spline at t = k dt, k = 0..N, the topology class and the selection flag. */

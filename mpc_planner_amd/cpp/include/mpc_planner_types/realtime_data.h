@@ -1,8 +1,10 @@
 /*
  * mpc_planner_types/realtime_data.h (HIP flavour) -- what the accelerated path reads of the per-tick sensor data; written
  * after mpc_planner_types/include/mpc_planner_types/realtime_data.h:16-51 (member names and reset() semantics kept so that module
- * code compiles unchanged; costmap, reference path and the past trajectory are not on this path and stay with the reference's own
- * header in a full tree).  The road bounds ARE on the path (Contouring::constructRoadConstraintsFromBounds, contouring.cpp:237-262): the
+ * code compiles unchanged; costmap and the past trajectory are not on this path and stay with the reference's own header in a full tree).
+ * The reference path is on it since Contouring::update tracks it (contouring.cpp:28-48): the reference keeps waypoints and fits a
+ * RosTools::Spline2D (absent); here `reference_path` holds the fitted cubics of the whole path (fitting is not built), empty = the caller
+ * supplies the window in ModuleData::path.  The road bounds ARE on the path (Contouring::constructRoadConstraintsFromBounds, contouring.cpp:237-262): the
  * reference keeps them as point lists and fits RosTools::Spline2D objects on the centreline's knot vector (:142-149); ros_tools is absent, so
  * here they are the fitted cubics themselves, one PathSegment per segment of ModuleData::path (same window, same knots).
  */
@@ -27,6 +29,8 @@ namespace MPCPlanner
         bool goal_received{false};
         double intrusion{0.};                                                 // feedback value published by the ROS wrappers
         std::vector<PathSegment> left_bound, right_bound;                     // Contouring's road constraints; aligned with ModuleData::path, empty = not supplied
+        std::vector<PathSegment> reference_path;                              // the WHOLE path (fitted cubics); non-empty: Contouring::update finds the closest point and
+        double reference_path_length{0.};                                     // the window itself, and the bounds above are aligned with THIS vector; the knot behind the last segment
 
         // Everything but the robot's disc model is per-tick data (reference :37-47).
         void reset()

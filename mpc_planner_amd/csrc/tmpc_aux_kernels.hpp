@@ -345,6 +345,164 @@ __global__ void tmpc_set_obstacle_parameters_kernel(Dims d, int B, double *param
     }
 }
 
+// ---- Contouring::update on a whole reference path (contouring.cpp:28-48, setSplineParameters :94-124) ---------------------------------------
+// RosTools::Spline2D::findClosestPoint is not in the reference tree: restated, assumptions in DESIGN.md U14.  No FMA contraction, the operation
+// order of modules.py::closest_point_on_segment / find_closest_point / path_window: every output is bit-equal to the host mirror.
+constexpr int PATH_MAX_SEGMENTS = 1024, PATH_COARSE = 8, PATH_BISECTIONS = 40;
+
+// point and derivative of one 2-D cubic c = (ax bx cx dx ay by cy dy) at t: the Horner forms of the road kernel's `frame`
+__device__ inline void path_cubic(const double *c, double t, double &x, double &y, double &dx, double &dy)
+{
+#pragma clang fp contract(off)
+    x = ((c[0] * t + c[1]) * t + c[2]) * t + c[3];
+    y = ((c[4] * t + c[5]) * t + c[6]) * t + c[7];
+    dx = (3.0 * c[0] * t + 2.0 * c[1]) * t + c[2];
+    dy = (3.0 * c[4] * t + 2.0 * c[5]) * t + c[6];
+}
+
+// closest point of the cubic on t in [0, L] to (px, py): D = |P(t) - p|^2, g = (P(t) - p).P'(t).  Nine coarse samples t_j = L (j / 8), the
+// bracket around the best (lowest j on ties), an end of the bracket if g does not change sign inside it, else exactly 40 bisections (no
+// data-dependent exit) and the bracket's midpoint; the coarse sample wins if its D is strictly smaller.
+__device__ inline void path_closest_on_segment(const double *cg, double L, double px, double py, double &D_out, double &t_out)
+{
+#pragma clang fp contract(off)
+    double c[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) c[i] = cg[i];
+    auto eval = [&](double t, double &g) {
+#pragma clang fp contract(off)
+        double x, y, dx, dy;
+        path_cubic(c, t, x, y, dx, dy);
+        const double ex = x - px, ey = y - py;
+        g = ex * dx + ey * dy;
+        return ex * ex + ey * ey;
+    };
+    double g;
+    int js = 0;
+    double Dj = eval(L * (0.0 / 8.0), g);
+    for (int j = 1; j <= PATH_COARSE; j++) {
+        const double Dc = eval(L * ((double)j / 8.0), g);
+        if (Dc < Dj) { js = j; Dj = Dc; }
+    }
+    double lo = L * ((double)(js > 0 ? js - 1 : 0) / 8.0), hi = L * ((double)(js < PATH_COARSE ? js + 1 : PATH_COARSE) / 8.0);
+    double tc;
+    eval(lo, g);
+    if (g >= 0.0) tc = lo;
+    else {
+        eval(hi, g);
+        if (g <= 0.0) tc = hi;
+        else {
+            for (int it = 0; it < PATH_BISECTIONS; it++) {
+                const double mid = 0.5 * (lo + hi);
+                eval(mid, g);
+                if (g > 0.0) hi = mid; else lo = mid;
+            }
+            tc = 0.5 * (lo + hi);
+        }
+    }
+    const double Dc = eval(tc, g);
+    if (Dj < Dc) { D_out = Dj; t_out = L * ((double)js / 8.0); }
+    else { D_out = Dc; t_out = tc; }
+}
+
+// one wave per scene q; lane l takes the candidate segments first + l, first + l + 64, ... (a local search has at most 63 candidates: one per
+// lane).  segment[q] < 0: every segment of the path is a candidate; otherwise [max(0, prev - R), min(n - 1, prev + R)], prev clamped into
+// [0, n - 1] (the reference's _closest_segment protocol, contouring.cpp:37, :155).  Winner: the smallest D, the lowest segment on ties -- a
+// 64-lane __shfl_xor argmin on the pair (D, segment) compared lexicographically, so the result does not depend on the lane order.  The
+// mirror's sequential scan starts from the first candidate and replaces on strict `<`: a NaN D never wins unless it is the first candidate's,
+// which then stays -- reproduced here by leaving NaN out of the reduction and letting a NaN first candidate (lane 0 holds it) take the result.
+// Then the lanes copy the window: slot w < S = segment winner + w as given, or, beyond the last segment, the straight continuation along the
+// end tangent (0, 0, x'(end), X(end), 0, 0, y'(end), Y(end)), start = length (U14-3); the bound cubics [n_scenes][2][n_seg_max][8] the same way
+// from their own last cubics into bound_window [n_scenes][2][S][8], the layout tmpc_road_halfspaces_kernel reads.  A scene with count <= 0
+// writes nothing.
+__global__ __launch_bounds__(64) void tmpc_track_path_kernel(int S, int n_seg_max, int R, const double *path, const int *count, const double *length,
+                                                             const double *bounds, const double *pos, int pos_stride, int *segment, double *closest_s,
+                                                             double *window, double *bound_window, uint8_t *reached)
+{
+#pragma clang fp contract(off)
+    const int q = blockIdx.x, lane = threadIdx.x;
+    int n = count[q];
+    n = n > n_seg_max ? n_seg_max : n;
+    if (n <= 0) return;
+    const double *pq = path + (size_t)q * n_seg_max * 9;
+    const double len = length[q];
+    const double px = pos[(size_t)q * pos_stride], py = pos[(size_t)q * pos_stride + 1];
+    int first = 0, last = n - 1;
+    int prev = segment[q];
+    if (prev >= 0) {
+        prev = prev > n - 1 ? n - 1 : prev;
+        first = prev - R > 0 ? prev - R : 0;
+        last = prev + R < n - 1 ? prev + R : n - 1;
+    }
+    double bD = 0.0, bt = 0.0, D_first = 0.0, t_first = 0.0;
+    int bi = -1;
+    for (int i = first + lane; i <= last; i += 64) {                     // ascending i per lane: strict '<' keeps the lowest index
+        const double *c = pq + (size_t)i * 9;
+        const double L = (i + 1 < n ? pq[(size_t)(i + 1) * 9 + 8] : len) - c[8];
+        double D, t;
+        path_closest_on_segment(c, L, px, py, D, t);
+        if (i == first) { D_first = D; t_first = t; }
+        if (D == D && (bi < 0 || D < bD)) { bD = D; bt = t; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double ov = __shfl_xor(bD, o, 64), ot = __shfl_xor(bt, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        const bool take = (oi >= 0) && (bi < 0 || ov < bD || (ov == bD && oi < bi));
+        if (take) { bD = ov; bt = ot; bi = oi; }
+    }
+    D_first = __shfl(D_first, 0, 64); t_first = __shfl(t_first, 0, 64);
+    if (D_first != D_first || bi < 0) { bi = first; bt = t_first; }
+    // the end of the path: its last cubic at t = L_last
+    const double L_last = len - pq[(size_t)(n - 1) * 9 + 8];
+    double ex, ey, edx, edy;
+    path_cubic(pq + (size_t)(n - 1) * 9, L_last, ex, ey, edx, edy);
+    if (lane == 0) {
+        segment[q] = bi;
+        closest_s[q] = pq[(size_t)bi * 9 + 8] + bt;
+        if (reached) { const double rx = ex - px, ry = ey - py; reached[q] = sqrt(rx * rx + ry * ry) < 1.0 ? 1 : 0; }     // isObjectiveReached, :167-175
+    }
+    for (int e = lane; e < S * 9; e += 64) {
+        const int w = e / 9, col = e - w * 9, i = bi + w;
+        double v;
+        if (i < n) v = pq[(size_t)i * 9 + col];
+        else v = col == 2 ? edx : col == 3 ? ex : col == 6 ? edy : col == 7 ? ey : col == 8 ? len : 0.0;
+        window[((size_t)q * S + w) * 9 + col] = v;
+    }
+    if (bounds && bound_window)
+        for (int side = 0; side < 2; side++) {
+            const double *bq = bounds + ((size_t)q * 2 + side) * n_seg_max * 8;
+            double bx, by, bdx, bdy;
+            path_cubic(bq + (size_t)(n - 1) * 8, L_last, bx, by, bdx, bdy);
+            for (int e = lane; e < S * 8; e += 64) {
+                const int w = e >> 3, col = e & 7, i = bi + w;
+                double v;
+                if (i < n) v = bq[(size_t)i * 8 + col];
+                else v = col == 2 ? bdx : col == 3 ? bx : col == 6 ? bdy : col == 7 ? by : 0.0;
+                bound_window[(((size_t)q * 2 + side) * S + w) * 8 + col] = v;
+            }
+        }
+}
+
+// ---- the spline columns of the current batch's parameter rows from the windows tmpc_track_path_kernel wrote (setSplineParameters, :94-124) ----
+// one thread per (trajectory, stage, window slot): the nine columns ip_spline(d, slot, 0..8) of stage k < N of entry b from window
+// [n_scenes][S][9] of scene scene_of[b]; an entry whose scene is outside [0, n_scenes) is left untouched.  With closest_s and state
+// [B][nx]: state[b][spline] = closest_s[scene] (state.set("spline", closest_s), :42).  Nothing else is written; both models' strides.
+__global__ void tmpc_set_path_parameters_kernel(Dims d, int B, double *params, const double *window, const int *scene_of, int n_scenes,
+                                                const double *closest_s, double *state)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = d.N, S = d.S;
+    if (e >= B * N * S) return;
+    const int w = e % S, k = (e / S) % N, b = e / (S * N);
+    const int sc = scene_of[b];
+    if (sc < 0 || sc >= n_scenes) return;
+    double *p = params + ((size_t)b * N + k) * d.npar;
+    const double *src = window + ((size_t)sc * S + w) * 9;
+#pragma unroll
+    for (int c = 0; c < 9; c++) p[ip_spline(d, w, c)] = src[c];
+    if (k == 0 && w == 0 && closest_s && state) state[(size_t)b * ext_nx(d) + (ZS - NU)] = closest_s[sc];
+}
+
 
 // ---- f-3: scenario -> polygon on device (SH-MPC, BASELINE config 5) ------------------------------------------------
 // The reference delegates this to the external scenario_module (scenario_constraints.cpp:47,76-79; source absent), so

@@ -1336,6 +1336,62 @@ int tmpc_set_obstacle_parameters(tmpc_handle *h, const void *d_obstacle_pos, con
     return TMPC_OK;
 }
 
+int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const void *d_path, const void *d_path_count, const void *d_path_length,
+                    const void *d_bounds, const void *d_pos, int32_t pos_stride, const tmpc_path_options *options, void *d_segment,
+                    void *d_closest_s, void *d_window, void *d_bound_window, void *d_reached)
+{
+#ifdef TMPC_GENERATED_STAGE
+    if (h) h->err = "tmpc_track_path: not available in a generated solver (its parameter layout is the module stack's)";
+    return TMPC_ERR_INVALID;
+#endif
+    if (!h) return TMPC_ERR_INVALID;
+    tmpc_path_options o{};                                            // NULL: the defaults (search_range 2)
+    o.size = sizeof(o); o.search_range = 2;
+    if (options) {
+        // like tmpc_obstacle_options: the caller's struct may be longer (a newer header) only with a zero tail; there is no shorter revision
+        if (options->size < sizeof(o)) { h->err = "tmpc_track_path: options->size is smaller than tmpc_path_options"; return TMPC_ERR_INVALID; }
+        const unsigned char *tail = reinterpret_cast<const unsigned char *>(options);
+        for (uint32_t i = sizeof(o); i < options->size; i++)
+            if (tail[i]) { h->err = "tmpc_track_path: options holds a non-zero field this library does not know"; return TMPC_ERR_INVALID; }
+        o = *options;
+    }
+    if (n_scenes <= 0) { h->err = "tmpc_track_path: n_scenes must be positive"; return TMPC_ERR_INVALID; }
+    if (n_seg_max < 1 || n_seg_max > tmpc::PATH_MAX_SEGMENTS) { h->err = "tmpc_track_path: 1 <= n_seg_max <= 1024"; return TMPC_ERR_INVALID; }
+    if (o.search_range < 0 || o.search_range > 31) { h->err = "tmpc_track_path: 0 <= search_range <= 31"; return TMPC_ERR_INVALID; }
+    if (pos_stride < 2) { h->err = "tmpc_track_path: pos_stride >= 2 (x and y first)"; return TMPC_ERR_INVALID; }
+    if (h->d.S <= 0) { h->err = "tmpc_track_path: the problem has no path segments (S = 0)"; return TMPC_ERR_INVALID; }
+    if (!d_path || !d_path_count || !d_path_length || !d_pos) { h->err = "tmpc_track_path: NULL input (d_path, d_path_count, d_path_length, d_pos)"; return TMPC_ERR_INVALID; }
+    if (!d_segment || !d_closest_s || !d_window) { h->err = "tmpc_track_path: NULL output (d_segment, d_closest_s, d_window)"; return TMPC_ERR_INVALID; }
+    if ((d_bounds == nullptr) != (d_bound_window == nullptr)) { h->err = "tmpc_track_path: d_bounds and d_bound_window go together (both or neither)"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_track_path_kernel, dim3((unsigned)n_scenes), dim3(64), 0, h->stream, h->d.S, n_seg_max, o.search_range,
+                       (const double *)d_path, (const int *)d_path_count, (const double *)d_path_length, (const double *)d_bounds, (const double *)d_pos,
+                       pos_stride, (int *)d_segment, (double *)d_closest_s, (double *)d_window, (double *)d_bound_window, (uint8_t *)d_reached);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
+int tmpc_set_path_parameters(tmpc_handle *h, const void *d_window, const void *d_scene_of, int32_t n_scenes, const void *d_closest_s, void *d_state)
+{
+#ifdef TMPC_GENERATED_STAGE
+    if (h) h->err = "tmpc_set_path_parameters: not available in a generated solver (its parameter layout is the module stack's)";
+    return TMPC_ERR_INVALID;
+#endif
+    if (!h) return TMPC_ERR_INVALID;
+    if (h->B <= 0 || !h->params) { h->err = "tmpc_set_path_parameters: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
+    if (h->d.S <= 0) { h->err = "tmpc_set_path_parameters: the problem has no path segments (S = 0)"; return TMPC_ERR_INVALID; }
+    if (!d_window || !d_scene_of || n_scenes <= 0) { h->err = "tmpc_set_path_parameters: bad argument (d_window, d_scene_of, n_scenes > 0)"; return TMPC_ERR_INVALID; }
+    if ((d_closest_s == nullptr) != (d_state == nullptr)) { h->err = "tmpc_set_path_parameters: d_closest_s and d_state go together (both or neither)"; return TMPC_ERR_INVALID; }
+    const int64_t n = (int64_t)h->B * h->d.N * h->d.S;
+    if (n > 0x7fffffff) { h->err = "tmpc_set_path_parameters: B x N x S too large"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_set_path_parameters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B,
+                       const_cast<double *>(h->params), (const double *)d_window, (const int *)d_scene_of, n_scenes, (const double *)d_closest_s,
+                       (double *)d_state);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
 int tmpc_scenario_halfspaces(tmpc_handle *h, const void *d_samples, int32_t n_pts, int32_t n_rows, const void *d_scene_of,
                              const void *d_state_x, double radius, double disc_offset)
 {

@@ -723,3 +723,140 @@ def prepare_obstacles(state, raw_pos, raw_radius, M, N, dt, raw_vel=None, raw_pr
     return dict(pos=np.asarray(obs["pos"], float), angle=np.asarray(obs["angle"], float), radius=np.asarray(obs["radius"], float),
                 major=np.where(live, major, 0.0), minor=np.where(live, minor, 0.0),
                 chi=np.where(gauss, -np.log(risk) / 0.5, 1.0), selected=selected, gaussian=gauss, shape=shape)
+
+
+# ---- Contouring::update on a whole reference path: closest point, segment window (contouring.cpp:28-48, :94-124) -------------------------
+# RosTools::Spline2D is not in the reference tree: the search is restated, its assumptions are DESIGN.md U14.  Host mirrors of
+# tmpc_track_path_kernel (csrc/tmpc_aux_kernels.hpp) and of mpc_planner_modules/reference_path.h, bit for bit: plain IEEE doubles, no
+# fused multiply-add, the operation order below.
+
+PATH_COARSE = 8          # coarse samples per segment: t_j = L (j / 8), j = 0 .. 8
+PATH_BISECTIONS = 40     # fixed: no data-dependent exit, every lane of a wave does the same work
+
+
+def _path_cubic(c, t):
+    """Point and derivative of one 2-D cubic c = (ax bx cx dx ay by cy dy) at t, the Horner forms of _road_segment_eval."""
+    px = ((c[0] * t + c[1]) * t + c[2]) * t + c[3]
+    py = ((c[4] * t + c[5]) * t + c[6]) * t + c[7]
+    dx = (3.0 * c[0] * t + 2.0 * c[1]) * t + c[2]
+    dy = (3.0 * c[4] * t + 2.0 * c[5]) * t + c[6]
+    return px, py, dx, dy
+
+
+def _path_segment_length(path, length, i):
+    """L_i = start_{i+1} - start_i; the last segment ends at `length`, the knot behind it."""
+    return (float(path[i + 1][8]) if i + 1 < len(path) else float(length)) - float(path[i][8])
+
+
+def closest_point_on_segment(c, L, px, py):
+    """(D, t): the closest point of the cubic c on t in [0, L] to (px, py), D = |P(t) - p|^2, g(t) = (P(t) - p).P'(t).  Nine coarse samples
+    t_j = L (j / 8); j* = argmin D(t_j), lowest j on ties; bracket [t_{max(j*-1, 0)}, t_{min(j*+1, 8)}]; g(lo) >= 0: t = lo, else g(hi) <= 0:
+    t = hi, else exactly 40 bisections on the sign of g and the bracket's midpoint; the coarse sample wins if its D is strictly smaller."""
+    c = [float(v) for v in c]; L = float(L); px = float(px); py = float(py)
+
+    def D_g(t):
+        x, y, dx, dy = _path_cubic(c, t)
+        ex, ey = x - px, y - py
+        return ex * ex + ey * ey, ex * dx + ey * dy
+
+    tj = [L * (j / 8.0) for j in range(PATH_COARSE + 1)]
+    js, Dj = 0, D_g(tj[0])[0]
+    for j in range(1, PATH_COARSE + 1):
+        Dc = D_g(tj[j])[0]
+        if Dc < Dj:
+            js, Dj = j, Dc
+    lo, hi = tj[max(js - 1, 0)], tj[min(js + 1, PATH_COARSE)]
+    if D_g(lo)[1] >= 0.0:
+        tc = lo
+    elif D_g(hi)[1] <= 0.0:
+        tc = hi
+    else:
+        for _ in range(PATH_BISECTIONS):
+            mid = 0.5 * (lo + hi)
+            if D_g(mid)[1] > 0.0:
+                hi = mid
+            else:
+                lo = mid
+        tc = 0.5 * (lo + hi)
+    Dc = D_g(tc)[0]
+    if Dj < Dc:
+        return Dj, tj[js]
+    return Dc, tc
+
+
+def find_closest_point(path, length, pos, segment=-1, search_range=2):
+    """RosTools::Spline2D::findClosestPoint as Contouring::update uses it (contouring.cpp:37; DESIGN.md U14-1).  path [n][9] =
+    (ax bx cx dx ay by cy dy start), `length` the knot behind the last segment.  segment < 0 (a new path, a reset): every segment is a
+    candidate; otherwise [max(0, prev - R), min(n - 1, prev + R)] with prev = segment clamped into [0, n - 1] and R = search_range.  The
+    comparison starts from the first candidate and replaces on strict `<`: the lowest segment index wins a tie (the convention of U13), and
+    a NaN / inf position yields the first candidate, never an index out of range.  Returns (segment, s = start_segment + t)."""
+    path = np.asarray(path, float)
+    n = len(path)
+    assert n > 0 and 0 <= int(search_range) <= 31
+    if int(segment) < 0:
+        first, last = 0, n - 1
+    else:
+        prev = min(max(int(segment), 0), n - 1)
+        first, last = max(0, prev - int(search_range)), min(n - 1, prev + int(search_range))
+    best_i, best_D, best_t = first, None, 0.0
+    for i in range(first, last + 1):
+        D, t = closest_point_on_segment(path[i, :8], _path_segment_length(path, length, i), pos[0], pos[1])
+        if best_D is None or D < best_D:
+            best_i, best_D, best_t = i, D, t
+    return best_i, float(path[best_i, 8]) + best_t
+
+
+def _path_end(coef, L_last):
+    """Point and tangent at the end of a path: its last cubic at t = L_last."""
+    return _path_cubic([float(v) for v in coef[-1][:8]], float(L_last))
+
+
+def path_window(path, length, segment, S, left=None, right=None):
+    """The S segments Contouring::setSplineParameters writes from `segment` on (contouring.cpp:94-124; DESIGN.md U14-2, U14-3): slot w holds
+    segment + w as given; a slot beyond the last segment continues the path STRAIGHT ALONG ITS END TANGENT -- (0, 0, x'(end), X(end), 0, 0,
+    y'(end), Y(end)), start = length, from the last cubic at t = L_last -- so that |path'| never vanishes.  left, right [n][8]: the bound
+    cubics on the same knots, windowed and padded the same way from their own last cubics.
+    Returns window [S][9], or (window, left_window [S][8], right_window [S][8]) with bounds."""
+    path = np.asarray(path, float)
+    n = len(path)
+    L_last = _path_segment_length(path, length, n - 1)
+
+    def pad(coef):
+        x, y, dx, dy = _path_end(coef, L_last)
+        return [0.0, 0.0, dx, x, 0.0, 0.0, dy, y]
+
+    window = np.zeros((S, 9))
+    sides = [None if b is None else np.asarray(b, float) for b in (left, right)]
+    side_windows = [None if b is None else np.zeros((S, 8)) for b in sides]
+    for w in range(S):
+        i = int(segment) + w
+        if i < n:
+            window[w] = path[i]
+        else:
+            window[w, :8] = pad(path); window[w, 8] = float(length)
+        for b, bw in zip(sides, side_windows):
+            if b is not None:
+                bw[w] = b[i, :8] if i < n else pad(b)
+    if left is None and right is None:
+        return window
+    return window, side_windows[0], side_windows[1]
+
+
+def path_objective_reached(path, length, pos):
+    """Contouring::isObjectiveReached (contouring.cpp:167-175): |p - P(length)| < 1.0."""
+    path = np.asarray(path, float)
+    x, y, _, _ = _path_end(path, _path_segment_length(path, length, len(path) - 1))
+    ex, ey = x - float(pos[0]), y - float(pos[1])
+    return bool(np.sqrt(ex * ex + ey * ey) < 1.0)
+
+
+def track_path(path, length, pos, S, segment=-1, search_range=2, left=None, right=None):
+    """One tick of Contouring::update on a whole path, for one scene (host mirror of tmpc_track_path): find_closest_point, path_window from
+    the segment found, the objective-reached flag.  Returns dict(segment, s, window [S][9], reached, and left / right [S][8] with bounds)."""
+    seg, s = find_closest_point(path, length, pos, segment, search_range)
+    out = dict(segment=seg, s=s, reached=path_objective_reached(path, length, pos))
+    if left is None and right is None:
+        out["window"] = path_window(path, length, seg, S)
+    else:
+        out["window"], out["left"], out["right"] = path_window(path, length, seg, S, left, right)
+    return out

@@ -368,6 +368,33 @@ def add_road_constraints(sc, width, two_way=False, radius=ROBOT_RADIUS, left=Non
     return out
 
 
+def with_long_path(sc, rng, n_segments=12, seg_len=2.0, shift=0.0, search_range=2):
+    """A make_scene() scene on a LONG reference path, of which the parameter rows see a window (Contouring::update on a whole path,
+    contouring.cpp:28-48): reference_path_segments(rng, S=n_segments, seg_len=seg_len), moved so that the robot (at the origin) stands on it
+    at path parameter `shift`; the closest point from a reset (modules.find_closest_point), the window of sc["S"] segments from the segment
+    found (modules.path_window) written by modules.contouring_set_parameters into every entry's rows, and state.set("spline", closest_s):
+    the spline entry of xinit is closest_s and the spline column of the warm start is advanced by it.  Every other column is copied.
+    Returns a new dict (make_scene's output is left as it is) with path [n][9], path_length, path_segment, path_s, segments = the window,
+    params, xinit, x0."""
+    path = reference_path_segments(rng, S=n_segments, seg_len=seg_len)
+    length = float(seg_len * n_segments)
+    if shift:
+        x, y, _, _ = md._road_segment_eval(path[:, :8], path[:, 8], float(shift))
+        path[:, 3] -= x; path[:, 7] -= y
+    state = sc["xinit"][0]
+    seg, s = md.find_closest_point(path, length, state[:2], -1, search_range)
+    window = md.path_window(path, length, seg, sc["S"])
+    params = sc["params"].copy()
+    for b in range(len(params)):
+        md.contouring_set_parameters(sc["pm"], params[b], WEIGHTS, window)
+    xinit = sc["xinit"].copy(); x0 = sc["x0"].copy()
+    xinit[:, 4] = s
+    x0[:, :, md.IDX["spline"]] += s
+    out = dict(sc)
+    out.update(path=path, path_length=length, path_segment=seg, path_s=s, segments=window, params=params, xinit=xinit, x0=x0)
+    return out
+
+
 def _make_scene_kw(args):
     idx, kw = args
     return make_scene(idx, **kw)

@@ -48,13 +48,18 @@ EXPORTS = ["tmpc_default_dims", "tmpc_default_dims_ex", "tmpc_create", "tmpc_des
            "tmpc_reset_multipliers", "tmpc_get_stream", "tmpc_kernel_info", "tmpc_set_slots", "tmpc_set_param_sharing", "tmpc_copy_state", "tmpc_scenario_empty_stages", "tmpc_sample_scenarios",
            "tmpc_scenario_discard", "tmpc_scenario_discarded", "tmpc_linearize_topology_ex", "tmpc_clear_slot", "tmpc_gather_best",
            "tmpc_create_v2", "tmpc_set_param_sharing_ex", "tmpc_latency_mode_capacity", "tmpc_has_lane_kernels", "tmpc_debug_lds_passes", "tmpc_debug_poison_lds", "tmpc_has_lab_switches",
-           "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters"]
+           "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters", "tmpc_track_path", "tmpc_set_path_parameters"]
 
 
 class TmpcObstacleOptions(C.Structure):
     """tmpc_obstacle_options (include/tmpc_hip.h)."""
     _fields_ = [("size", C.c_uint32), ("probabilistic", C.c_int32), ("propagate_passes", C.c_int32), ("reserved", C.c_int32),
                 ("noise", C.c_double), ("max_obstacle_distance", C.c_double)]
+
+
+class TmpcPathOptions(C.Structure):
+    """tmpc_path_options (include/tmpc_hip.h)."""
+    _fields_ = [("size", C.c_uint32), ("search_range", C.c_int32)]
 
 
 class TmpcError(RuntimeError):
@@ -125,6 +130,9 @@ def load_library(path=None):
     if hasattr(lib, "tmpc_prepare_obstacles"):
         lib.tmpc_prepare_obstacles.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 6 + [C.POINTER(TmpcObstacleOptions)] + [vp] * 5
         lib.tmpc_set_obstacle_parameters.argtypes = [vp] + [vp] * 6 + [C.c_double] * 5
+    if hasattr(lib, "tmpc_track_path"):
+        lib.tmpc_track_path.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 5 + [C.c_int32, C.POINTER(TmpcPathOptions)] + [vp] * 5
+        lib.tmpc_set_path_parameters.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
     if hasattr(lib, "tmpc_scenario_discarded"):        # (absent from reference builds of earlier rounds used in A/B runs)
         lib.tmpc_scenario_discarded.argtypes = [vp, vp]
     if hasattr(lib, "tmpc_copy_state"):        # (absent from reference builds of earlier rounds used in A/B runs)
@@ -440,6 +448,33 @@ class BatchedSolver:
                                                           vp(d_obstacle_gaussian), vp(d_scene_of), vp(d_state), float(robot_radius),
                                                           float(disc_offset), float(risk), chi, float(obstacle_radius)),
                     "tmpc_set_obstacle_parameters")
+
+    def track_path(self, n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_pos, pos_stride, d_segment, d_closest_s, d_window,
+                   d_bounds=None, d_bound_window=None, d_reached=None, search_range=2):
+        """Contouring::update on whole reference paths (tmpc_track_path; raw device pointers): per scene the closest point of d_path
+        [n_scenes][n_seg_max][9] (d_path_count segments, parameter length d_path_length) to d_pos [n_scenes][pos_stride] -- searched over
+        every segment where d_segment is negative, else search_range segments either side of it -- into d_segment (in / out) and d_closest_s,
+        the window of S segments from there into d_window [n_scenes][S][9] (padded straight along the end tangent), with d_bounds
+        [n_scenes][2][n_seg_max][8] the bound cubics of the window into d_bound_window [n_scenes][2][S][8] (what road_halfspaces takes), and
+        the objective-reached flag into d_reached (u8).  Equal bit for bit to modules.track_path.  Needs no batch.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_track_path"):
+            raise TmpcError("this library has no tmpc_track_path (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        opt = TmpcPathOptions(C.sizeof(TmpcPathOptions), int(search_range))
+        self._check(self.lib.tmpc_track_path(self._h, int(n_scenes), int(n_seg_max), vp(d_path), vp(d_path_count), vp(d_path_length), vp(d_bounds),
+                                             vp(d_pos), int(pos_stride), C.byref(opt), vp(d_segment), vp(d_closest_s), vp(d_window),
+                                             vp(d_bound_window), vp(d_reached)), "tmpc_track_path")
+
+    def set_path_parameters(self, d_window, d_scene_of, n_scenes, d_closest_s=None, d_state=None):
+        """The spline columns of the current batch's parameter rows, in place, from track_path's d_window (tmpc_set_path_parameters; raw
+        device pointers); entries whose d_scene_of is outside [0, n_scenes) are left untouched.  With d_closest_s and d_state [B][nx]: the
+        spline entry of each named entry's state becomes its scene's closest_s -- before warmstart(d_state) the solve starts from the fresh
+        value, after it from the previous tick's, as in the reference (planner.cpp:81-96).  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_set_path_parameters"):
+            raise TmpcError("this library has no tmpc_set_path_parameters (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        self._check(self.lib.tmpc_set_path_parameters(self._h, vp(d_window), vp(d_scene_of), int(n_scenes), vp(d_closest_s), vp(d_state)),
+                    "tmpc_set_path_parameters")
 
     def scenario_halfspaces(self, d_samples, n_pts, n_rows, d_scene_of, d_state_x, radius, disc_offset=0.0):
         """Device scenario -> halfspace reduction of SH-MPC (raw device pointers; samples [n_scenes][N][n_pts][2]);

@@ -4,7 +4,10 @@ to get their durations.  The road kernel works per (scene, stage): it is launche
 Obstacle preparation (tmpc_prepare_obstacles, tmpc_set_obstacle_parameters) runs at bench.py's default launch, 512 scenes x 64 trajectories, with
 `--slots R` raw-obstacle slots per scene, all of them filled (default 64; `--slots 1024`, the cap, runs the obstacle kernels alone so that a
 profile of that run holds the R = 1024 durations only).  Besides the profile, one JSON line per obstacle kernel: the mean of 50 back-to-back
-launches between two HIP events on the handle's stream (launch gaps included: an upper bound of the kernel time)."""
+launches between two HIP events on the handle's stream (launch gaps included: an upper bound of the kernel time).
+`--path local|global [--segments n]`: the reference-path kernels alone (tmpc_track_path, tmpc_set_path_parameters) at the same launch, 512 paths of
+n segments (default 64; 1024 is the cap) of 2 m, searched 2 segments either side of the previous one (local) or over every segment (global: the
+previous segment is put back to -1 before every launch, a 512-int copy that the event times include and the profile lists separately)."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -48,6 +51,52 @@ def obstacle_kernels(R, n_scenes=512, traj=64, M=8, N=20):
     so.close()
 
 
+def path_kernels(mode, n_seg, n_scenes=512, traj=64, N=20, S=5):
+    rng = np.random.default_rng(11)
+    B = n_scenes * traj
+    so = solver.BatchedSolver(solver.default_dims(), B_max=B)
+    f64 = dict(dtype=torch.float64, device=dev)
+    xinit = torch.zeros((B, 5), **f64); x0 = torch.zeros((B, N + 1, 7), **f64); params = torch.zeros((B, N, so.dims.npar), **f64)
+    so.set_batch_device(B, xinit.data_ptr(), x0.data_ptr(), params.data_ptr())
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    base = np.stack([scenes.reference_path_segments(np.random.default_rng(s_), S=n_seg, seg_len=2.0) for s_ in range(16)])
+    paths = up(np.tile(base, (n_scenes // 16, 1, 1))); cnt = up(np.full(n_scenes, n_seg, np.int32)); length = up(np.full(n_scenes, 2.0 * n_seg))
+    bounds = up(np.tile(np.stack([base[:, :, :8], base[:, :, :8]], 1), (n_scenes // 16, 1, 1, 1)))
+    x = rng.uniform(0.0, 2.0 * n_seg, n_scenes)
+    state = up(np.stack([x, rng.uniform(-1.0, 1.0, n_scenes), np.zeros(n_scenes), np.full(n_scenes, 1.2)], 1))
+    seg0 = up(np.full(n_scenes, -1, np.int32) if mode == "global" else np.clip((x // 2.0).astype(np.int32) - 1, 0, n_seg - 1))
+    seg = seg0.clone(); cs = torch.zeros(n_scenes, **f64); win = torch.zeros((n_scenes, S, 9), **f64); bw = torch.zeros((n_scenes, 2, S, 8), **f64)
+    reached = torch.zeros(n_scenes, dtype=torch.uint8, device=dev)
+    scene_of = up(np.repeat(np.arange(n_scenes, dtype=np.int32), traj)); st = torch.zeros((B, 5), **f64)
+    hs = torch.cuda.ExternalStream(so.stream_ptr(), device=dev)
+
+    def track():
+        with torch.cuda.stream(hs):
+            seg.copy_(seg0)                                            # (tmpc_track_path leaves the segment it found: the next launch would be a local search)
+        so.track_path(n_scenes, n_seg, paths.data_ptr(), cnt.data_ptr(), length.data_ptr(), state.data_ptr(), 4, seg.data_ptr(), cs.data_ptr(), win.data_ptr(),
+                      d_bounds=bounds.data_ptr(), d_bound_window=bw.data_ptr(), d_reached=reached.data_ptr(), search_range=2)
+    write = lambda: so.set_path_parameters(win.data_ptr(), scene_of.data_ptr(), n_scenes, d_closest_s=cs.data_ptr(), d_state=st.data_ptr())
+    for name, call in (("tmpc_track_path_kernel", track), ("tmpc_set_path_parameters_kernel", write)):
+        for _ in range(10):
+            call()
+        so.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(hs):
+            e0.record()
+        for _ in range(50):
+            call()
+        with torch.cuda.stream(hs):
+            e1.record()
+        so.synchronize()
+        print(json.dumps(dict(kernel=name, n_scenes=n_scenes, trajectories=B, segments=n_seg, search=mode, S=S, N=N,
+                              us_per_launch_events=e0.elapsed_time(e1) * 1e3 / 50)), flush=True)
+    so.close()
+
+
+if "--path" in sys.argv:
+    path_kernels(sys.argv[sys.argv.index("--path") + 1], int(sys.argv[sys.argv.index("--segments") + 1]) if "--segments" in sys.argv else 64)
+    print("done")
+    sys.exit(0)
 if "--slots" in sys.argv:
     obstacle_kernels(slots)
     print("done")
