@@ -455,6 +455,40 @@ int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const v
 int tmpc_set_path_parameters(tmpc_handle *h, const void *d_window, const void *d_scene_of, int32_t n_scenes, const void *d_closest_s,
                              void *d_state);
 
+/* ---- reference paths fitted on device: waypoints -> the cubic segments tmpc_track_path reads.  What Contouring::onDataReceived
+ * (mpc_planner_modules/src/contouring.cpp:126-157) and PathReferenceVelocity::onDataReceived (path_reference_velocity.cpp:28-40) do when a
+ * path arrives: the centreline through the waypoints, the two bound curves and the velocity profile on the CENTRELINE's knots, road/width
+ * from the bounds' first waypoints.  RosTools::Spline2D and tk::spline are not in the reference tree: the natural cubic spline (second
+ * derivative zero at both ends) is restated, DESIGN.md U15.  Needs no batch, uses the stream of the handle only; also available in a
+ * generated solver (no parameter layout is involved).  Stream-ordered, no allocation, no synchronisation.  Inputs (device):
+ *   d_xy        f64 [n_scenes][n_pts_max][2]   waypoints;  2 <= n_pts_max <= 1025
+ *   d_count     i32 [n_scenes]                 waypoints of the scene, clipped to [0, n_pts_max]
+ *   d_s         f64 [n_scenes][n_pts_max]      or NULL.  Given: the knots t_i = s_i as supplied (not shifted).  NULL: chord lengths, t_0 = 0,
+ *                                              t_{i+1} = t_i + sqrt(dx dx + dy dy), accumulated strictly left to right
+ *   d_left_xy, d_right_xy                      as d_xy, or NULL: the bounds' waypoints, one per waypoint of the centreline (all of d_left_xy,
+ *                                              d_right_xy, d_bounds or none of them)
+ *   d_v         f64 [n_scenes][n_pts_max]      or NULL: the velocity at each waypoint (with d_velocity, both or neither)
+ * Outputs (device, caller-owned), in exactly the layouts tmpc_track_path reads, rows n_seg_max apart, n_pts_max - 1 <= n_seg_max <= 1024, so
+ * that one allocation serves both calls:
+ *   d_path        f64 [n_scenes][n_seg_max][9]     (ax bx cx dx ay by cy dy start), x(t) = ((ax t + bx) t + cx) t + dx on t = s - start
+ *   d_path_count  i32 [n_scenes]                   count - 1 segments
+ *   d_path_length f64 [n_scenes]                   the last knot
+ *   d_bounds      f64 [n_scenes][2][n_seg_max][8]  or NULL: left, right
+ *   d_velocity    f64 [n_scenes][n_seg_max][4]     or NULL: (a b c d) of v(s)
+ *   d_road_width  f64 [n_scenes]                   or NULL: sqrt(ex ex + ey ey) between the bounds' first waypoints (contouring.cpp:152); written
+ *                                                  with bounds only
+ *   d_status      u8  [n_scenes]                   or NULL: 0 fitted, 1 invalid
+ * INVALID: fewer than 2 waypoints, or a knot spacing h_i = t_{i+1} - t_i for which h_i > 0 && h_i < inf is false (a duplicate waypoint, a
+ * non-increasing s, NaN; tk::spline asserts there).  An invalid scene gets d_path_count = 0 and d_status = 1 and NOTHING else of it is
+ * written; tmpc_track_path ignores a path with count <= 0.  Coordinates are not checked otherwise.  Rows at or beyond a scene's segment count
+ * are not touched.  Equal bit for bit to mpc_planner_amd.modules.fit_path (no FMA contraction, same operation order).  One wave per scene:
+ * the Thomas recurrence is sequential, one lane per curve (at most 7: x, y, four bound curves, v); everything else uses all lanes.
+ * TMPC_ERR_INVALID, before any launch: a NULL required pointer (d_xy, d_count, d_path, d_path_count, d_path_length), a partial group
+ * (d_left_xy / d_right_xy / d_bounds; d_v / d_velocity), n_scenes <= 0, n_pts_max outside [2, 1025], n_seg_max outside [n_pts_max - 1, 1024]. */
+int tmpc_fit_path(tmpc_handle *h, int32_t n_scenes, int32_t n_pts_max, int32_t n_seg_max, const void *d_xy, const void *d_count, const void *d_s,
+                  const void *d_left_xy, const void *d_right_xy, const void *d_v, void *d_path, void *d_path_count, void *d_path_length,
+                  void *d_bounds, void *d_velocity, void *d_road_width, void *d_status);
+
 /* ---- scenario -> polygon construction of SH-MPC on device.  Replaces what the reference gets from the
  * external scenario_module (scenario_constraints.cpp:47 update, :76-79 setParameters; source absent -> restated, see
  * mpc_planner_amd/modules.py::scenario_halfspaces): for every trajectory b and stage k >= 1, each of the n_pts sampled

@@ -11,7 +11,7 @@
  *
  * Same class and method names, same member semantics; what the reference takes from packages that are not in its tree
  * is an explicit input here: CONFIG[...] (mpc_planner_util, yaml-cpp) -> ModuleConfig; guidance_planner::GlobalGuidance ->
- * std::vector<GuidanceTrajectory>; RosTools::Spline2D -> fitted cubic segments (RealTimeData::reference_path = the whole path, reference_path.h; ModuleData::path = the window); scenario_module's sampler / polygon
+ * std::vector<GuidanceTrajectory>; RosTools::Spline2D -> cubic segments, fitted from RealTimeData::reference_path_points by reference_path.h or handed in fitted (RealTimeData::reference_path = the whole path; ModuleData::path = the window); scenario_module's sampler / polygon
  * construction -> halfspaces handed in per scenario solver.  The OpenMP loop over local planners becomes: prepare every planner's
  * parameters on the host (same statements, same order), ONE Solver::solveBatch launch, then the reference's bookkeeping.
  * Header-only: everything is small and is compiled against the generated setSolverParameter* functions.
@@ -117,10 +117,30 @@ namespace MPCPlanner
             _segments = module_data.path;
             if (_cfg.add_road_constraints) constructRoadConstraints(data, module_data);
         }
-        /* (:126-157) a new path: the next update searches every segment.  (Fitting the spline to waypoints is not on this path: the cubics
-         * arrive fitted, in data.reference_path.) */
-        void onDataReceived(RealTimeData &, std::string &&data_name) { if (data_name == "reference_path") _closest_segment = -1; }
+        /* (:126-157) a new path: the next update searches every segment.  With waypoints in data.reference_path_points the path is fitted here
+         * (ReferencePathSpline::fit; on reference_path_points.s if given, else on chord lengths) into data.reference_path and
+         * reference_path_length; with road constraints and both bounds' waypoints the bound curves are fitted on the centreline's knots into
+         * data.left_bound / right_bound and road/width becomes the distance between their first waypoints (:138-153).  An invalid path
+         * (fewer than two points, a repeated waypoint) leaves data.reference_path empty.  Without waypoints the cubics arrive fitted, in
+         * data.reference_path, and data is left as it is. */
+        void onDataReceived(RealTimeData &data, std::string &&data_name)
+        {
+            if (data_name != "reference_path") return;
+            if (!data.reference_path_points.empty()) {
+                ReferencePathSpline path;
+                path.fit(data.reference_path_points.x, data.reference_path_points.y, data.reference_path_points.s);
+                data.reference_path = path.segments; data.reference_path_length = path.length;
+                if (_cfg.add_road_constraints && !data.left_bound_points.empty() && !data.right_bound_points.empty()) {
+                    double width = _cfg.road_width;
+                    if (path.fitBounds(data.left_bound_points.x, data.left_bound_points.y, data.right_bound_points.x, data.right_bound_points.y, &width))
+                        _cfg.road_width = width;                                /* Update the road width (:152) */
+                    data.left_bound = path.left_bound; data.right_bound = path.right_bound;
+                }
+            }
+            _closest_segment = -1;
+        }
         void reset() { _closest_segment = -1; }
+        double roadWidth() const { return _cfg.road_width; }            /* road/width as this module reads it: the configured value, or what onDataReceived set (:152) */
         /* (:167-175) */
         bool isObjectiveReached(const State &state, const RealTimeData &data) const
         {

@@ -1,6 +1,7 @@
 /*
  * mpc_planner_modules/reference_path_batch.h -- the batched device twin of mpc_planner_modules/reference_path.h, next to
- * mpc_planner/data_preparation_batch.h: the whole paths of several scenes (and their bound cubics) are uploaded ONCE; per tick track()
+ * mpc_planner/data_preparation_batch.h: the whole paths of several scenes (and their bound cubics) are uploaded ONCE -- fitted cubics with
+ * setPaths(), or raw waypoints with setWaypoints(), which tmpc_fit_path turns into the cubics on the device --; per tick track()
  * enqueues tmpc_track_path -- closest point from the previous segment, the window of S segments, the bound window, the objective-reached flag
  * -- and setParameters() enqueues tmpc_set_path_parameters, which writes the spline columns of the handle's current batch and, optionally,
  * the `spline` entry of a device state buffer: what Contouring::update / setSplineParameters do per scene on the host (contouring.cpp:28-48,
@@ -37,7 +38,7 @@ namespace MPCPlanner
         }
         ~BatchedPathTracking()
         {
-            for (void *p : {_d_path, _d_count, _d_length, _d_segment, _d_closest_s, _d_window, _d_reached, _d_bounds, _d_bound_window, _d_scene_of}) if (p) (void)hipFree(p);
+            for (void *p : {_d_path, _d_count, _d_length, _d_segment, _d_closest_s, _d_window, _d_reached, _d_bounds, _d_bound_window, _d_scene_of, _d_waypoints, _d_status, _d_road_width}) if (p) (void)hipFree(p);
         }
         BatchedPathTracking(const BatchedPathTracking &) = delete;
         BatchedPathTracking &operator=(const BatchedPathTracking &) = delete;
@@ -67,6 +68,61 @@ namespace MPCPlanner
             if (_with_bounds) copy(_d_bounds, bounds.data(), bounds.size() * 8, stream);
             if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");   // the staging vectors end with this call
         }
+        /* The alternative to setPaths(): raw waypoints for every scene, fitted ON THE DEVICE (tmpc_fit_path) into the twin's own
+         * path / count / length / bound buffers -- bit for bit what ReferencePathSpline::fit / fitBounds give on the host.  One upload (the
+         * waypoints of all scenes, their bounds, their s and the counts in one staging block), one kernel.  Waypoints beyond n_seg_max + 1
+         * are not seen.  Knots: the paths' s if EVERY path carries one, chord lengths if none does.  with_bounds: left / right hold one
+         * Boundary per scene with the centreline's point count.  An invalid scene (fewer than two waypoints, a repeated waypoint) gets
+         * count 0: track() leaves it alone; status() tells.  Every scene's previous segment goes back to -1. */
+        void setWaypoints(const std::vector<ReferencePath> &paths, const std::vector<Boundary> *left = nullptr, const std::vector<Boundary> *right = nullptr)
+        {
+            const size_t Q = (size_t)_Q, P = (size_t)_R + 1;
+            if (paths.size() != Q) fail("setWaypoints: one path per scene");
+            if (_with_bounds && (!left || !right || left->size() != Q || right->size() != Q)) fail("setWaypoints: a left and a right bound per scene");
+            size_t with_s = 0;
+            for (const ReferencePath &p : paths) with_s += p.hasDistance() ? 1 : 0;
+            if (with_s != 0 && with_s != Q) fail("setWaypoints: s for every path or for none");
+            // one staging block: xy [Q][P][2], s [Q][P], left [Q][P][2], right [Q][P][2] (doubles), then count and segment [Q] each (ints)
+            const size_t o_xy = 0, o_s = o_xy + Q * P * 2, o_left = o_s + Q * P, o_right = o_left + Q * P * 2, n_dbl = o_right + Q * P * 2;
+            const size_t bytes = n_dbl * 8 + 2 * Q * sizeof(int);
+            std::vector<double> stage(n_dbl + (2 * Q * sizeof(int) + 7) / 8, 0.);
+            int *count = reinterpret_cast<int *>(stage.data() + n_dbl), *segment = count + Q;
+            for (size_t q = 0; q < Q; q++) {
+                const ReferencePath &p = paths[q];
+                if (p.y.size() != p.x.size() || (p.hasDistance() && p.s.size() != p.x.size())) fail("setWaypoints: x, y and s of one length");
+                const size_t n = p.x.size() < P ? p.x.size() : P;
+                count[q] = (int)n; segment[q] = -1;
+                if (_with_bounds)
+                    for (const Boundary *b : {&(*left)[q], &(*right)[q]}) if (b->x.size() != p.x.size() || b->y.size() != p.x.size()) fail("setWaypoints: the bounds need the centreline's point count");
+                for (size_t i = 0; i < n; i++) {
+                    stage[o_xy + (q * P + i) * 2] = p.x[i]; stage[o_xy + (q * P + i) * 2 + 1] = p.y[i];
+                    if (with_s) stage[o_s + q * P + i] = p.s[i];
+                    if (_with_bounds) {
+                        stage[o_left + (q * P + i) * 2] = (*left)[q].x[i]; stage[o_left + (q * P + i) * 2 + 1] = (*left)[q].y[i];
+                        stage[o_right + (q * P + i) * 2] = (*right)[q].x[i]; stage[o_right + (q * P + i) * 2 + 1] = (*right)[q].y[i];
+                    }
+                }
+            }
+            if (!_d_waypoints) { alloc(_d_waypoints, bytes); alloc(_d_status, Q); alloc(_d_road_width, Q * 8); }
+            void *stream = this->stream();
+            copy(_d_waypoints, stage.data(), bytes, stream);
+            double *base = static_cast<double *>(_d_waypoints);
+            int *d_count_in = reinterpret_cast<int *>(base + n_dbl);
+            if (hipMemcpyAsync(_d_segment, d_count_in + Q, Q * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) fail("hipMemcpyAsync");
+            if (tmpc_fit_path(_h, _Q, (int)P, _R, base + o_xy, d_count_in, with_s ? base + o_s : nullptr, _with_bounds ? base + o_left : nullptr,
+                              _with_bounds ? base + o_right : nullptr, nullptr, _d_path, _d_count, _d_length, _with_bounds ? _d_bounds : nullptr, nullptr,
+                              _with_bounds ? _d_road_width : nullptr, _d_status)) fail(tmpc_last_error(_h));
+            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");   // the staging vector ends with this call
+        }
+        /* after setWaypoints(): per scene 0 = fitted, 1 = invalid (u8), and with bounds the road width (f64); device buffers */
+        const void *status() const { return _d_status; }
+        const void *roadWidth() const { return _d_road_width; }
+        /* the fitted (or uploaded) whole paths: [n_scenes][n_seg_max][9], i32 [n_scenes], f64 [n_scenes], [n_scenes][2][n_seg_max][8] or nullptr */
+        const void *paths() const { return _d_path; }
+        const void *pathCounts() const { return _d_count; }
+        const void *pathLengths() const { return _d_length; }
+        const void *bounds() const { return _d_bounds; }
+
         /* Contouring::reset() for every scene: the next track() searches every segment */
         void reset()
         {
@@ -137,6 +193,7 @@ namespace MPCPlanner
         bool _with_bounds;
         void *_d_path{nullptr}, *_d_count{nullptr}, *_d_length{nullptr}, *_d_segment{nullptr}, *_d_closest_s{nullptr}, *_d_window{nullptr}, *_d_reached{nullptr};
         void *_d_bounds{nullptr}, *_d_bound_window{nullptr}, *_d_scene_of{nullptr};
+        void *_d_waypoints{nullptr}, *_d_status{nullptr}, *_d_road_width{nullptr};       /* setWaypoints(): allocated on its first call */
         size_t _n_scene_of{0};
     };
 }

@@ -1,8 +1,8 @@
 /*
  * mpc_planner_types/data_types.h -- the data types that cross the accelerated path, restated after the reference's
  * mpc_planner_types/include/mpc_planner_types/data_types.h:13-134 (same names, members and constructors) on the 2-double
- * Vector2d of solver_interface.h (Eigen is not in the build image).  Types the path never touches (ReferencePath bounds,
- * FixedSizeTrajectory, costmap) are left to the reference.
+ * Vector2d of solver_interface.h (Eigen is not in the build image).  ReferencePath / Boundary (the waypoints a path is fitted from) live in
+ * mpc_planner_types/path_segment.h; types the path never touches (FixedSizeTrajectory, costmap) are left to the reference.
  */
 #ifndef MPC_DATA_TYPES_HIP_H
 #define MPC_DATA_TYPES_HIP_H

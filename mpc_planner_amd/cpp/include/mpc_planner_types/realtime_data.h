@@ -3,8 +3,9 @@
  * after mpc_planner_types/include/mpc_planner_types/realtime_data.h:16-51 (member names and reset() semantics kept so that module
  * code compiles unchanged; costmap and the past trajectory are not on this path and stay with the reference's own header in a full tree).
  * The reference path is on it since Contouring::update tracks it (contouring.cpp:28-48): the reference keeps waypoints and fits a
- * RosTools::Spline2D (absent); here `reference_path` holds the fitted cubics of the whole path (fitting is not built), empty = the caller
- * supplies the window in ModuleData::path.  The road bounds ARE on the path (Contouring::constructRoadConstraintsFromBounds, contouring.cpp:237-262): the
+ * RosTools::Spline2D (absent); here `reference_path` holds the fitted cubics of the whole path, empty = the caller supplies the window in
+ * ModuleData::path; waypoints go into `reference_path_points` (and `left_bound_points` / `right_bound_points`), from which
+ * Contouring::onDataReceived fits the cubics (mpc_planner_modules/reference_path.h).  The road bounds ARE on the path (Contouring::constructRoadConstraintsFromBounds, contouring.cpp:237-262): the
  * reference keeps them as point lists and fits RosTools::Spline2D objects on the centreline's knot vector (:142-149); ros_tools is absent, so
  * here they are the fitted cubics themselves, one PathSegment per segment of ModuleData::path (same window, same knots).
  */
@@ -31,6 +32,8 @@ namespace MPCPlanner
         std::vector<PathSegment> left_bound, right_bound;                     // Contouring's road constraints; aligned with ModuleData::path, empty = not supplied
         std::vector<PathSegment> reference_path;                              // the WHOLE path (fitted cubics); non-empty: Contouring::update finds the closest point and
         double reference_path_length{0.};                                     // the window itself, and the bounds above are aligned with THIS vector; the knot behind the last segment
+        ReferencePath reference_path_points;                                  // waypoints as they arrive (the reference's RealTimeData::reference_path); non-empty:
+        Boundary left_bound_points, right_bound_points;                       // Contouring::onDataReceived("reference_path") fits reference_path / left_bound / right_bound from them
 
         // Everything but the robot's disc model is per-tick data (reference :37-47).
         void reset()

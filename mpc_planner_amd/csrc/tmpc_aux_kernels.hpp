@@ -503,6 +503,153 @@ __global__ void tmpc_set_path_parameters_kernel(Dims d, int B, double *params, c
     if (k == 0 && w == 0 && closest_s && state) state[(size_t)b * ext_nx(d) + (ZS - NU)] = closest_s[sc];
 }
 
+// ---- waypoints -> cubic segments: Contouring::onDataReceived (contouring.cpp:126-157), PathReferenceVelocity::onDataReceived -----------------
+// (path_reference_velocity.cpp:28-40).  RosTools::Spline2D and tk::spline are not in the reference tree: the natural cubic spline is restated
+// as DESIGN.md U15.  No FMA contraction, the operation order of modules.py::path_knots / fit_cubic / fit_path: every output is bit-equal to
+// the host mirror.
+constexpr int FIT_MAX_POINTS = 1025, FIT_CHUNK = 8;
+
+// one curve of a scene: n values `stride_in` doubles apart, and its (a b c d) columns in rows `stride_out` doubles apart
+struct FitCurve { const double *in; int stride_in; double *out; int stride_out; };
+
+// curve k of scene q: 0, 1 = x, y of the centreline (columns 0-3 and 4-7 of path [.][9]); then, with bounds, 2 .. 5 = left x, left y, right x,
+// right y (bounds [2][.][8]); then, with a velocity profile, v (velocity [.][4])
+__device__ inline FitCurve fit_curve(int k, int q, int n_pts_max, int n_seg_max, const double *xy, const double *left_xy, const double *right_xy,
+                                     const double *v_in, double *path, double *bounds, double *velocity)
+{
+    const size_t pts = (size_t)q * n_pts_max;
+    if (k < 2) return FitCurve{xy + pts * 2 + k, 2, path + (size_t)q * n_seg_max * 9 + 4 * k, 9};
+    if (bounds && k < 6) {
+        const int side = (k - 2) >> 1, comp = (k - 2) & 1;
+        return FitCurve{(side ? right_xy : left_xy) + pts * 2 + comp, 2, bounds + ((size_t)q * 2 + side) * n_seg_max * 8 + 4 * comp, 8};
+    }
+    return FitCurve{v_in + pts, 1, velocity + (size_t)q * n_seg_max * 4, 4};
+}
+
+// One wave per scene q.  (1) Knots into LDS: the given s, or the chord lengths by all lanes and their running sum by lane 0, strictly left
+// to right (a scan would round differently).  (2) h_i = t_{i+1} - t_i by all lanes; the scene is INVALID if n < 2 or any h_i fails
+// h_i > 0 && h_i < inf: count = 0, status = 1, nothing else is written.  (3) All lanes: up_i = h_i / 3, di_i = (2 (h_{i-1} + h_i)) / 3, the
+// `start` column, and the right-hand sides r_i of every curve into the curve's own b column.  (4) Lanes 0 .. K-1 take one curve each (K <= 7)
+// through the forward sweep -- den_i = di_i - lo_i cp_{i-1}, cp_i = up_i / den_i, g_i = (r_i - lo_i g_{i-1}) / den_i; every lane carries the
+// same cp recurrence in registers, lane 0 keeps it in LDS -- and the back substitution m_i = g_i - cp_i m_{i+1}; g_i, then m_i, sit in the
+// b column, read and written FIT_CHUNK rows at a time so that the loads do not wait on the recurrence.  (5) All lanes: a, c, d of every
+// row.  LDS: five arrays of 1025 doubles, 41 KB.  Rows at or beyond count are not touched.
+__global__ __launch_bounds__(64) void tmpc_fit_path_kernel(int n_pts_max, int n_seg_max, const double *xy, const int *count, const double *s_in,
+                                                           const double *left_xy, const double *right_xy, const double *v_in, double *path,
+                                                           int *path_count, double *path_length, double *bounds, double *velocity,
+                                                           double *road_width, uint8_t *status)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_t[FIT_MAX_POINTS], s_h[FIT_MAX_POINTS], s_up[FIT_MAX_POINTS], s_di[FIT_MAX_POINTS], s_cp[FIT_MAX_POINTS];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    int n = count[q];
+    n = n < 0 ? 0 : (n > n_pts_max ? n_pts_max : n);
+    if (n < 2) {                                                         // (uniform over the block: nobody reaches a barrier)
+        if (lane == 0) { path_count[q] = 0; if (status) status[q] = 1; }
+        return;
+    }
+    const double *pq = xy + (size_t)q * n_pts_max * 2;
+    if (s_in) {
+        for (int i = lane; i < n; i += 64) s_t[i] = s_in[(size_t)q * n_pts_max + i];
+    } else {
+        for (int i = lane; i < n - 1; i += 64) {
+            const double dx = pq[2 * (i + 1)] - pq[2 * i], dy = pq[2 * (i + 1) + 1] - pq[2 * i + 1];
+            s_h[i] = sqrt(dx * dx + dy * dy);
+        }
+        __syncthreads();
+        if (lane == 0) {
+            double t = 0.0;
+            s_t[0] = 0.0;
+            for (int i = 1; i < n; i++) { t = t + s_h[i - 1]; s_t[i] = t; }
+        }
+    }
+    __syncthreads();
+    bool bad = false;
+    for (int i = lane; i < n - 1; i += 64) {
+        const double h = s_t[i + 1] - s_t[i];
+        if (!(h > 0.0 && h < __builtin_huge_val())) bad = true;
+        s_h[i] = h;
+    }
+    if (__syncthreads_or(bad ? 1 : 0)) {
+        if (lane == 0) { path_count[q] = 0; if (status) status[q] = 1; }
+        return;
+    }
+    const int K = 2 + (bounds ? 4 : 0) + (velocity ? 1 : 0);
+    if (lane == 0) {
+        path_count[q] = n - 1;
+        path_length[q] = s_t[n - 1];
+        if (status) status[q] = 0;
+        if (road_width && bounds) {
+            const size_t o = (size_t)q * n_pts_max * 2;
+            const double ex = left_xy[o] - right_xy[o], ey = left_xy[o + 1] - right_xy[o + 1];
+            road_width[q] = sqrt(ex * ex + ey * ey);
+        }
+    }
+    for (int i = lane; i < n - 1; i += 64) {
+        s_up[i] = s_h[i] / 3.0;
+        if (i >= 1) s_di[i] = (2.0 * (s_h[i - 1] + s_h[i])) / 3.0;
+        path[((size_t)q * n_seg_max + i) * 9 + 8] = s_t[i];
+    }
+    for (int k = 0; k < K; k++) {
+        const FitCurve c = fit_curve(k, q, n_pts_max, n_seg_max, xy, left_xy, right_xy, v_in, path, bounds, velocity);
+        for (int i = 1 + lane; i <= n - 2; i += 64) {
+            const double ym = c.in[(size_t)(i - 1) * c.stride_in], y0 = c.in[(size_t)i * c.stride_in], yp = c.in[(size_t)(i + 1) * c.stride_in];
+            c.out[(size_t)i * c.stride_out + 1] = (yp - y0) / s_h[i] - (y0 - ym) / s_h[i - 1];
+        }
+    }
+    __syncthreads();
+    const FitCurve mine = fit_curve(lane < K ? lane : 0, q, n_pts_max, n_seg_max, xy, left_xy, right_xy, v_in, path, bounds, velocity);
+    double *bcol = mine.out + 1;
+    const size_t so = (size_t)mine.stride_out;
+    if (lane < K) {
+        double cp = 0.0, g = 0.0;
+        for (int i0 = 1; i0 <= n - 2; i0 += FIT_CHUNK) {
+            double r[FIT_CHUNK];
+#pragma unroll
+            for (int j = 0; j < FIT_CHUNK; j++) r[j] = i0 + j <= n - 2 ? bcol[(size_t)(i0 + j) * so] : 0.0;
+#pragma unroll
+            for (int j = 0; j < FIT_CHUNK; j++) {
+                const int i = i0 + j;
+                if (i <= n - 2) {
+                    const double lo = s_up[i - 1];
+                    const double den = s_di[i] - lo * cp;
+                    cp = s_up[i] / den;
+                    g = (r[j] - lo * g) / den;
+                    bcol[(size_t)i * so] = g;
+                    if (lane == 0) s_cp[i] = cp;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (lane < K) {
+        double m = 0.0;                                                  // m_{n-1}
+        for (int i0 = n - 2; i0 >= 1; i0 -= FIT_CHUNK) {
+            double gg[FIT_CHUNK];
+#pragma unroll
+            for (int j = 0; j < FIT_CHUNK; j++) gg[j] = i0 - j >= 1 ? bcol[(size_t)(i0 - j) * so] : 0.0;
+#pragma unroll
+            for (int j = 0; j < FIT_CHUNK; j++) {
+                const int i = i0 - j;
+                if (i >= 1) { m = gg[j] - s_cp[i] * m; bcol[(size_t)i * so] = m; }
+            }
+        }
+        bcol[0] = 0.0;                                                   // m_0
+    }
+    __syncthreads();
+    for (int k = 0; k < K; k++) {
+        const FitCurve c = fit_curve(k, q, n_pts_max, n_seg_max, xy, left_xy, right_xy, v_in, path, bounds, velocity);
+        for (int i = lane; i < n - 1; i += 64) {
+            double *o = c.out + (size_t)i * c.stride_out;
+            const double m0 = o[1], m1 = i + 1 < n - 1 ? o[c.stride_out + 1] : 0.0, h = s_h[i];
+            const double y0 = c.in[(size_t)i * c.stride_in], y1 = c.in[(size_t)(i + 1) * c.stride_in];
+            o[0] = (m1 - m0) / (3.0 * h);
+            o[2] = (y1 - y0) / h - ((2.0 * m0 + m1) * h) / 3.0;
+            o[3] = y0;
+        }
+    }
+}
+
 
 // ---- f-3: scenario -> polygon on device (SH-MPC, BASELINE config 5) ------------------------------------------------
 // The reference delegates this to the external scenario_module (scenario_constraints.cpp:47,76-79; source absent), so

@@ -1392,6 +1392,29 @@ int tmpc_set_path_parameters(tmpc_handle *h, const void *d_window, const void *d
     return TMPC_OK;
 }
 
+int tmpc_fit_path(tmpc_handle *h, int32_t n_scenes, int32_t n_pts_max, int32_t n_seg_max, const void *d_xy, const void *d_count, const void *d_s,
+                  const void *d_left_xy, const void *d_right_xy, const void *d_v, void *d_path, void *d_path_count, void *d_path_length,
+                  void *d_bounds, void *d_velocity, void *d_road_width, void *d_status)
+{
+    if (!h) return TMPC_ERR_INVALID;
+    if (n_scenes <= 0) { h->err = "tmpc_fit_path: n_scenes must be positive"; return TMPC_ERR_INVALID; }
+    if (n_pts_max < 2 || n_pts_max > tmpc::FIT_MAX_POINTS) { h->err = "tmpc_fit_path: 2 <= n_pts_max <= 1025"; return TMPC_ERR_INVALID; }
+    if (n_seg_max < n_pts_max - 1 || n_seg_max > tmpc::PATH_MAX_SEGMENTS) { h->err = "tmpc_fit_path: n_pts_max - 1 <= n_seg_max <= 1024"; return TMPC_ERR_INVALID; }
+    if (!d_xy || !d_count) { h->err = "tmpc_fit_path: NULL input (d_xy, d_count)"; return TMPC_ERR_INVALID; }
+    if (!d_path || !d_path_count || !d_path_length) { h->err = "tmpc_fit_path: NULL output (d_path, d_path_count, d_path_length)"; return TMPC_ERR_INVALID; }
+    if ((d_left_xy == nullptr) != (d_right_xy == nullptr) || (d_left_xy == nullptr) != (d_bounds == nullptr)) {
+        h->err = "tmpc_fit_path: d_left_xy, d_right_xy and d_bounds go together (all or none)"; return TMPC_ERR_INVALID;
+    }
+    if ((d_v == nullptr) != (d_velocity == nullptr)) { h->err = "tmpc_fit_path: d_v and d_velocity go together (both or neither)"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_fit_path_kernel, dim3((unsigned)n_scenes), dim3(64), 0, h->stream, n_pts_max, n_seg_max, (const double *)d_xy,
+                       (const int *)d_count, (const double *)d_s, (const double *)d_left_xy, (const double *)d_right_xy, (const double *)d_v,
+                       (double *)d_path, (int *)d_path_count, (double *)d_path_length, (double *)d_bounds, (double *)d_velocity,
+                       (double *)d_road_width, (uint8_t *)d_status);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
 int tmpc_scenario_halfspaces(tmpc_handle *h, const void *d_samples, int32_t n_pts, int32_t n_rows, const void *d_scene_of,
                              const void *d_state_x, double radius, double disc_offset)
 {

@@ -860,3 +860,130 @@ def track_path(path, length, pos, S, segment=-1, search_range=2, left=None, righ
     else:
         out["window"], out["left"], out["right"] = path_window(path, length, seg, S, left, right)
     return out
+
+
+# ---- Contouring::onDataReceived / PathReferenceVelocity::onDataReceived: waypoints -> cubic segments (contouring.cpp:126-157, ------------
+# path_reference_velocity.cpp:28-40).  RosTools::Spline2D and tk::spline are not in the reference tree: the natural cubic spline is restated
+# as DESIGN.md U15.  Host mirrors of tmpc_fit_path_kernel (csrc/tmpc_aux_kernels.hpp) and of ReferencePathSpline::fit
+# (mpc_planner_modules/reference_path.h), bit for bit: plain IEEE doubles, no fused multiply-add, the operation order below.
+
+PATH_FIT_MAX_POINTS = 1025
+
+
+def path_knots(xy, s=None):
+    """The knots t_0 .. t_{n-1} of n waypoints xy [n][2] (U15): the given s as supplied (not shifted), else the chord lengths accumulated
+    strictly left to right, t_0 = 0, t_{i+1} = t_i + sqrt(dx dx + dy dy) -- a loop, not a scan: a parallel prefix sum rounds differently."""
+    xy = np.asarray(xy, float).reshape(-1, 2)
+    n = len(xy)
+    if s is not None:
+        return np.array(np.asarray(s, float).reshape(-1)[:n], float)
+    t = np.zeros(n)
+    with np.errstate(all="ignore"):
+        d = xy[1:] - xy[:-1]
+        chord = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
+        for i in range(1, n):
+            t[i] = t[i - 1] + chord[i - 1]
+    return t
+
+
+def path_knots_valid(knots):
+    """U15: at least two knots, and every h_i = t_{i+1} - t_i satisfies h_i > 0 && h_i < inf (false for a duplicate waypoint, a
+    non-increasing s, NaN and inf: tk::spline asserts there)."""
+    t = np.asarray(knots, float)
+    if len(t) < 2:
+        return False
+    with np.errstate(all="ignore"):
+        h = t[1:] - t[:-1]
+        return bool(np.all((h > 0.0) & (h < np.inf)))
+
+
+def fit_cubic(knots, values):
+    """The natural cubic spline through (t_i, y_i), second derivative zero at both ends, as [n-1][4] = (a, b, c, d) of
+    ((a t + b) t + c) t + d on t = s - t_i (U15).  The tridiagonal system for the half second derivatives m_i (m_0 = m_{n-1} = 0) by the
+    Thomas recurrence without pivoting -- rows (h_{i-1} / 3, 2 (h_{i-1} + h_i) / 3, h_i / 3), strictly diagonally dominant --, forward
+    i = 1 .. n-2, back i = n-2 .. 1.  Two points: the straight line.  Raises ValueError on invalid knots (path_knots_valid)."""
+    t = np.asarray(knots, float).reshape(-1)
+    y = np.asarray(values, float).reshape(-1)
+    n = len(t)
+    if len(y) != n:
+        raise ValueError("fit_cubic: one value per knot")
+    if not path_knots_valid(t):
+        raise ValueError("fit_cubic: fewer than two knots, or a knot spacing that is not positive and finite")
+    with np.errstate(all="ignore"):
+        h = t[1:] - t[:-1]
+        up = h / 3.0                                                     # up_i; lo_i = up_{i-1}
+        di = (2.0 * (h[:-1] + h[1:])) / 3.0                              # di_i at [i - 1]
+        slope = (y[1:] - y[:-1]) / h
+        r = slope[1:] - slope[:-1]                                       # r_i at [i - 1]
+        cp, g, m = np.zeros(n), np.zeros(n), np.zeros(n)
+        for i in range(1, n - 1):
+            lo = up[i - 1]
+            den = di[i - 1] - lo * cp[i - 1]
+            cp[i] = up[i] / den
+            g[i] = (r[i - 1] - lo * g[i - 1]) / den
+        for i in range(n - 2, 0, -1):
+            m[i] = g[i] - cp[i] * m[i + 1]
+        out = np.zeros((n - 1, 4))
+        out[:, 0] = (m[1:] - m[:-1]) / (3.0 * h)
+        out[:, 1] = m[:-1]
+        out[:, 2] = slope - ((2.0 * m[:-1] + m[1:]) * h) / 3.0
+        out[:, 3] = y[:-1]
+    return out
+
+
+def fit_path(xy, s=None, left=None, right=None, v=None):
+    """One scene of tmpc_fit_path (host mirror; Contouring::onDataReceived, contouring.cpp:126-157, and PathReferenceVelocity::onDataReceived,
+    path_reference_velocity.cpp:28-40): the centreline through xy [n][2] on path_knots(xy, s); the bound curves through left / right [n][2]
+    (both or neither) and the velocity curve through v [n] on the CENTRELINE's knots (getTVector(), set_points(s, v)), so they must have
+    the centreline's point count; road_width = sqrt(ex ex + ey ey) between the bounds' first waypoints (:152).
+    Returns dict(path [n-1][9] = (ax bx cx dx ay by cy dy start), count = n - 1, length = t_{n-1}, left, right [n-1][8] or None, velocity
+    [n-1][4] or None, road_width or None, status).  An invalid scene (n < 2, or a knot spacing that is not positive and finite): count 0,
+    status 1, arrays of zero rows, length / road_width None -- the device writes nothing else of such a scene."""
+    xy = np.asarray(xy, float).reshape(-1, 2)
+    n = len(xy)
+    if (left is None) != (right is None):
+        raise ValueError("fit_path: left and right go together (both or neither)")
+    if n > PATH_FIT_MAX_POINTS:
+        raise ValueError("fit_path: at most 1025 waypoints")
+    sides = None if left is None else [np.asarray(b, float).reshape(-1, 2) for b in (left, right)]
+    vel = None if v is None else np.asarray(v, float).reshape(-1)
+    if (sides is not None and any(len(b) != n for b in sides)) or (vel is not None and len(vel) != n) or (s is not None and len(np.asarray(s).reshape(-1)) < n):
+        raise ValueError("fit_path: bounds, velocity and s need the centreline's point count")
+    t = path_knots(xy, s)
+    if not path_knots_valid(t):
+        return dict(path=np.zeros((0, 9)), count=0, length=None, left=None if sides is None else np.zeros((0, 8)),
+                    right=None if sides is None else np.zeros((0, 8)), velocity=None if vel is None else np.zeros((0, 4)), road_width=None, status=1)
+    path = np.concatenate([fit_cubic(t, xy[:, 0]), fit_cubic(t, xy[:, 1]), t[:-1, None]], 1)
+    out = dict(path=path, count=n - 1, length=float(t[-1]), left=None, right=None, velocity=None, road_width=None, status=0)
+    if sides is not None:
+        out["left"], out["right"] = [np.concatenate([fit_cubic(t, b[:, 0]), fit_cubic(t, b[:, 1])], 1) for b in sides]
+        with np.errstate(all="ignore"):
+            ex, ey = sides[0][0, 0] - sides[1][0, 0], sides[0][0, 1] - sides[1][0, 1]
+            out["road_width"] = float(np.sqrt(ex * ex + ey * ey))
+    if vel is not None:
+        out["velocity"] = fit_cubic(t, vel)
+    return out
+
+
+def path_velocity_window(velocity, count, segment, S, reference_velocity):
+    """PathReferenceVelocity::setParameters (path_reference_velocity.cpp:59-95) for stacks that carry the spline_v{i}_{a..d} columns
+    (codegen.stacks.contouring_path_velocity_ellipsoids): [S][4], slot w = velocity segment `segment + w` (velocity [count][4] as
+    fit_path returns it); a slot beyond the last segment is (0, 0, 0, 0) -- "brake at the end"; without a profile (velocity None) every
+    slot is (0, 0, 0, reference_velocity).  Host only: no hand-written kernel shape has these columns."""
+    out = np.zeros((S, 4))
+    if velocity is None:
+        out[:, 3] = float(reference_velocity)
+        return out
+    velocity = np.asarray(velocity, float).reshape(-1, 4)
+    for w in range(S):
+        i = int(segment) + w
+        if 0 <= i < int(count):
+            out[w] = velocity[i]
+    return out
+
+
+def path_velocity_set_parameters(pm, params, window):
+    """The spline_v{i}_{a..d} columns of every stage from path_velocity_window's [S][4] (setSolverParameterSplineVA .. VD, :80-83)."""
+    for i in range(len(window)):
+        for w, k in enumerate("abcd"):
+            params[:, pm.index(f"spline_v{i}_{k}")] = window[i, w]

@@ -48,7 +48,7 @@ EXPORTS = ["tmpc_default_dims", "tmpc_default_dims_ex", "tmpc_create", "tmpc_des
            "tmpc_reset_multipliers", "tmpc_get_stream", "tmpc_kernel_info", "tmpc_set_slots", "tmpc_set_param_sharing", "tmpc_copy_state", "tmpc_scenario_empty_stages", "tmpc_sample_scenarios",
            "tmpc_scenario_discard", "tmpc_scenario_discarded", "tmpc_linearize_topology_ex", "tmpc_clear_slot", "tmpc_gather_best",
            "tmpc_create_v2", "tmpc_set_param_sharing_ex", "tmpc_latency_mode_capacity", "tmpc_has_lane_kernels", "tmpc_debug_lds_passes", "tmpc_debug_poison_lds", "tmpc_has_lab_switches",
-           "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters", "tmpc_track_path", "tmpc_set_path_parameters"]
+           "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters", "tmpc_track_path", "tmpc_set_path_parameters", "tmpc_fit_path"]
 
 
 class TmpcObstacleOptions(C.Structure):
@@ -133,6 +133,8 @@ def load_library(path=None):
     if hasattr(lib, "tmpc_track_path"):
         lib.tmpc_track_path.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 5 + [C.c_int32, C.POINTER(TmpcPathOptions)] + [vp] * 5
         lib.tmpc_set_path_parameters.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
+    if hasattr(lib, "tmpc_fit_path"):
+        lib.tmpc_fit_path.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 13
     if hasattr(lib, "tmpc_scenario_discarded"):        # (absent from reference builds of earlier rounds used in A/B runs)
         lib.tmpc_scenario_discarded.argtypes = [vp, vp]
     if hasattr(lib, "tmpc_copy_state"):        # (absent from reference builds of earlier rounds used in A/B runs)
@@ -475,6 +477,21 @@ class BatchedSolver:
         vp = lambda p_: C.c_void_p(p_) if p_ else None
         self._check(self.lib.tmpc_set_path_parameters(self._h, vp(d_window), vp(d_scene_of), int(n_scenes), vp(d_closest_s), vp(d_state)),
                     "tmpc_set_path_parameters")
+
+    def fit_path(self, n_scenes, n_pts_max, n_seg_max, d_xy, d_count, d_path, d_path_count, d_path_length, d_s=None, d_left_xy=None,
+                 d_right_xy=None, d_v=None, d_bounds=None, d_velocity=None, d_road_width=None, d_status=None):
+        """Waypoints to cubic segments on device (tmpc_fit_path; raw device pointers): per scene the natural cubic spline
+        through d_count waypoints of d_xy [n_scenes][n_pts_max][2] -- on the knots d_s [n_scenes][n_pts_max], or on chord lengths -- into
+        d_path [n_scenes][n_seg_max][9], d_path_count and d_path_length, the layouts track_path reads; with d_left_xy / d_right_xy the bound
+        curves on the centreline's knots into d_bounds [n_scenes][2][n_seg_max][8] and the road width into d_road_width; with d_v the
+        velocity profile into d_velocity [n_scenes][n_seg_max][4]; d_status (u8): 0 fitted, 1 invalid (count 0, nothing else written).
+        Equal bit for bit to modules.fit_path.  Needs no batch.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_fit_path"):
+            raise TmpcError("this library has no tmpc_fit_path (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        self._check(self.lib.tmpc_fit_path(self._h, int(n_scenes), int(n_pts_max), int(n_seg_max), vp(d_xy), vp(d_count), vp(d_s), vp(d_left_xy),
+                                           vp(d_right_xy), vp(d_v), vp(d_path), vp(d_path_count), vp(d_path_length), vp(d_bounds), vp(d_velocity),
+                                           vp(d_road_width), vp(d_status)), "tmpc_fit_path")
 
     def scenario_halfspaces(self, d_samples, n_pts, n_rows, d_scene_of, d_state_x, radius, disc_offset=0.0):
         """Device scenario -> halfspace reduction of SH-MPC (raw device pointers; samples [n_scenes][N][n_pts][2]);

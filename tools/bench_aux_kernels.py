@@ -7,7 +7,9 @@ profile of that run holds the R = 1024 durations only).  Besides the profile, on
 launches between two HIP events on the handle's stream (launch gaps included: an upper bound of the kernel time).
 `--path local|global [--segments n]`: the reference-path kernels alone (tmpc_track_path, tmpc_set_path_parameters) at the same launch, 512 paths of
 n segments (default 64; 1024 is the cap) of 2 m, searched 2 segments either side of the previous one (local) or over every segment (global: the
-previous segment is put back to -1 before every launch, a 512-int copy that the event times include and the profile lists separately)."""
+previous segment is put back to -1 before every launch, a 512-int copy that the event times include and the profile lists separately).
+`--fit [--points n]`: the path-fit kernel alone (tmpc_fit_path), 512 scenes of n waypoints (default 65; 1025 is the cap) with bounds and a velocity
+profile -- seven curves per scene --, chord knots; needs no batch.  One JSON line: the mean of 50 launches between two HIP events."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -93,6 +95,47 @@ def path_kernels(mode, n_seg, n_scenes=512, traj=64, N=20, S=5):
     so.close()
 
 
+def fit_kernel(n_pts, n_scenes=512):
+    so = solver.BatchedSolver(solver.default_dims(), B_max=4)
+    f64 = dict(dtype=torch.float64, device=dev)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    base = []
+    for s_ in range(16):
+        rng = np.random.default_rng(s_)
+        heading = np.cumsum(rng.normal(size=n_pts) * 0.15); step = rng.uniform(0.2, 3.0, n_pts)
+        base.append(np.cumsum(np.stack([np.cos(heading) * step, np.sin(heading) * step], 1), 0))
+    xy = np.tile(np.stack(base), (n_scenes // 16, 1, 1))
+    t_xy, t_left, t_right = up(xy), up(xy + [0.0, 2.0]), up(xy - [0.0, 2.0])
+    t_v = up(np.random.default_rng(99).uniform(0.5, 3.0, (n_scenes, n_pts))); t_cnt = up(np.full(n_scenes, n_pts, np.int32))
+    R = n_pts - 1
+    path = torch.zeros((n_scenes, R, 9), **f64); pc = torch.zeros(n_scenes, dtype=torch.int32, device=dev); length = torch.zeros(n_scenes, **f64)
+    bounds = torch.zeros((n_scenes, 2, R, 8), **f64); vel = torch.zeros((n_scenes, R, 4), **f64); rw = torch.zeros(n_scenes, **f64)
+    status = torch.zeros(n_scenes, dtype=torch.uint8, device=dev)
+    call = lambda: so.fit_path(n_scenes, n_pts, R, t_xy.data_ptr(), t_cnt.data_ptr(), path.data_ptr(), pc.data_ptr(), length.data_ptr(), d_left_xy=t_left.data_ptr(),
+                               d_right_xy=t_right.data_ptr(), d_v=t_v.data_ptr(), d_bounds=bounds.data_ptr(), d_velocity=vel.data_ptr(), d_road_width=rw.data_ptr(),
+                               d_status=status.data_ptr())
+    hs = torch.cuda.ExternalStream(so.stream_ptr(), device=dev)
+    for _ in range(10):
+        call()
+    so.synchronize()
+    assert int(status.sum().item()) == 0 and int(pc.min().item()) == R
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.cuda.stream(hs):
+        e0.record()
+    for _ in range(50):
+        call()
+    with torch.cuda.stream(hs):
+        e1.record()
+    so.synchronize()
+    print(json.dumps(dict(kernel="tmpc_fit_path_kernel", n_scenes=n_scenes, points=n_pts, curves=7, knots="chord",
+                          us_per_launch_events=e0.elapsed_time(e1) * 1e3 / 50)), flush=True)
+    so.close()
+
+
+if "--fit" in sys.argv:
+    fit_kernel(int(sys.argv[sys.argv.index("--points") + 1]) if "--points" in sys.argv else 65)
+    print("done")
+    sys.exit(0)
 if "--path" in sys.argv:
     path_kernels(sys.argv[sys.argv.index("--path") + 1], int(sys.argv[sys.argv.index("--segments") + 1]) if "--segments" in sys.argv else 64)
     print("done")
