@@ -2,8 +2,9 @@
  * mpc_planner/data_preparation.h (HIP flavour) -- the reference's obstacle preparation (mpc_planner/include/mpc_planner/data_preparation.h,
  * mpc_planner/src/data_preparation.cpp) with its six functions, their names and signatures, on the Eigen-free types of
  * mpc_planner_types/data_types.h.  The reference reads the global CONFIG; these read a ModuleConfig passed as the last argument (N,
- * integrator_step, max_obstacles, max_obstacle_distance, probabilistic_enable).  Same operation order as
- * mpc_planner_amd/modules.py (prepare_obstacles and its parts) and tmpc_prepare_obstacles_kernel: values agree bit for bit, and so does the
+ * integrator_step, max_obstacles, max_obstacle_distance, probabilistic_enable).  The arithmetic is that of
+ * mpc_planner_types/prep_arithmetic.h, the one source tmpc_prepare_obstacles_kernel compiles too; the independent statement both are tested
+ * against is mpc_planner_amd/modules.py (prepare_obstacles and its parts): values agree bit for bit, and so does the
  * selection wherever the ranking keys differ (ties: the lower index, DESIGN.md U13 -- the reference's std::sort leaves them unspecified).
  * The batched device twin is mpc_planner/data_preparation_batch.h.
  */
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include <mpc_planner_modules/modules_hip.h>
+#include <mpc_planner_types/prep_arithmetic.h>
 
 namespace MPCPlanner
 {
@@ -43,19 +45,18 @@ namespace MPCPlanner
     /* :49-56 */
     inline DynamicObstacle getDummyObstacle(const State &state)
     {
-        return DynamicObstacle(-1, Vector2d(state.get("x") + 100., state.get("y") + 100.), 0., 0.);
+        return DynamicObstacle(-1, Vector2d(tmpc_arith::dummy_coordinate(state.get("x")), tmpc_arith::dummy_coordinate(state.get("y"))), 0., 0.);
     }
 
-    /* :170-186; squares written x * x (what std::pow(x, 2.) evaluates to) */
+    /* :170-186 */
     inline void propagatePredictionUncertainty(Prediction &prediction, const ModuleConfig &cfg)
     {
         if (prediction.type != PredictionType::GAUSSIAN) return;
         const double dt = cfg.integrator_step;
         double major = 0., minor = 0.;
         for (int k = 0; k < cfg.N; k++) {
-            const double sa = prediction.modes[0][k].major_radius * dt, sb = prediction.modes[0][k].minor_radius * dt;
-            major = std::sqrt(major * major + sa * sa);
-            minor = std::sqrt(minor * minor + sb * sb);
+            major = tmpc_arith::propagate_step(major, prediction.modes[0][k].major_radius, dt);
+            minor = tmpc_arith::propagate_step(minor, prediction.modes[0][k].minor_radius, dt);
             prediction.modes[0][k].major_radius = major;
             prediction.modes[0][k].minor_radius = minor;
         }
@@ -74,7 +75,7 @@ namespace MPCPlanner
         if (cfg.probabilistic_enable) { prediction = Prediction(PredictionType::GAUSSIAN); noise = 0.3; }
         else prediction = Prediction(PredictionType::DETERMINISTIC);
         for (int i = 0; i < steps; i++)
-            prediction.modes[0].push_back(PredictionStep(Vector2d(position(0) + (velocity(0) * dt) * (double)i, position(1) + (velocity(1) * dt) * (double)i),
+            prediction.modes[0].push_back(PredictionStep(Vector2d(tmpc_arith::cv_step(position(0), velocity(0), dt, i), tmpc_arith::cv_step(position(1), velocity(1), dt, i)),
                                                          0., noise, noise));
         if (cfg.probabilistic_enable) propagatePredictionUncertainty(prediction, cfg);
         return prediction;
@@ -85,24 +86,21 @@ namespace MPCPlanner
     {
         std::vector<DynamicObstacle> nearby_obstacles;
         const Vector2d pos = state.getPos();
-        for (auto &obstacle : obstacles) {
-            const double dx = obstacle.position(0) - pos(0), dy = obstacle.position(1) - pos(1);
-            if (std::sqrt(dx * dx + dy * dy) < cfg.max_obstacle_distance) nearby_obstacles.push_back(obstacle);
-        }
+        for (auto &obstacle : obstacles)
+            if (tmpc_arith::within_distance(obstacle.position(0), obstacle.position(1), pos(0), pos(1), cfg.max_obstacle_distance)) nearby_obstacles.push_back(obstacle);
         obstacles = nearby_obstacles;
     }
 
-    /* the ranking key of :113-131: min over k < N of ((k + 1) 0.6) |pred_k - (p + (v k) (cos psi, sin psi))|, from 1e5 (`v k` has no dt: kept) */
+    /* the ranking key of :113-131: the minimum over k < N of tmpc_arith::selection_key_term */
     inline double obstacleSelectionDistance(const DynamicObstacle &obstacle, const State &state, const ModuleConfig &cfg)
     {
-        double min_dist = 1e5;
+        double min_dist = tmpc_arith::SELECTION_KEY_START;
         const double c = std::cos(state.get("psi")), s = std::sin(state.get("psi"));
         const Vector2d pos = state.getPos();
         const double v = state.get("v");
         for (int k = 0; k < cfg.N; k++) {
-            const double vk = v * (double)k;
-            const double dx = obstacle.prediction.modes[0][k].position(0) - (pos(0) + vk * c), dy = obstacle.prediction.modes[0][k].position(1) - (pos(1) + vk * s);
-            const double dist = ((double)(k + 1) * 0.6) * std::sqrt(dx * dx + dy * dy);
+            const Vector2d &o = obstacle.prediction.modes[0][k].position;
+            const double dist = tmpc_arith::selection_key_term(k, o(0), o(1), pos(0), pos(1), v, c, s);
             if (dist < min_dist) min_dist = dist;
         }
         return min_dist;

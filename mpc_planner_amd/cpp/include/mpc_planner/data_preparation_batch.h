@@ -11,18 +11,17 @@
 #ifndef MPC_DATA_PREPARATION_BATCH_HIP_H
 #define MPC_DATA_PREPARATION_BATCH_HIP_H
 
-#include <hip/hip_runtime_api.h>
-
 #include <mpc_planner/data_preparation.h>
+#include <mpc_planner_solver/device_plumbing.h>
 
 namespace MPCPlanner
 {
-    class BatchedObstaclePreparation
+    class BatchedObstaclePreparation : private DevicePlumbing
     {
     public:
         /* n_scenes scenes of up to n_slots (<= 1024) raw obstacles each; cfg.max_obstacles prepared obstacles and cfg.N steps per scene */
         BatchedObstaclePreparation(tmpc_handle *handle, int n_scenes, int n_slots, const ModuleConfig &cfg)
-            : _h(handle), _Q(n_scenes), _R(n_slots), _M(cfg.max_obstacles), _N(cfg.N), _cfg(cfg)
+            : DevicePlumbing(handle, "BatchedObstaclePreparation"), _Q(n_scenes), _R(n_slots), _M(cfg.max_obstacles), _N(cfg.N), _cfg(cfg)
         {
             const size_t Q = (size_t)_Q, R = (size_t)_R, M = (size_t)_M, N = (size_t)_N;
             alloc(_d_count, Q * sizeof(int)); alloc(_d_state, Q * 4 * 8); alloc(_d_pos, Q * R * 2 * 8); alloc(_d_radius, Q * R * 8);
@@ -31,7 +30,7 @@ namespace MPCPlanner
         }
         ~BatchedObstaclePreparation()
         {
-            for (void *p : {_d_count, _d_state, _d_pos, _d_radius, _d_vel, _d_pred, _o_pos, _o_shape, _o_radius, _o_gauss, _o_sel, _d_scene_of}) if (p) (void)hipFree(p);
+            for (void *p : {_d_count, _d_state, _d_pos, _d_radius, _d_vel, _d_pred, _o_pos, _o_shape, _o_radius, _o_gauss, _o_sel}) if (p) (void)hipFree(p);
         }
         BatchedObstaclePreparation(const BatchedObstaclePreparation &) = delete;
         BatchedObstaclePreparation &operator=(const BatchedObstaclePreparation &) = delete;
@@ -63,12 +62,11 @@ namespace MPCPlanner
                     }
                 }
             }
-            void *stream = nullptr;
-            if (tmpc_get_stream(_h, &stream)) fail(tmpc_last_error(_h));
+            void *stream = this->stream();
             copy(_d_count, count.data(), Q * sizeof(int), stream); copy(_d_state, state.data(), Q * 4 * 8, stream);
             copy(_d_pos, pos.data(), pos.size() * 8, stream); copy(_d_radius, radius.data(), radius.size() * 8, stream);
             copy(velocities ? _d_vel : _d_pred, aux.data(), aux.size() * 8, stream);
-            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");   // the staging vectors end with this call
+            sync(stream);                                                     // the staging vectors end with this call
             tmpc_obstacle_options opt{};
             opt.size = sizeof(opt); opt.probabilistic = _cfg.probabilistic_enable ? 1 : 0; opt.propagate_passes = propagate_passes; opt.noise = 0.3;
             opt.max_obstacle_distance = _cfg.max_obstacle_distance;
@@ -80,16 +78,9 @@ namespace MPCPlanner
          * EllipsoidConstraints / GaussianConstraints::setParameters for every entry, stage and obstacle in one launch. */
         void setParameters(const std::vector<int> &scene_of, double disc_offset = 0.)
         {
-            void *stream = nullptr;
-            if (tmpc_get_stream(_h, &stream)) fail(tmpc_last_error(_h));
-            if (scene_of.size() > _n_scene_of) {
-                if (_d_scene_of) (void)hipFree(_d_scene_of);
-                alloc(_d_scene_of, scene_of.size() * sizeof(int)); _n_scene_of = scene_of.size();
-            }
-            copy(_d_scene_of, scene_of.data(), scene_of.size() * sizeof(int), stream);
-            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");   // (the caller's vector may end with this call)
+            const void *d_scene_of = uploadSceneOf(scene_of);
             const double chi = ExponentialQuantile(0.5, 1.0 - _cfg.risk);                                  // on the host: no device logarithm enters
-            if (tmpc_set_obstacle_parameters(_h, _o_pos, _o_shape, _o_radius, _o_gauss, _d_scene_of, _d_state, _cfg.robot_radius, disc_offset, _cfg.risk, chi,
+            if (tmpc_set_obstacle_parameters(_h, _o_pos, _o_shape, _o_radius, _o_gauss, d_scene_of, _d_state, _cfg.robot_radius, disc_offset, _cfg.risk, chi,
                                              _cfg.obstacle_radius)) fail(tmpc_last_error(_h));
         }
 
@@ -110,18 +101,10 @@ namespace MPCPlanner
         }
 
     private:
-        static void fail(const char *what) { std::fprintf(stderr, "BatchedObstaclePreparation: %s\n", what); std::exit(1); }
-        static void alloc(void *&p, size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) fail("hipMalloc"); }
-        static void copy(void *dst, const void *src, size_t bytes, void *stream)
-        {
-            if (bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) fail("hipMemcpyAsync");
-        }
-        tmpc_handle *_h;
         int _Q, _R, _M, _N;
         ModuleConfig _cfg;
         void *_d_count{nullptr}, *_d_state{nullptr}, *_d_pos{nullptr}, *_d_radius{nullptr}, *_d_vel{nullptr}, *_d_pred{nullptr};
-        void *_o_pos{nullptr}, *_o_shape{nullptr}, *_o_radius{nullptr}, *_o_gauss{nullptr}, *_o_sel{nullptr}, *_d_scene_of{nullptr};
-        size_t _n_scene_of{0};
+        void *_o_pos{nullptr}, *_o_shape{nullptr}, *_o_radius{nullptr}, *_o_gauss{nullptr}, *_o_sel{nullptr};
     };
 }
 #endif

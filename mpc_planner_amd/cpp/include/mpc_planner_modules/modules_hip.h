@@ -164,10 +164,10 @@ namespace MPCPlanner
                 setSolverParameterSplineStart(k, _solver->_params, sg.start, i);
             }
         }
-        /* ---- road constraints (:181-262).  RosTools::Spline2D is not in the reference tree; ASSUMED: getOrthogonal(s) =
-         * (y'(s), -x'(s)) / |.| (the normal to the right of travel), getPoint / the derivative = the plain piecewise cubic of the segment
-         * i = max{j : start_j <= s} of the window (i = 0 below the first knot, the last cubic continues beyond it).  Same arithmetic, in the same
-         * order, as modules.py::road_halfspaces / road_halfspaces_from_bounds and tmpc_road_halfspaces_kernel. ---- */
+        /* ---- road constraints (:181-262): the rows of mpc_planner_types/prep_arithmetic.h (RosTools::Spline2D restated there), the
+         * one source tmpc_road_halfspaces_kernel compiles too, on the cubic of the segment i = max{j : start_j <= s} of the window (i = 0 below the
+         * first knot, the last cubic continues beyond it); the independent statement both are tested against, bit for bit, is
+         * modules.py::road_halfspaces / road_halfspaces_from_bounds. ---- */
         void constructRoadConstraints(const RealTimeData &data, ModuleData &module_data)
         {
             const std::vector<PathSegment> &left = _path_mode ? _left_window : data.left_bound, &right = _path_mode ? _right_window : data.right_bound;
@@ -185,12 +185,11 @@ namespace MPCPlanner
             for (int k = 1; k < _solver->N; k++) {
                 module_data.static_obstacles[k].clear();
                 const double cur_s = _solver->getEgoPrediction(k, "spline");
-                Vector2d path_point(0., 0.), A(0., 0.);
-                evaluateSegments(_segments, cur_s, path_point, A);
-                const double b_left = A(0) * (path_point(0) + A(0) * offset_first) + A(1) * (path_point(1) + A(1) * offset_first);
-                module_data.static_obstacles[k].emplace_back(A, b_left);
-                const double b_right = A(0) * (path_point(0) - A(0) * offset_second) + A(1) * (path_point(1) - A(1) * offset_second);
-                module_data.static_obstacles[k].emplace_back(Vector2d(-A(0), -A(1)), -b_right);
+                double c[8], row[6];
+                const double t = segmentAt(_segments, cur_s, c);
+                tmpc_arith::road_rows_centreline(c, t, offset_first, offset_second, row);
+                module_data.static_obstacles[k].emplace_back(Vector2d(row[0], row[1]), row[2]);
+                module_data.static_obstacles[k].emplace_back(Vector2d(row[3], row[4]), row[5]);
             }
         }
         void constructRoadConstraintsFromBounds(const RealTimeData &data, ModuleData &module_data)
@@ -200,13 +199,13 @@ namespace MPCPlanner
             for (int k = 1; k < _solver->N; k++) {
                 module_data.static_obstacles[k].clear();
                 const double cur_s = _solver->getEgoPrediction(k, "spline");
-                Vector2d Pl(0., 0.), Al(0., 0.), Pr(0., 0.), Ar(0., 0.);
-                evaluateSegments(_path_mode ? _left_window : data.left_bound, cur_s, Pl, Al);
-                const double bl = Al(0) * (Pl(0) + Al(0) * r) + Al(1) * (Pl(1) + Al(1) * r);
-                module_data.static_obstacles[k].emplace_back(Vector2d(-Al(0), -Al(1)), -bl);
-                evaluateSegments(_path_mode ? _right_window : data.right_bound, cur_s, Pr, Ar);
-                const double br = Ar(0) * (Pr(0) - Ar(0) * r) + Ar(1) * (Pr(1) - Ar(1) * r);
-                module_data.static_obstacles[k].emplace_back(Ar, br);
+                double c[8], row[6];
+                const double tl = segmentAt(_path_mode ? _left_window : data.left_bound, cur_s, c);
+                tmpc_arith::road_row_left_bound(c, tl, r, row);
+                const double tr = segmentAt(_path_mode ? _right_window : data.right_bound, cur_s, c);
+                tmpc_arith::road_row_right_bound(c, tr, r, row + 3);
+                module_data.static_obstacles[k].emplace_back(Vector2d(row[0], row[1]), row[2]);
+                module_data.static_obstacles[k].emplace_back(Vector2d(row[3], row[4]), row[5]);
             }
         }
         std::shared_ptr<Solver> _solver;
@@ -218,20 +217,13 @@ namespace MPCPlanner
                 for (auto &obstacle : module_data.static_obstacles) obstacle.reserve(2);
             }
         }
-        /* point and right-hand unit normal at s of the cubics `coef`, on the knots of the path window (`_segments[i].start`) */
-        void evaluateSegments(const std::vector<PathSegment> &coef, double s, Vector2d &point, Vector2d &orthogonal) const
+        /* the cubic of `coef` that holds s on the knots of the path window (`_segments[i].start`), as eight coefficients, and t = s - start_i */
+        double segmentAt(const std::vector<PathSegment> &coef, double s, double c[8]) const
         {
             size_t i = 0;
             for (size_t j = 0; j < _segments.size() && j < coef.size(); j++) if (_segments[j].start <= s) i = j;
-            const PathSegment &c = coef.at(i);
-            const double t = s - _segments[i].start;
-            const double px = ((c.ax * t + c.bx) * t + c.cx) * t + c.dx;
-            const double py = ((c.ay * t + c.by) * t + c.cy) * t + c.dy;
-            const double dx = (3.0 * c.ax * t + 2.0 * c.bx) * t + c.cx;
-            const double dy = (3.0 * c.ay * t + 2.0 * c.by) * t + c.cy;
-            const double n = std::sqrt(dx * dx + dy * dy);
-            point = Vector2d(px, py);
-            orthogonal = Vector2d(dy / n, -dx / n);
+            coefficients(coef.at(i), c);
+            return s - _segments[i].start;
         }
         ModuleConfig _cfg;
         std::vector<PathSegment> _segments;

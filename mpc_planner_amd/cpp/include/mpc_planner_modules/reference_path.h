@@ -2,9 +2,10 @@
  * mpc_planner_modules/reference_path.h -- a whole reference path as Contouring::update needs it every tick (contouring.cpp:28-48): the closest
  * point, the segment window setSplineParameters writes (:94-124), the objective-reached test (:167-175); and as onDataReceived builds it when
  * waypoints arrive (:126-157): fit / fitBounds / fitCubic, the natural cubic spline of DESIGN.md U15.  Needs no Solver and no generated
- * header.  RosTools::Spline2D is not in the reference tree: the search is restated, its assumptions are DESIGN.md U14.  The arithmetic and its
- * order are those of mpc_planner_amd/modules.py (closest_point_on_segment, find_closest_point, path_window) and of tmpc_track_path_kernel: the
- * three agree bit for bit where the compiler does not fuse multiply-adds (build with -ffp-contract=off on a target that has them).
+ * header.  RosTools::Spline2D is not in the reference tree: the search is restated, its assumptions are DESIGN.md U14.  The arithmetic is that
+ * of mpc_planner_types/prep_arithmetic.h, the one source tmpc_track_path_kernel and tmpc_fit_path_kernel compile too; the independent
+ * statement both are tested against, bit for bit, is mpc_planner_amd/modules.py (closest_point_on_segment, find_closest_point, path_window,
+ * fit_cubic) -- where the compiler does not fuse multiply-adds (build with -ffp-contract=off on a target that has them).
  */
 #ifndef MPC_REFERENCE_PATH_HIP_H
 #define MPC_REFERENCE_PATH_HIP_H
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include <mpc_planner_types/path_segment.h>
+#include <mpc_planner_types/prep_arithmetic.h>
 
 namespace MPCPlanner
 {
@@ -22,60 +24,12 @@ namespace MPCPlanner
         double length{0.};                                      /* the knot behind the last segment: L_i = start_{i+1} - start_i, L_last = length - start_last */
         std::vector<PathSegment> left_bound, right_bound;       /* optional: bound cubics on the same knots (their `start` is not read) */
 
-        static constexpr int COARSE = 8, BISECTIONS = 40;
-
         bool empty() const { return segments.empty(); }
         int numSegments() const { return (int)segments.size(); }
         double segmentLength(int i) const { return (i + 1 < numSegments() ? segments[i + 1].start : length) - segments[i].start; }
 
-        /* point and derivative of one cubic at t, Horner form (the forms of Contouring::evaluateSegments) */
-        static void cubic(const PathSegment &c, double t, double &x, double &y, double &dx, double &dy)
-        {
-            x = ((c.ax * t + c.bx) * t + c.cx) * t + c.dx;
-            y = ((c.ay * t + c.by) * t + c.cy) * t + c.dy;
-            dx = (3.0 * c.ax * t + 2.0 * c.bx) * t + c.cx;
-            dy = (3.0 * c.ay * t + 2.0 * c.by) * t + c.cy;
-        }
-
-        /* closest point of the cubic on t in [0, L] to (px, py): D = |P(t) - p|^2, g = (P(t) - p).P'(t).  Nine coarse samples t_j = L (j / 8); the
-         * bracket around the best (lowest j on ties); an end of the bracket if g does not change sign inside it, else exactly 40 bisections and
-         * the bracket's midpoint; the coarse sample wins if its D is strictly smaller. */
-        static void closestOnSegment(const PathSegment &c, double L, double px, double py, double &D_out, double &t_out)
-        {
-            auto eval = [&](double t, double &g) {
-                double x, y, dx, dy;
-                cubic(c, t, x, y, dx, dy);
-                const double ex = x - px, ey = y - py;
-                g = ex * dx + ey * dy;
-                return ex * ex + ey * ey;
-            };
-            double g;
-            int js = 0;
-            double Dj = eval(L * (0.0 / 8.0), g);
-            for (int j = 1; j <= COARSE; j++) {
-                const double Dc = eval(L * ((double)j / 8.0), g);
-                if (Dc < Dj) { js = j; Dj = Dc; }
-            }
-            double lo = L * ((double)(js > 0 ? js - 1 : 0) / 8.0), hi = L * ((double)(js < COARSE ? js + 1 : COARSE) / 8.0);
-            double tc;
-            eval(lo, g);
-            if (g >= 0.0) tc = lo;
-            else {
-                eval(hi, g);
-                if (g <= 0.0) tc = hi;
-                else {
-                    for (int it = 0; it < BISECTIONS; it++) {
-                        const double mid = 0.5 * (lo + hi);
-                        eval(mid, g);
-                        if (g > 0.0) hi = mid; else lo = mid;
-                    }
-                    tc = 0.5 * (lo + hi);
-                }
-            }
-            const double Dc = eval(tc, g);
-            if (Dj < Dc) { D_out = Dj; t_out = L * ((double)js / 8.0); }
-            else { D_out = Dc; t_out = tc; }
-        }
+        /* point and derivative of cubic c at t */
+        static void cubic(const PathSegment &c, double t, double &x, double &y, double &dx, double &dy) { double k[8]; coefficients(c, k); tmpc_arith::cubic(k, t, x, y, dx, dy); }
 
         /* RosTools::Spline2D::findClosestPoint as Contouring::update uses it (:37; U14-1).  segment < 0 (a new path, a reset): every segment is a
          * candidate; otherwise [max(0, prev - range), min(n - 1, prev + range)], prev clamped into [0, n - 1].  The comparison starts from the
@@ -95,8 +49,9 @@ namespace MPCPlanner
             int best = first;
             double best_D = 0., best_t = 0.;
             for (int i = first; i <= last; i++) {
-                double D, t;
-                closestOnSegment(segments[i], segmentLength(i), p(0), p(1), D, t);
+                double D, t, k[8];
+                coefficients(segments[i], k);
+                tmpc_arith::closest_on_segment(k, segmentLength(i), p(0), p(1), D, t);
                 if (i == first || D < best_D) { best = i; best_D = D; best_t = t; }
             }
             segment = best;
@@ -118,7 +73,9 @@ namespace MPCPlanner
             auto pad = [&](const PathSegment &last) {
                 double x, y, dx, dy;
                 cubic(last, L_last, x, y, dx, dy);
-                return PathSegment{0., 0., dx, x, 0., 0., dy, y, length};
+                double r[9];
+                for (int col = 0; col < 9; col++) r[col] = tmpc_arith::padding_entry(col, x, y, dx, dy, length);
+                return PathSegment{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8]};
             };
             for (int w = 0; w < S; w++) {
                 const int i = segment + w;
@@ -150,7 +107,7 @@ namespace MPCPlanner
             if (t.size() < 2) return false;
             for (size_t i = 0; i + 1 < t.size(); i++) {
                 const double h = t[i + 1] - t[i];
-                if (!(h > 0.0 && h < HUGE_VAL)) return false;
+                if (!tmpc_arith::spacing_valid(h)) return false;
             }
             return true;
         }
@@ -165,21 +122,15 @@ namespace MPCPlanner
             std::vector<double> h(n - 1), cp(n, 0.), g(n, 0.), m(n, 0.);
             for (size_t i = 0; i + 1 < n; i++) h[i] = t[i + 1] - t[i];
             for (size_t i = 1; i + 1 < n; i++) {
-                const double lo = h[i - 1] / 3.0;
-                const double di = (2.0 * (h[i - 1] + h[i])) / 3.0;
-                const double up = h[i] / 3.0;
-                const double r = (y[i + 1] - y[i]) / h[i] - (y[i] - y[i - 1]) / h[i - 1];
-                const double den = di - lo * cp[i - 1];
-                cp[i] = up / den;
-                g[i] = (r - lo * g[i - 1]) / den;
+                cp[i] = cp[i - 1]; g[i] = g[i - 1];
+                tmpc_arith::thomas_forward(tmpc_arith::spline_off(h[i - 1]), tmpc_arith::spline_diag(h[i - 1], h[i]), tmpc_arith::spline_off(h[i]),
+                                           tmpc_arith::spline_rhs(y[i - 1], y[i], y[i + 1], h[i - 1], h[i]), cp[i], g[i]);
             }
-            for (size_t i = n - 2; i >= 1; i--) m[i] = g[i] - cp[i] * m[i + 1];
+            for (size_t i = n - 2; i >= 1; i--) m[i] = tmpc_arith::thomas_backward(g[i], cp[i], m[i + 1]);
             a.assign(n - 1, 0.); b.assign(n - 1, 0.); c.assign(n - 1, 0.); d.assign(n - 1, 0.);
             for (size_t i = 0; i + 1 < n; i++) {
-                a[i] = (m[i + 1] - m[i]) / (3.0 * h[i]);
                 b[i] = m[i];
-                c[i] = (y[i + 1] - y[i]) / h[i] - ((2.0 * m[i] + m[i + 1]) * h[i]) / 3.0;
-                d[i] = y[i];
+                tmpc_arith::spline_row(m[i], m[i + 1], h[i], y[i], y[i + 1], a[i], c[i], d[i]);
             }
             return true;
         }
@@ -223,8 +174,7 @@ namespace MPCPlanner
             if (n <= 0) return false;
             double x, y, dx, dy;
             cubic(segments[n - 1], segmentLength(n - 1), x, y, dx, dy);
-            const double ex = x - p(0), ey = y - p(1);
-            return std::sqrt(ex * ex + ey * ey) < 1.0;
+            return tmpc_arith::within_distance(x, y, p(0), p(1), 1.0);
         }
     };
 }

@@ -13,23 +13,17 @@
 #ifndef MPC_REFERENCE_PATH_BATCH_HIP_H
 #define MPC_REFERENCE_PATH_BATCH_HIP_H
 
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include <hip/hip_runtime_api.h>
-
-#include "tmpc_hip.h"
 #include <mpc_planner_modules/reference_path.h>
+#include <mpc_planner_solver/device_plumbing.h>
 
 namespace MPCPlanner
 {
-    class BatchedPathTracking
+    class BatchedPathTracking : private DevicePlumbing
     {
     public:
         /* n_scenes paths of up to n_seg_max (<= 1024) segments each; S = the solver's window (tmpc_dims::S) */
         BatchedPathTracking(tmpc_handle *handle, int n_scenes, int n_seg_max, int S, bool with_bounds)
-            : _h(handle), _Q(n_scenes), _R(n_seg_max), _S(S), _with_bounds(with_bounds)
+            : DevicePlumbing(handle, "BatchedPathTracking"), _Q(n_scenes), _R(n_seg_max), _S(S), _with_bounds(with_bounds)
         {
             const size_t Q = (size_t)_Q, R = (size_t)_R, W = (size_t)_S;
             alloc(_d_path, Q * R * 9 * 8); alloc(_d_count, Q * sizeof(int)); alloc(_d_length, Q * 8); alloc(_d_segment, Q * sizeof(int));
@@ -38,7 +32,7 @@ namespace MPCPlanner
         }
         ~BatchedPathTracking()
         {
-            for (void *p : {_d_path, _d_count, _d_length, _d_segment, _d_closest_s, _d_window, _d_reached, _d_bounds, _d_bound_window, _d_scene_of, _d_waypoints, _d_status, _d_road_width}) if (p) (void)hipFree(p);
+            for (void *p : {_d_path, _d_count, _d_length, _d_segment, _d_closest_s, _d_window, _d_reached, _d_bounds, _d_bound_window, _d_waypoints, _d_status, _d_road_width}) if (p) (void)hipFree(p);
         }
         BatchedPathTracking(const BatchedPathTracking &) = delete;
         BatchedPathTracking &operator=(const BatchedPathTracking &) = delete;
@@ -58,15 +52,15 @@ namespace MPCPlanner
                 length[q] = p.length;
                 if (_with_bounds && (p.left_bound.size() < (size_t)count[q] || p.right_bound.size() < (size_t)count[q])) fail("setPaths: a bound cubic per segment");
                 for (size_t i = 0; i < (size_t)count[q]; i++) {
-                    put(&path[(q * R + i) * 9], p.segments[i]); path[(q * R + i) * 9 + 8] = p.segments[i].start;
-                    if (_with_bounds) { put(&bounds[((q * 2 + 0) * R + i) * 8], p.left_bound[i]); put(&bounds[((q * 2 + 1) * R + i) * 8], p.right_bound[i]); }
+                    coefficients(p.segments[i], &path[(q * R + i) * 9]); path[(q * R + i) * 9 + 8] = p.segments[i].start;
+                    if (_with_bounds) { coefficients(p.left_bound[i], &bounds[((q * 2 + 0) * R + i) * 8]); coefficients(p.right_bound[i], &bounds[((q * 2 + 1) * R + i) * 8]); }
                 }
             }
             void *stream = this->stream();
             copy(_d_path, path.data(), path.size() * 8, stream); copy(_d_count, count.data(), Q * sizeof(int), stream);
             copy(_d_length, length.data(), Q * 8, stream); copy(_d_segment, segment.data(), Q * sizeof(int), stream);
             if (_with_bounds) copy(_d_bounds, bounds.data(), bounds.size() * 8, stream);
-            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");   // the staging vectors end with this call
+            sync(stream);                                                     // the staging vectors end with this call
         }
         /* The alternative to setPaths(): raw waypoints for every scene, fitted ON THE DEVICE (tmpc_fit_path) into the twin's own
          * path / count / length / bound buffers -- bit for bit what ReferencePathSpline::fit / fitBounds give on the host.  One upload (the
@@ -112,7 +106,7 @@ namespace MPCPlanner
             if (tmpc_fit_path(_h, _Q, (int)P, _R, base + o_xy, d_count_in, with_s ? base + o_s : nullptr, _with_bounds ? base + o_left : nullptr,
                               _with_bounds ? base + o_right : nullptr, nullptr, _d_path, _d_count, _d_length, _with_bounds ? _d_bounds : nullptr, nullptr,
                               _with_bounds ? _d_road_width : nullptr, _d_status)) fail(tmpc_last_error(_h));
-            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");   // the staging vector ends with this call
+            sync(stream);                                                     // the staging vector ends with this call
         }
         /* after setWaypoints(): per scene 0 = fitted, 1 = invalid (u8), and with bounds the road width (f64); device buffers */
         const void *status() const { return _d_status; }
@@ -129,7 +123,7 @@ namespace MPCPlanner
             const std::vector<int> segment((size_t)_Q, -1);
             void *stream = this->stream();
             copy(_d_segment, segment.data(), segment.size() * sizeof(int), stream);
-            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");
+            sync(stream);
         }
 
         /* One tick of Contouring::update for every scene: d_pos f64 [n_scenes][pos_stride] on the device, x and y first (a state buffer as
@@ -148,14 +142,7 @@ namespace MPCPlanner
          * the reference (planner.cpp:81-96). */
         void setParameters(const std::vector<int> &scene_of, void *d_state = nullptr)
         {
-            void *stream = this->stream();
-            if (scene_of.size() > _n_scene_of) {
-                if (_d_scene_of) (void)hipFree(_d_scene_of);
-                alloc(_d_scene_of, scene_of.size() * sizeof(int)); _n_scene_of = scene_of.size();
-            }
-            copy(_d_scene_of, scene_of.data(), scene_of.size() * sizeof(int), stream);
-            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) fail("hipStreamSynchronize");   // (the caller's vector may end with this call)
-            if (tmpc_set_path_parameters(_h, _d_window, _d_scene_of, _Q, d_state ? _d_closest_s : nullptr, d_state)) fail(tmpc_last_error(_h));
+            if (tmpc_set_path_parameters(_h, _d_window, uploadSceneOf(scene_of), _Q, d_state ? _d_closest_s : nullptr, d_state)) fail(tmpc_last_error(_h));
         }
 
         /* device buffers, valid after track(): the window [n_scenes][S][9], the bound window [n_scenes][2][S][8] (what tmpc_road_halfspaces takes
@@ -175,26 +162,11 @@ namespace MPCPlanner
         }
 
     private:
-        static void fail(const char *what) { std::fprintf(stderr, "BatchedPathTracking: %s\n", what); std::exit(1); }
-        static void alloc(void *&p, size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) fail("hipMalloc"); }
-        static void copy(void *dst, const void *src, size_t bytes, void *stream)
-        {
-            if (bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) fail("hipMemcpyAsync");
-        }
-        static void put(double *o, const PathSegment &c) { o[0] = c.ax; o[1] = c.bx; o[2] = c.cx; o[3] = c.dx; o[4] = c.ay; o[5] = c.by; o[6] = c.cy; o[7] = c.dy; }
-        void *stream() const
-        {
-            void *s = nullptr;
-            if (tmpc_get_stream(_h, &s)) fail(tmpc_last_error(_h));
-            return s;
-        }
-        tmpc_handle *_h;
         int _Q, _R, _S;
         bool _with_bounds;
         void *_d_path{nullptr}, *_d_count{nullptr}, *_d_length{nullptr}, *_d_segment{nullptr}, *_d_closest_s{nullptr}, *_d_window{nullptr}, *_d_reached{nullptr};
-        void *_d_bounds{nullptr}, *_d_bound_window{nullptr}, *_d_scene_of{nullptr};
+        void *_d_bounds{nullptr}, *_d_bound_window{nullptr};
         void *_d_waypoints{nullptr}, *_d_status{nullptr}, *_d_road_width{nullptr};       /* setWaypoints(): allocated on its first call */
-        size_t _n_scene_of{0};
     };
 }
 #endif

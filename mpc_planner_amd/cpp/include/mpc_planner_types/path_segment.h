@@ -11,6 +11,8 @@ namespace MPCPlanner
     /* One cubic segment of the contouring reference (contouring.cpp:94-124 reads these numbers out of RosTools::Spline2D, which
      * is not in the reference tree): x(t) = ax t^3 + bx t^2 + cx t + dx, same for y, t = s - start. */
     struct PathSegment { double ax, bx, cx, dx, ay, by, cy, dy, start; };
+    /* its eight coefficients as the array mpc_planner_types/prep_arithmetic.h and the device buffers take: (ax bx cx dx ay by cy dy) */
+    inline void coefficients(const PathSegment &c, double o[8]) { o[0] = c.ax; o[1] = c.bx; o[2] = c.cx; o[3] = c.dx; o[4] = c.ay; o[5] = c.by; o[6] = c.cy; o[7] = c.dy; }
 
     /* Waypoints as they arrive (the reference's ReferencePath, mpc_planner_types/data_types.h:93-111): x, y, and optionally the heading psi
      * (not used by the fit), the velocity v at each waypoint and the path parameter s of each waypoint (empty: chord lengths). */

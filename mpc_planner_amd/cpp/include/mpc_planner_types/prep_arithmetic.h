@@ -1,0 +1,184 @@
+/* mpc_planner_types/prep_arithmetic.h -- the double-precision arithmetic of data preparation (road rows, obstacle preparation, path tracking,
+ * path fitting), written ONCE for the device kernels (csrc/tmpc_aux_kernels.hpp) and the Solver-free C++ headers (reference_path.h,
+ * data_preparation.h, Contouring in modules_hip.h): both compile these functions, so they cannot drift apart.  The independent statement the
+ * tests compare both against is the numpy mirror, mpc_planner_amd/modules.py; every function keeps the mirror's operation order, and nothing is
+ * fused into multiply-adds (the pragma under clang; build host code with -ffp-contract=off).  Plain functions on doubles: no containers, no
+ * planner types.  A cubic is its eight coefficients c = (ax bx cx dx ay by cy dy): x(t) = ((ax t + bx) t + cx) t + dx, the same for y. */
+#ifndef MPC_PREP_ARITHMETIC_HIP_H
+#define MPC_PREP_ARITHMETIC_HIP_H
+
+#include <math.h>
+
+#ifdef __HIPCC__
+#define TMPC_ARITH_FN __host__ __device__ inline
+#else
+#define TMPC_ARITH_FN inline
+#endif
+#ifdef __clang__
+#define TMPC_ARITH_NO_FMA _Pragma("clang fp contract(off)")
+#else
+#define TMPC_ARITH_NO_FMA
+#endif
+
+namespace tmpc_arith
+{
+    /* ---- cubic: point and derivative at t, Horner form ---- */
+    TMPC_ARITH_FN void cubic(const double c[8], double t, double &x, double &y, double &dx, double &dy)
+    {
+        TMPC_ARITH_NO_FMA
+        x = ((c[0] * t + c[1]) * t + c[2]) * t + c[3];
+        y = ((c[4] * t + c[5]) * t + c[6]) * t + c[7];
+        dx = (3.0 * c[0] * t + 2.0 * c[1]) * t + c[2];
+        dy = (3.0 * c[4] * t + 2.0 * c[5]) * t + c[6];
+    }
+
+    /* ---- closest point of the cubic on t in [0, L] to (px, py) (RosTools::Spline2D::findClosestPoint restated): D = |P(t) - p|^2,
+     * g = (P(t) - p).P'(t).  Nine coarse samples t_j = L (j / 8), the bracket around the best (lowest j on ties), an end of the bracket if g does
+     * not change sign inside it, else exactly 40 bisections (no data-dependent exit) and the bracket's midpoint; the coarse sample wins if its D
+     * is strictly smaller. ---- */
+    constexpr int COARSE = 8, BISECTIONS = 40;
+    TMPC_ARITH_FN void closest_on_segment(const double cg[8], double L, double px, double py, double &D_out, double &t_out)
+    {
+        TMPC_ARITH_NO_FMA
+        double c[8];
+        for (int i = 0; i < 8; i++) c[i] = cg[i];
+        auto eval = [&](double t, double &g) {
+            TMPC_ARITH_NO_FMA
+            double x, y, dx, dy;
+            cubic(c, t, x, y, dx, dy);
+            const double ex = x - px, ey = y - py;
+            g = ex * dx + ey * dy;
+            return ex * ex + ey * ey;
+        };
+        double g;
+        int js = 0;
+        double Dj = eval(L * (0.0 / 8.0), g);
+        for (int j = 1; j <= COARSE; j++) {
+            const double Dc = eval(L * ((double)j / 8.0), g);
+            if (Dc < Dj) { js = j; Dj = Dc; }
+        }
+        double lo = L * ((double)(js > 0 ? js - 1 : 0) / 8.0), hi = L * ((double)(js < COARSE ? js + 1 : COARSE) / 8.0);
+        double tc;
+        eval(lo, g);
+        if (g >= 0.0) tc = lo;
+        else {
+            eval(hi, g);
+            if (g <= 0.0) tc = hi;
+            else {
+                for (int it = 0; it < BISECTIONS; it++) {
+                    const double mid = 0.5 * (lo + hi);
+                    eval(mid, g);
+                    if (g > 0.0) hi = mid; else lo = mid;
+                }
+                tc = 0.5 * (lo + hi);
+            }
+        }
+        const double Dc = eval(tc, g);
+        if (Dj < Dc) { D_out = Dj; t_out = L * ((double)js / 8.0); }
+        else { D_out = Dc; t_out = tc; }
+    }
+
+    /* ---- road rows (Contouring::constructRoadConstraints, contouring.cpp:181-262).  RosTools::Spline2D is not in the reference tree; ASSUMED
+     * (DESIGN.md U12): getOrthogonal(s) = (y'(s), -x'(s)) / |.| (to the right of travel: the only sign for which bounds mode is a corridor between
+     * the bounds), and P, x', y' are the plain piecewise cubics, no sigmoid glue.  The lookup of the segment that holds s, i = max{j : start_j <= s},
+     * rounds nothing and stays with each caller's storage. ---- */
+    /* point P and right-hand unit normal A of a cubic at t */
+    TMPC_ARITH_FN void road_frame(const double c[8], double t, double &px, double &py, double &ax, double &ay)
+    {
+        TMPC_ARITH_NO_FMA
+        double dx, dy;
+        cubic(c, t, px, py, dx, dy);
+        const double n = sqrt(dx * dx + dy * dy);
+        ax = dy / n; ay = -dx / n;
+    }
+    /* A.(P + A off) and A.(P - A off) */
+    TMPC_ARITH_FN double road_offset_plus(double px, double py, double ax, double ay, double off) { TMPC_ARITH_NO_FMA return ax * (px + ax * off) + ay * (py + ay * off); }
+    TMPC_ARITH_FN double road_offset_minus(double px, double py, double ax, double ay, double off) { TMPC_ARITH_NO_FMA return ax * (px - ax * off) + ay * (py - ay * off); }
+    /* centreline form (:191-235): rows (A, A.(P + A off_first)) and (-A, -A.(P - A off_second)) of the path's cubic c; row = (a1 a2 b) twice */
+    TMPC_ARITH_FN void road_rows_centreline(const double c[8], double t, double off_first, double off_second, double *row)
+    {
+        double px, py, ax, ay;
+        road_frame(c, t, px, py, ax, ay);
+        const double b0 = road_offset_plus(px, py, ax, ay, off_first);
+        const double b1 = road_offset_minus(px, py, ax, ay, off_second);
+        row[0] = ax; row[1] = ay; row[2] = b0;
+        row[3] = -ax; row[4] = -ay; row[5] = -b1;
+    }
+    /* bounds form (:237-262): row (-A_l, -A_l.(P_l + A_l off)) of the left bound's cubic, row (A_r, A_r.(P_r - A_r off)) of the right bound's */
+    TMPC_ARITH_FN void road_row_left_bound(const double c[8], double t, double off, double *row)
+    {
+        double px, py, ax, ay;
+        road_frame(c, t, px, py, ax, ay);
+        const double vl = road_offset_plus(px, py, ax, ay, off);
+        row[0] = -ax; row[1] = -ay; row[2] = -vl;
+    }
+    TMPC_ARITH_FN void road_row_right_bound(const double c[8], double t, double off, double *row)
+    {
+        double px, py, ax, ay;
+        road_frame(c, t, px, py, ax, ay);
+        const double vr = road_offset_minus(px, py, ax, ay, off);
+        row[0] = ax; row[1] = ay; row[2] = vr;
+    }
+
+    /* ---- window padding: column col of the row (0, 0, x'(end), X(end), 0, 0, y'(end), Y(end)), start = length, that continues a
+     * path straight along its end tangent; x, y, dx, dy = cubic() of the last segment at t = L_last ---- */
+    TMPC_ARITH_FN double padding_entry(int col, double x, double y, double dx, double dy, double length) { return col == 2 ? dx : col == 3 ? x : col == 6 ? dy : col == 7 ? y : col == 8 ? length : 0.0; }
+    /* the same for a bound cubic: eight columns, no start (written out: composed from the other, the kernel's column switch compiles differently) */
+    TMPC_ARITH_FN double padding_entry(int col, double x, double y, double dx, double dy) { return col == 2 ? dx : col == 3 ? x : col == 6 ? dy : col == 7 ? y : 0.0; }
+
+    /* ---- natural cubic spline through (t_i, y_i): Thomas recurrence on the half second derivatives m_i, m_0 = m_{n-1} = 0, no
+     * pivoting (strictly diagonally dominant).  Row i of the system: lo_i = spline_off(h_{i-1}), di_i, up_i = spline_off(h_i), r_i ---- */
+    TMPC_ARITH_FN bool spacing_valid(double h) { TMPC_ARITH_NO_FMA return h > 0.0 && h < __builtin_huge_val(); }
+    TMPC_ARITH_FN double spline_off(double h) { TMPC_ARITH_NO_FMA return h / 3.0; }
+    TMPC_ARITH_FN double spline_diag(double hm, double h) { TMPC_ARITH_NO_FMA return (2.0 * (hm + h)) / 3.0; }
+    TMPC_ARITH_FN double spline_rhs(double ym, double y0, double yp, double hm, double h) { TMPC_ARITH_NO_FMA return (yp - y0) / h - (y0 - ym) / hm; }
+    /* forward sweep, row i: (cp, g) of row i - 1 become those of row i */
+    TMPC_ARITH_FN void thomas_forward(double lo, double di, double up, double r, double &cp, double &g)
+    {
+        TMPC_ARITH_NO_FMA
+        const double den = di - lo * cp;
+        cp = up / den;
+        g = (r - lo * g) / den;
+    }
+    /* back substitution: m_i from m_{i+1} */
+    TMPC_ARITH_FN double thomas_backward(double g, double cp, double m_next) { TMPC_ARITH_NO_FMA return g - cp * m_next; }
+    /* a, c, d of ((a u + b) u + c) u + d on u = s - t_i; b = m0 */
+    TMPC_ARITH_FN void spline_row(double m0, double m1, double h, double y0, double y1, double &a, double &c, double &d)
+    {
+        TMPC_ARITH_NO_FMA
+        a = (m1 - m0) / (3.0 * h);
+        c = (y1 - y0) / h - ((2.0 * m0 + m1) * h) / 3.0;
+        d = y0;
+    }
+
+    /* ---- obstacle preparation (mpc_planner/src/data_preparation.cpp) ---- */
+    /* step k of the constant-velocity prediction, one coordinate (:58-79) */
+    TMPC_ARITH_FN double cv_step(double p, double v, double dt, int k) { TMPC_ARITH_NO_FMA return p + (v * dt) * (double)k; }
+    /* |(px, py) - (x, y)| < max_dist: removeDistantObstacles keeps the obstacle (:81-93); Contouring::isObjectiveReached with max_dist 1 */
+    TMPC_ARITH_FN bool within_distance(double px, double py, double x, double y, double max_dist)
+    {
+        TMPC_ARITH_NO_FMA
+        const double dx = px - x, dy = py - y;
+        return sqrt(dx * dx + dy * dy) < max_dist;
+    }
+    /* the selection key (:113-131) is the minimum over k < N, from SELECTION_KEY_START, of ((k + 1) 0.6) |o_k - (p + (v k) (cos psi, sin psi))|
+     * (`v k` has no dt: kept); c, s = cos psi, sin psi */
+    constexpr double SELECTION_KEY_START = 1e5;
+    TMPC_ARITH_FN double selection_key_term(int k, double ox, double oy, double x, double y, double v, double c, double s)
+    {
+        TMPC_ARITH_NO_FMA
+        const double vk = v * (double)k;
+        const double dx = ox - (x + vk * c), dy = oy - (y + vk * s);
+        return ((double)(k + 1) * 0.6) * sqrt(dx * dx + dy * dy);
+    }
+    /* propagatePredictionUncertainty (:170-186), one step of one axis: sqrt(acc^2 + (sigma dt)^2), squares written x * x */
+    TMPC_ARITH_FN double propagate_step(double acc, double sigma, double dt)
+    {
+        TMPC_ARITH_NO_FMA
+        const double s = sigma * dt;
+        return sqrt(acc * acc + s * s);
+    }
+    /* getDummyObstacle (:49-56): one coordinate of the dummy's position from the robot's */
+    TMPC_ARITH_FN double dummy_coordinate(double x) { TMPC_ARITH_NO_FMA return x + 100.0; }
+}
+#endif

@@ -2,6 +2,7 @@
 // linearisation), f-2 (cross-tick warm start), f-3 (scenario -> halfspace reduction) and the stage-function debug kernel.
 // Included by tmpc_solve.hip after the stage functions (tmpc_stage.hpp).
 #pragma once
+#include "../cpp/include/mpc_planner_types/prep_arithmetic.h"      // the data-preparation arithmetic, shared with the C++ headers
 
 namespace tmpc {
 
@@ -152,16 +153,13 @@ __global__ void tmpc_linearize_topology_kernel(Dims d, int B, const double *x0, 
 // one thread per (scene, stage).  For stage k = 1 .. N-1 of scene q (stage 0 gets nothing, :204, :247) with b = main_of[q] the batch entry
 // that stands for the scene's MAIN solver, s_k = its warm start's spline state (`_solver->getEgoPrediction(k, "spline")`, :208, :250) and the
 // path window of its parameter row of stage k (spline_x{i}_{a..d}, spline_y{i}_{a..d}, spline{i}_start):
-//   centreline mode (bounds == nullptr; :191-235): P, A = point and normal of the path at s_k,
-//       row 0 (A, A.(P + A off_first)), row 1 (-A, -A.(P - A off_second));  off_first = times half - r, off_second = half - r
-//   bounds mode (:237-262): P_l, A_l / P_r, A_r of the left / right bound spline at the same s_k -- bounds [n_scenes][2][S][8] =
-//       (ax bx cx dx ay by cy dy), on the centreline's knots (:142-149) --, off_first = off_second = r:
-//       row 0 (-A_l, -A_l.(P_l + A_l off_first)), row 1 (A_r, A_r.(P_r - A_r off_second)).
-// RosTools::Spline2D is not in the reference tree; ASSUMED: getOrthogonal(s) = (y'(s), -x'(s)) / |.| (to the right of travel:
-// the only sign for which bounds mode is a corridor between the bounds), and P, x', y' are the plain piecewise cubics of segment
-// i = max{j : start_j <= s} (0 below the first knot; the last segment's cubic continues beyond the window), no sigmoid glue.
+//   centreline mode (bounds == nullptr; :191-235): tmpc_arith::road_rows_centreline of the path at s_k; off_first = times half - r, off_second = half - r
+//   bounds mode (:237-262): road_row_left_bound / road_row_right_bound of the left / right bound spline at the same s_k -- bounds
+//       [n_scenes][2][S][8] = (ax bx cx dx ay by cy dy), on the centreline's knots (:142-149) --, off_first = off_second = r.
+// The rows are tmpc_arith's (prep_arithmetic.h: the assumptions of DESIGN.md U12 too), the source Contouring compiles as well: bit-equal to the
+// independent modules.py::road_halfspaces(_from_bounds).  The cubic is that of segment i = max{j : start_j <= s} (0 below the first knot; the
+// last segment's cubic continues beyond the window).
 // Rows first_row, first_row + 1 of stat [n_scenes][N][n_static][3] -- what tmpc_linearize_topology_kernel copies -- and nothing else.
-// No FMA contraction, the operation order of modules.py::road_halfspaces / road_halfspaces_from_bounds: bit-equal to the host mirrors.
 __global__ void tmpc_road_halfspaces_kernel(Dims d, int B, int n_scenes, const double *x0, const double *params, const int *main_of,
                                             const double *bounds, double off_first, double off_second, double *stat, int n_static, int first_row)
 {
@@ -175,33 +173,14 @@ __global__ void tmpc_road_halfspaces_kernel(Dims d, int B, int n_scenes, const d
     const double *p = params + ((size_t)b * N + k) * d.npar;
     const double s = x0[((size_t)b * (N + 1) + k) * ext_nv(d) + ZS];
     int i = 0;
-    for (int j = 0; j < S; j++) if (p[ip_spline(d, j, 8)] <= s) i = j;
+    for (int j = 0; j < S; j++) if (p[ip_spline(d, j, 8)] <= s) i = j;      // (a comparison, nothing is rounded: the kernel's own)
     const double t = s - p[ip_spline(d, i, 8)];
-    // point and unit normal of one 2-D cubic c = (ax bx cx dx ay by cy dy) at t
-    auto frame = [&](const double *c, double &px, double &py, double &ax, double &ay) {
-        px = ((c[0] * t + c[1]) * t + c[2]) * t + c[3];
-        py = ((c[4] * t + c[5]) * t + c[6]) * t + c[7];
-        const double dx = (3.0 * c[0] * t + 2.0 * c[1]) * t + c[2];
-        const double dy = (3.0 * c[4] * t + 2.0 * c[5]) * t + c[6];
-        const double n = sqrt(dx * dx + dy * dy);
-        ax = dy / n; ay = -dx / n;
-    };
     double *row = stat + (((size_t)sc * N + k) * n_static + first_row) * 3;
-    double px, py, ax, ay;
-    if (bounds == nullptr) {
-        frame(p + ip_spline(d, i, 0), px, py, ax, ay);
-        const double b0 = ax * (px + ax * off_first) + ay * (py + ay * off_first);
-        const double b1 = ax * (px - ax * off_second) + ay * (py - ay * off_second);
-        row[0] = ax; row[1] = ay; row[2] = b0;
-        row[3] = -ax; row[4] = -ay; row[5] = -b1;
-    } else {
+    if (bounds == nullptr) tmpc_arith::road_rows_centreline(p + ip_spline(d, i, 0), t, off_first, off_second, row);
+    else {
         const double *bl = bounds + (((size_t)sc * 2 + 0) * S + i) * 8, *br = bounds + (((size_t)sc * 2 + 1) * S + i) * 8;
-        frame(bl, px, py, ax, ay);
-        const double vl = ax * (px + ax * off_first) + ay * (py + ay * off_first);
-        row[0] = -ax; row[1] = -ay; row[2] = -vl;
-        frame(br, px, py, ax, ay);
-        const double vr = ax * (px - ax * off_second) + ay * (py - ay * off_second);
-        row[3] = ax; row[4] = ay; row[5] = vr;
+        tmpc_arith::road_row_left_bound(bl, t, off_first, row);
+        tmpc_arith::road_row_right_bound(br, t, off_second, row + 3);
     }
 }
 
@@ -221,7 +200,8 @@ __global__ void tmpc_road_halfspaces_kernel(Dims d, int B, int n_scenes, const d
 // Slot i's key and validity go into LDS (slots [0, count) only: the only ones read); a slot's rank is the number of smaller (key, index)
 // pairs, O(R^2) per scene, which at R <= 1024 is nothing and needs no sort network; then all lanes write the M x N prediction entries.
 // cos / sin of the device may differ from libm's in the last bits: they enter the ranking key only, never an output value.
-// No FMA contraction, the operation order of modules.py::prepare_obstacles: every output is bit-equal to the host mirror.
+// The arithmetic is tmpc_arith's, the source mpc_planner/data_preparation.h compiles too: every output is bit-equal to the independent
+// modules.py::prepare_obstacles.
 constexpr int PREP_MAX_SLOTS = 1024, PREP_THREADS = 256;
 __global__ __launch_bounds__(PREP_THREADS) void tmpc_prepare_obstacles_kernel(int N, double dt, int R, int M, const int *count, const double *state,
                                                                             const double *raw_pos, const double *raw_radius, const double *raw_vel,
@@ -248,14 +228,12 @@ __global__ __launch_bounds__(PREP_THREADS) void tmpc_prepare_obstacles_kernel(in
     for (int i = tid; i < cnt; i += PREP_THREADS) {
         const double px = rp[i * 2], py = rp[i * 2 + 1];
         bool valid = true;
-        if (max_dist > 0.0) { const double dx = px - x, dy = py - y; valid = sqrt(dx * dx + dy * dy) < max_dist; }
-        double best = 1e5;
+        if (max_dist > 0.0) valid = tmpc_arith::within_distance(px, py, x, y, max_dist);
+        double best = tmpc_arith::SELECTION_KEY_START;
         for (int k = 0; k < N; k++) {
-            const double ox = pr ? pr[((size_t)i * N + k) * 5] : px + (rv[i * 2] * dt) * (double)k;
-            const double oy = pr ? pr[((size_t)i * N + k) * 5 + 1] : py + (rv[i * 2 + 1] * dt) * (double)k;
-            const double vk = v * (double)k;
-            const double dx = ox - (x + vk * c), dy = oy - (y + vk * s);
-            const double dist = ((double)(k + 1) * 0.6) * sqrt(dx * dx + dy * dy);
+            const double ox = pr ? pr[((size_t)i * N + k) * 5] : tmpc_arith::cv_step(px, rv[i * 2], dt, k);
+            const double oy = pr ? pr[((size_t)i * N + k) * 5 + 1] : tmpc_arith::cv_step(py, rv[i * 2 + 1], dt, k);
+            const double dist = tmpc_arith::selection_key_term(k, ox, oy, x, y, v, c, s);
             if (dist < best) best = dist;
         }
         s_key[i] = best; s_valid[i] = valid ? 1 : 0;
@@ -277,9 +255,9 @@ __global__ __launch_bounds__(PREP_THREADS) void tmpc_prepare_obstacles_kernel(in
         const int m = e / N, k = e - m * N, i = s_sel[m];
         const size_t o = ((size_t)q * M + m) * N + k;
         double ox, oy, ang = 0.0, major = sigma, minor = sigma;
-        if (i < 0) { ox = x + 100.0; oy = y + 100.0; }
+        if (i < 0) { ox = tmpc_arith::dummy_coordinate(x); oy = tmpc_arith::dummy_coordinate(y); }
         else if (pr) { const double *g = pr + ((size_t)i * N + k) * 5; ox = g[0]; oy = g[1]; ang = g[2]; major = g[3]; minor = g[4]; }
-        else { ox = rp[i * 2] + (rv[i * 2] * dt) * (double)k; oy = rp[i * 2 + 1] + (rv[i * 2 + 1] * dt) * (double)k; }
+        else { ox = tmpc_arith::cv_step(rp[i * 2], rv[i * 2], dt, k); oy = tmpc_arith::cv_step(rp[i * 2 + 1], rv[i * 2 + 1], dt, k); }
         out_pos[o * 2] = ox; out_pos[o * 2 + 1] = oy;
         out_shape[o * 3] = ang;
         if (passes == 0 || !is_gaussian(i)) { out_shape[o * 3 + 1] = major; out_shape[o * 3 + 2] = minor; }     // (else: the chain below writes them)
@@ -296,9 +274,9 @@ __global__ __launch_bounds__(PREP_THREADS) void tmpc_prepare_obstacles_kernel(in
             double acc0 = 0.0, acc1 = 0.0;
             for (int k = 0; k < N; k++) {
                 double val = (i < 0 || !pr) ? sigma : pr[((size_t)i * N + k) * 5 + 3 + axis];
-                const double s0 = val * dt;
-                acc0 = sqrt(acc0 * acc0 + s0 * s0); val = acc0;
-                if (passes > 1) { const double s1 = val * dt; acc1 = sqrt(acc1 * acc1 + s1 * s1); val = acc1; }
+                const double a0 = tmpc_arith::propagate_step(acc0, val, dt);
+                acc0 = a0; val = a0;
+                if (passes > 1) { const double a1 = tmpc_arith::propagate_step(acc1, val, dt); acc1 = a1; val = a1; }
                 out_shape[(((size_t)q * M + m) * N + k) * 3 + 1 + axis] = val;
             }
         }
@@ -346,64 +324,9 @@ __global__ void tmpc_set_obstacle_parameters_kernel(Dims d, int B, double *param
 }
 
 // ---- Contouring::update on a whole reference path (contouring.cpp:28-48, setSplineParameters :94-124) ---------------------------------------
-// RosTools::Spline2D::findClosestPoint is not in the reference tree: restated, assumptions in DESIGN.md U14.  No FMA contraction, the operation
-// order of modules.py::closest_point_on_segment / find_closest_point / path_window: every output is bit-equal to the host mirror.
-constexpr int PATH_MAX_SEGMENTS = 1024, PATH_COARSE = 8, PATH_BISECTIONS = 40;
-
-// point and derivative of one 2-D cubic c = (ax bx cx dx ay by cy dy) at t: the Horner forms of the road kernel's `frame`
-__device__ inline void path_cubic(const double *c, double t, double &x, double &y, double &dx, double &dy)
-{
-#pragma clang fp contract(off)
-    x = ((c[0] * t + c[1]) * t + c[2]) * t + c[3];
-    y = ((c[4] * t + c[5]) * t + c[6]) * t + c[7];
-    dx = (3.0 * c[0] * t + 2.0 * c[1]) * t + c[2];
-    dy = (3.0 * c[4] * t + 2.0 * c[5]) * t + c[6];
-}
-
-// closest point of the cubic on t in [0, L] to (px, py): D = |P(t) - p|^2, g = (P(t) - p).P'(t).  Nine coarse samples t_j = L (j / 8), the
-// bracket around the best (lowest j on ties), an end of the bracket if g does not change sign inside it, else exactly 40 bisections (no
-// data-dependent exit) and the bracket's midpoint; the coarse sample wins if its D is strictly smaller.
-__device__ inline void path_closest_on_segment(const double *cg, double L, double px, double py, double &D_out, double &t_out)
-{
-#pragma clang fp contract(off)
-    double c[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) c[i] = cg[i];
-    auto eval = [&](double t, double &g) {
-#pragma clang fp contract(off)
-        double x, y, dx, dy;
-        path_cubic(c, t, x, y, dx, dy);
-        const double ex = x - px, ey = y - py;
-        g = ex * dx + ey * dy;
-        return ex * ex + ey * ey;
-    };
-    double g;
-    int js = 0;
-    double Dj = eval(L * (0.0 / 8.0), g);
-    for (int j = 1; j <= PATH_COARSE; j++) {
-        const double Dc = eval(L * ((double)j / 8.0), g);
-        if (Dc < Dj) { js = j; Dj = Dc; }
-    }
-    double lo = L * ((double)(js > 0 ? js - 1 : 0) / 8.0), hi = L * ((double)(js < PATH_COARSE ? js + 1 : PATH_COARSE) / 8.0);
-    double tc;
-    eval(lo, g);
-    if (g >= 0.0) tc = lo;
-    else {
-        eval(hi, g);
-        if (g <= 0.0) tc = hi;
-        else {
-            for (int it = 0; it < PATH_BISECTIONS; it++) {
-                const double mid = 0.5 * (lo + hi);
-                eval(mid, g);
-                if (g > 0.0) hi = mid; else lo = mid;
-            }
-            tc = 0.5 * (lo + hi);
-        }
-    }
-    const double Dc = eval(tc, g);
-    if (Dj < Dc) { D_out = Dj; t_out = L * ((double)js / 8.0); }
-    else { D_out = Dc; t_out = tc; }
-}
+// RosTools::Spline2D::findClosestPoint is not in the reference tree: restated, assumptions in DESIGN.md U14.  The arithmetic is tmpc_arith's, the
+// source mpc_planner_modules/reference_path.h compiles too: every output is bit-equal to the independent modules.py::track_path.
+constexpr int PATH_MAX_SEGMENTS = 1024;
 
 // one wave per scene q; lane l takes the candidate segments first + l, first + l + 64, ... (a local search has at most 63 candidates: one per
 // lane).  segment[q] < 0: every segment of the path is a candidate; otherwise [max(0, prev - R), min(n - 1, prev + R)], prev clamped into
@@ -440,7 +363,7 @@ __global__ __launch_bounds__(64) void tmpc_track_path_kernel(int S, int n_seg_ma
         const double *c = pq + (size_t)i * 9;
         const double L = (i + 1 < n ? pq[(size_t)(i + 1) * 9 + 8] : len) - c[8];
         double D, t;
-        path_closest_on_segment(c, L, px, py, D, t);
+        tmpc_arith::closest_on_segment(c, L, px, py, D, t);
         if (i == first) { D_first = D; t_first = t; }
         if (D == D && (bi < 0 || D < bD)) { bD = D; bt = t; bi = i; }
     }
@@ -455,29 +378,29 @@ __global__ __launch_bounds__(64) void tmpc_track_path_kernel(int S, int n_seg_ma
     // the end of the path: its last cubic at t = L_last
     const double L_last = len - pq[(size_t)(n - 1) * 9 + 8];
     double ex, ey, edx, edy;
-    path_cubic(pq + (size_t)(n - 1) * 9, L_last, ex, ey, edx, edy);
+    tmpc_arith::cubic(pq + (size_t)(n - 1) * 9, L_last, ex, ey, edx, edy);
     if (lane == 0) {
         segment[q] = bi;
         closest_s[q] = pq[(size_t)bi * 9 + 8] + bt;
-        if (reached) { const double rx = ex - px, ry = ey - py; reached[q] = sqrt(rx * rx + ry * ry) < 1.0 ? 1 : 0; }     // isObjectiveReached, :167-175
+        if (reached) reached[q] = tmpc_arith::within_distance(ex, ey, px, py, 1.0) ? 1 : 0;                               // isObjectiveReached, :167-175
     }
     for (int e = lane; e < S * 9; e += 64) {
         const int w = e / 9, col = e - w * 9, i = bi + w;
         double v;
         if (i < n) v = pq[(size_t)i * 9 + col];
-        else v = col == 2 ? edx : col == 3 ? ex : col == 6 ? edy : col == 7 ? ey : col == 8 ? len : 0.0;
+        else v = tmpc_arith::padding_entry(col, ex, ey, edx, edy, len);
         window[((size_t)q * S + w) * 9 + col] = v;
     }
     if (bounds && bound_window)
         for (int side = 0; side < 2; side++) {
             const double *bq = bounds + ((size_t)q * 2 + side) * n_seg_max * 8;
             double bx, by, bdx, bdy;
-            path_cubic(bq + (size_t)(n - 1) * 8, L_last, bx, by, bdx, bdy);
+            tmpc_arith::cubic(bq + (size_t)(n - 1) * 8, L_last, bx, by, bdx, bdy);
             for (int e = lane; e < S * 8; e += 64) {
                 const int w = e >> 3, col = e & 7, i = bi + w;
                 double v;
                 if (i < n) v = bq[(size_t)i * 8 + col];
-                else v = col == 2 ? bdx : col == 3 ? bx : col == 6 ? bdy : col == 7 ? by : 0.0;
+                else v = tmpc_arith::padding_entry(col, bx, by, bdx, bdy);
                 bound_window[(((size_t)q * 2 + side) * S + w) * 8 + col] = v;
             }
         }
@@ -505,8 +428,8 @@ __global__ void tmpc_set_path_parameters_kernel(Dims d, int B, double *params, c
 
 // ---- waypoints -> cubic segments: Contouring::onDataReceived (contouring.cpp:126-157), PathReferenceVelocity::onDataReceived -----------------
 // (path_reference_velocity.cpp:28-40).  RosTools::Spline2D and tk::spline are not in the reference tree: the natural cubic spline is restated
-// as DESIGN.md U15.  No FMA contraction, the operation order of modules.py::path_knots / fit_cubic / fit_path: every output is bit-equal to
-// the host mirror.
+// as DESIGN.md U15.  The rows and Thomas steps are tmpc_arith's, the source ReferencePathSpline::fitCubic compiles too: every output is bit-equal
+// to the independent modules.py::path_knots / fit_cubic / fit_path.
 constexpr int FIT_MAX_POINTS = 1025, FIT_CHUNK = 8;
 
 // one curve of a scene: n values `stride_in` doubles apart, and its (a b c d) columns in rows `stride_out` doubles apart
@@ -567,7 +490,7 @@ __global__ __launch_bounds__(64) void tmpc_fit_path_kernel(int n_pts_max, int n_
     bool bad = false;
     for (int i = lane; i < n - 1; i += 64) {
         const double h = s_t[i + 1] - s_t[i];
-        if (!(h > 0.0 && h < __builtin_huge_val())) bad = true;
+        if (!tmpc_arith::spacing_valid(h)) bad = true;
         s_h[i] = h;
     }
     if (__syncthreads_or(bad ? 1 : 0)) {
@@ -586,15 +509,15 @@ __global__ __launch_bounds__(64) void tmpc_fit_path_kernel(int n_pts_max, int n_
         }
     }
     for (int i = lane; i < n - 1; i += 64) {
-        s_up[i] = s_h[i] / 3.0;
-        if (i >= 1) s_di[i] = (2.0 * (s_h[i - 1] + s_h[i])) / 3.0;
+        s_up[i] = tmpc_arith::spline_off(s_h[i]);
+        if (i >= 1) s_di[i] = tmpc_arith::spline_diag(s_h[i - 1], s_h[i]);
         path[((size_t)q * n_seg_max + i) * 9 + 8] = s_t[i];
     }
     for (int k = 0; k < K; k++) {
         const FitCurve c = fit_curve(k, q, n_pts_max, n_seg_max, xy, left_xy, right_xy, v_in, path, bounds, velocity);
         for (int i = 1 + lane; i <= n - 2; i += 64) {
             const double ym = c.in[(size_t)(i - 1) * c.stride_in], y0 = c.in[(size_t)i * c.stride_in], yp = c.in[(size_t)(i + 1) * c.stride_in];
-            c.out[(size_t)i * c.stride_out + 1] = (yp - y0) / s_h[i] - (y0 - ym) / s_h[i - 1];
+            c.out[(size_t)i * c.stride_out + 1] = tmpc_arith::spline_rhs(ym, y0, yp, s_h[i - 1], s_h[i]);
         }
     }
     __syncthreads();
@@ -602,7 +525,7 @@ __global__ __launch_bounds__(64) void tmpc_fit_path_kernel(int n_pts_max, int n_
     double *bcol = mine.out + 1;
     const size_t so = (size_t)mine.stride_out;
     if (lane < K) {
-        double cp = 0.0, g = 0.0;
+        double g = 0.0, cp = 0.0;
         for (int i0 = 1; i0 <= n - 2; i0 += FIT_CHUNK) {
             double r[FIT_CHUNK];
 #pragma unroll
@@ -611,10 +534,7 @@ __global__ __launch_bounds__(64) void tmpc_fit_path_kernel(int n_pts_max, int n_
             for (int j = 0; j < FIT_CHUNK; j++) {
                 const int i = i0 + j;
                 if (i <= n - 2) {
-                    const double lo = s_up[i - 1];
-                    const double den = s_di[i] - lo * cp;
-                    cp = s_up[i] / den;
-                    g = (r[j] - lo * g) / den;
+                    tmpc_arith::thomas_forward(s_up[i - 1], s_di[i], s_up[i], r[j], cp, g);
                     bcol[(size_t)i * so] = g;
                     if (lane == 0) s_cp[i] = cp;
                 }
@@ -631,7 +551,7 @@ __global__ __launch_bounds__(64) void tmpc_fit_path_kernel(int n_pts_max, int n_
 #pragma unroll
             for (int j = 0; j < FIT_CHUNK; j++) {
                 const int i = i0 - j;
-                if (i >= 1) { m = gg[j] - s_cp[i] * m; bcol[(size_t)i * so] = m; }
+                if (i >= 1) { m = tmpc_arith::thomas_backward(gg[j], s_cp[i], m); bcol[(size_t)i * so] = m; }
             }
         }
         bcol[0] = 0.0;                                                   // m_0
@@ -643,9 +563,7 @@ __global__ __launch_bounds__(64) void tmpc_fit_path_kernel(int n_pts_max, int n_
             double *o = c.out + (size_t)i * c.stride_out;
             const double m0 = o[1], m1 = i + 1 < n - 1 ? o[c.stride_out + 1] : 0.0, h = s_h[i];
             const double y0 = c.in[(size_t)i * c.stride_in], y1 = c.in[(size_t)(i + 1) * c.stride_in];
-            o[0] = (m1 - m0) / (3.0 * h);
-            o[2] = (y1 - y0) / h - ((2.0 * m0 + m1) * h) / 3.0;
-            o[3] = y0;
+            tmpc_arith::spline_row(m0, m1, h, y0, y1, o[0], o[2], o[3]);
         }
     }
 }

@@ -473,6 +473,27 @@ struct tmpc_handle {
         }                                                                                           \
     } while (0)
 
+// the entry points that write the hand-written kernels' parameter layout refuse in a generated solver, whose layout is the module stack's
+#ifdef TMPC_GENERATED_STAGE
+#define TMPC_NOT_IN_GENERATED_SOLVER(h, name) \
+    do { if (h) (h)->err = name ": not available in a generated solver (its parameter layout is the module stack's)"; return TMPC_ERR_INVALID; } while (0)
+#else
+#define TMPC_NOT_IN_GENERATED_SOLVER(h, name) do { } while (0)
+#endif
+
+// An options struct of the C-ABI (its first field: uint32_t size).  `o` holds the defaults and keeps them when the caller passes NULL; like
+// tmpc_create_v2, the caller's struct may be longer (a newer header) only with a zero tail, and there is no shorter revision.
+template <class Options> static bool read_options(tmpc_handle *h, const char *fn, const char *type, const Options *options, Options &o)
+{
+    if (!options) return true;
+    if (options->size < sizeof(o)) { h->err = std::string(fn) + ": options->size is smaller than " + type; return false; }
+    const unsigned char *tail = reinterpret_cast<const unsigned char *>(options);
+    for (uint32_t i = sizeof(o); i < options->size; i++)
+        if (tail[i]) { h->err = std::string(fn) + ": options holds a non-zero field this library does not know"; return false; }
+    o = *options;
+    return true;
+}
+
 namespace {
 // Scratch device buffers / events of the diagnostic entry points: released on every return path.
 struct DevBufs {
@@ -1223,10 +1244,7 @@ int tmpc_linearize_topology_ex(tmpc_handle *h, const void *d_obstacle_pos, int32
                                const void *d_static_halfspaces, int32_t n_static, const void *d_scene_of, const void *d_state_x,
                                double robot_radius, const void *d_is_original)
 {
-#ifdef TMPC_GENERATED_STAGE
-    if (h) h->err = "tmpc_linearize_topology: not available in a generated solver (its parameter layout is the module stack's)";
-    return TMPC_ERR_INVALID;
-#endif
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_linearize_topology");
     if (!h || h->B <= 0 || !h->params || !d_scene_of || !d_state_x || h->d.n_lin <= 0 || n_obstacles < 0 || n_static < 0 ||
         n_obstacles + n_static > h->d.n_lin || (n_obstacles > 0 && !d_obstacle_pos) || (n_static > 0 && !d_static_halfspaces)) {
         if (h) h->err = "tmpc_linearize_topology: bad argument / no batch / more obstacle + static rows than the problem's topology rows";
@@ -1252,10 +1270,7 @@ int tmpc_linearize_topology(tmpc_handle *h, const void *d_obstacle_pos, const vo
 int tmpc_road_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scenes, const void *d_bound_segments, double offset_first,
                          double offset_second, void *d_static_halfspaces, int32_t n_static, int32_t first_row)
 {
-#ifdef TMPC_GENERATED_STAGE
-    if (h) h->err = "tmpc_road_halfspaces: not available in a generated solver (its parameter layout is the module stack's)";
-    return TMPC_ERR_INVALID;
-#endif
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_road_halfspaces");
     if (!h) return TMPC_ERR_INVALID;
     if (h->B <= 0 || !h->x0 || !h->params) { h->err = "tmpc_road_halfspaces: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
     if (!d_main_of || !d_static_halfspaces || n_scenes <= 0) { h->err = "tmpc_road_halfspaces: bad argument (d_main_of, d_static_halfspaces, n_scenes > 0)"; return TMPC_ERR_INVALID; }
@@ -1276,21 +1291,11 @@ int tmpc_prepare_obstacles(tmpc_handle *h, int32_t n_scenes, int32_t n_slots, in
                            const tmpc_obstacle_options *options, void *d_obstacle_pos, void *d_obstacle_shape, void *d_obstacle_radius,
                            void *d_obstacle_gaussian, void *d_selected)
 {
-#ifdef TMPC_GENERATED_STAGE
-    if (h) h->err = "tmpc_prepare_obstacles: not available in a generated solver (its parameter layout is the module stack's)";
-    return TMPC_ERR_INVALID;
-#endif
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_prepare_obstacles");
     if (!h) return TMPC_ERR_INVALID;
     tmpc_obstacle_options o{};                                        // NULL: the defaults (deterministic, no passes, no distance filter)
     o.size = sizeof(o); o.noise = 0.3;
-    if (options) {
-        // like tmpc_create_v2: the caller's struct may be longer (a newer header) only with a zero tail; there is no shorter revision
-        if (options->size < sizeof(o)) { h->err = "tmpc_prepare_obstacles: options->size is smaller than tmpc_obstacle_options"; return TMPC_ERR_INVALID; }
-        const unsigned char *tail = reinterpret_cast<const unsigned char *>(options);
-        for (uint32_t i = sizeof(o); i < options->size; i++)
-            if (tail[i]) { h->err = "tmpc_prepare_obstacles: options holds a non-zero field this library does not know"; return TMPC_ERR_INVALID; }
-        o = *options;
-    }
+    if (!read_options(h, "tmpc_prepare_obstacles", "tmpc_obstacle_options", options, o)) return TMPC_ERR_INVALID;
     if (n_scenes <= 0) { h->err = "tmpc_prepare_obstacles: n_scenes must be positive"; return TMPC_ERR_INVALID; }
     if (n_slots < 0 || n_slots > tmpc::PREP_MAX_SLOTS) { h->err = "tmpc_prepare_obstacles: 0 <= n_slots <= 1024"; return TMPC_ERR_INVALID; }
     if (max_obstacles <= 0 || max_obstacles > 4096) { h->err = "tmpc_prepare_obstacles: 1 <= max_obstacles <= 4096"; return TMPC_ERR_INVALID; }
@@ -1315,10 +1320,7 @@ int tmpc_set_obstacle_parameters(tmpc_handle *h, const void *d_obstacle_pos, con
                                  const void *d_obstacle_gaussian, const void *d_scene_of, const void *d_state, double robot_radius,
                                  double disc_offset, double risk, double chi, double obstacle_radius)
 {
-#ifdef TMPC_GENERATED_STAGE
-    if (h) h->err = "tmpc_set_obstacle_parameters: not available in a generated solver (its parameter layout is the module stack's)";
-    return TMPC_ERR_INVALID;
-#endif
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_set_obstacle_parameters");
     if (!h) return TMPC_ERR_INVALID;
     if (h->B <= 0 || !h->params) { h->err = "tmpc_set_obstacle_parameters: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
     if (h->d.M <= 0) { h->err = "tmpc_set_obstacle_parameters: the problem has no obstacle rows (M = 0)"; return TMPC_ERR_INVALID; }
@@ -1340,21 +1342,11 @@ int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const v
                     const void *d_bounds, const void *d_pos, int32_t pos_stride, const tmpc_path_options *options, void *d_segment,
                     void *d_closest_s, void *d_window, void *d_bound_window, void *d_reached)
 {
-#ifdef TMPC_GENERATED_STAGE
-    if (h) h->err = "tmpc_track_path: not available in a generated solver (its parameter layout is the module stack's)";
-    return TMPC_ERR_INVALID;
-#endif
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_track_path");
     if (!h) return TMPC_ERR_INVALID;
     tmpc_path_options o{};                                            // NULL: the defaults (search_range 2)
     o.size = sizeof(o); o.search_range = 2;
-    if (options) {
-        // like tmpc_obstacle_options: the caller's struct may be longer (a newer header) only with a zero tail; there is no shorter revision
-        if (options->size < sizeof(o)) { h->err = "tmpc_track_path: options->size is smaller than tmpc_path_options"; return TMPC_ERR_INVALID; }
-        const unsigned char *tail = reinterpret_cast<const unsigned char *>(options);
-        for (uint32_t i = sizeof(o); i < options->size; i++)
-            if (tail[i]) { h->err = "tmpc_track_path: options holds a non-zero field this library does not know"; return TMPC_ERR_INVALID; }
-        o = *options;
-    }
+    if (!read_options(h, "tmpc_track_path", "tmpc_path_options", options, o)) return TMPC_ERR_INVALID;
     if (n_scenes <= 0) { h->err = "tmpc_track_path: n_scenes must be positive"; return TMPC_ERR_INVALID; }
     if (n_seg_max < 1 || n_seg_max > tmpc::PATH_MAX_SEGMENTS) { h->err = "tmpc_track_path: 1 <= n_seg_max <= 1024"; return TMPC_ERR_INVALID; }
     if (o.search_range < 0 || o.search_range > 31) { h->err = "tmpc_track_path: 0 <= search_range <= 31"; return TMPC_ERR_INVALID; }
@@ -1373,10 +1365,7 @@ int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const v
 
 int tmpc_set_path_parameters(tmpc_handle *h, const void *d_window, const void *d_scene_of, int32_t n_scenes, const void *d_closest_s, void *d_state)
 {
-#ifdef TMPC_GENERATED_STAGE
-    if (h) h->err = "tmpc_set_path_parameters: not available in a generated solver (its parameter layout is the module stack's)";
-    return TMPC_ERR_INVALID;
-#endif
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_set_path_parameters");
     if (!h) return TMPC_ERR_INVALID;
     if (h->B <= 0 || !h->params) { h->err = "tmpc_set_path_parameters: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
     if (h->d.S <= 0) { h->err = "tmpc_set_path_parameters: the problem has no path segments (S = 0)"; return TMPC_ERR_INVALID; }
@@ -1418,10 +1407,7 @@ int tmpc_fit_path(tmpc_handle *h, int32_t n_scenes, int32_t n_pts_max, int32_t n
 int tmpc_scenario_halfspaces(tmpc_handle *h, const void *d_samples, int32_t n_pts, int32_t n_rows, const void *d_scene_of,
                              const void *d_state_x, double radius, double disc_offset)
 {
-#ifdef TMPC_GENERATED_STAGE
-    if (h) h->err = "tmpc_scenario_halfspaces: not available in a generated solver (its parameter layout is the module stack's)";
-    return TMPC_ERR_INVALID;
-#endif
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_scenario_halfspaces");
     if (!h || h->B <= 0 || !h->params || !d_samples || !d_scene_of || !d_state_x || n_pts <= 0 || n_rows <= 0 || n_rows > 64 ||
         n_rows > h->d.n_slk) {
         if (h) h->err = "tmpc_scenario_halfspaces: bad argument / no batch / more rows than the problem's slack rows";

@@ -113,7 +113,7 @@ def _road_segment_eval(coef, starts, s):
     """Point and derivative of the plain piecewise cubic at s (DESIGN.md U12, assumption 2): the segment i = max{j : start_j <= s}
     (i = 0 below the first knot; beyond the last knot the last segment's cubic continues), t = s - start_i, Horner form -- no sigmoid
     glue, that belongs to the NLP's spline.  coef [S][8] = (ax bx cx dx ay by cy dy); starts [S].  Same operation order as
-    tmpc_road_halfspaces_kernel and the C++ Contouring::evaluateSegments."""
+    tmpc_arith::road_frame, which tmpc_road_halfspaces_kernel and the C++ Contouring compile."""
     i = 0
     for j in range(len(starts)):
         if starts[j] <= s:

@@ -23,7 +23,8 @@ N, M, S = 20, 8, 5
 def _build_header_only():
     """No generated header, no HIP, no library: the header stands alone."""
     os.makedirs(os.path.dirname(BIN), exist_ok=True)
-    if not os.path.exists(BIN) or os.path.getmtime(BIN) < max(os.path.getmtime(SRC), os.path.getmtime(os.path.join(CPP, "include", "mpc_planner_modules", "reference_path.h"))):
+    headers = [os.path.join(CPP, "include", "mpc_planner_modules", "reference_path.h"), os.path.join(CPP, "include", "mpc_planner_types", "prep_arithmetic.h")]
+    if not os.path.exists(BIN) or os.path.getmtime(BIN) < max(os.path.getmtime(f) for f in [SRC] + headers):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-I", os.path.join(CPP, "include"), SRC, "-o", BIN])
 
 
