@@ -93,12 +93,23 @@ struct Lds {
 
 // ---- sparse [B A] (compact kernels) ------------------------------------------------------------------------------
 // For the unicycle [B A] (5 x 7) has 8 stage-dependent entries (dyn8, tmpc_riccati.hpp) and constants 0, 1, dt, dt^2/2.  `tab` =
-// dyn8[N][8] followed by 20 constants; an entry is addressed by a 4-bit code: 0..7 = dyn8 entry of the stage, 8..13 = 0, 1, dt,
-// dt^2/2 and the spline row's own (sdt, shdt2) -- (dt, dt^2/2) for the contouring model, (0, 0) for SecondOrderUnicycleModel, whose fifth
-// state slot is inert (Dims::model).  The last 12 constants are rows psi, v, s of [B A] in dyn8 column order (a, w, psi, v) for the forward sweep.
+// dyn8[N][8] followed by 20 constants; an entry is addressed by a 4-bit code: 0..7 = dyn8 entry of the stage, 8..12 = 1, the
+// spline row's own (sdt, shdt2) -- (dt, dt^2/2) for the contouring model, (0, 0) for SecondOrderUnicycleModel, whose fifth
+// state slot is inert (Dims::model) --, 0 and dt.
 // Reading [B A] through the table returns exactly the values the dense copy held (zeros and ones included), so every sum that
 // runs over a row or column of [B A] keeps its operation order: results are bitwise those of the dense layout.
-constexpr int BAC_0 = 8, BAC_1 = 9, BAC_DT = 10, BAC_H = 11, BAC_SDT = 12, BAC_SH = 13, BA_NGROUP0 = 8, BA_NCONST = 20;
+// The 20 constants are ORDERED so that the sequential loops reach what a lane needs of a stage with the fewest LDS instructions
+// (each is one instruction whatever the lane count): dyn8 holds a column's (X, Y) entries next to each other, and the constants hold
+//   * rows psi, v, s of [B A] in dyn8 column order (a, w, psi, v) at stride 2 like rows x, y in dyn8 (forward sweep: BAR_*),
+//   * a column's entries of rows x, y next to each other (columns x, y, s: BAP_*), like the (X, Y) pair of the other columns in dyn8,
+//   * a column's entries of rows psi, v, s next to each other (BAT_*),
+// all overlapping in 20 slots (no LDS was free for a longer table):
+//   index    0  1    2   3  4   5   6   7  8  9  10  11   12  13  14  15  16  17  18  19
+//   value    1  sdt  sh  0  dt  sh  dt  0  0  0  1   sdt  0   dt  dt  0   1   0   0   1
+constexpr int BAC_1 = 8, BAC_SDT = 9, BAC_SH = 10, BAC_0 = 11, BAC_DT = 12, BA_NCONST = 20;
+constexpr int BAR_S = 5, BAR_PSI = 12, BAR_V = 13;                                      // rows s, psi, v: (a, w, psi, v) at +0, +2, +4, +6
+constexpr int BAP_X = 16, BAP_Y = 15, BAP_S = 7;                                        // columns x, y, s: rows (x, y) at +0, +1
+constexpr int BAT_A = 3, BAT_W = 6, BAT_XY = 7, BAT_PSI = 16, BAT_V = 9, BAT_S = 17;    // columns: rows (psi, v, s) at +0, +1, +2
 constexpr unsigned ba_pack(int a, int w, int x, int y, int p, int v, int s_)
 {
     return (unsigned)a | (unsigned)w << 4 | (unsigned)x << 8 | (unsigned)y << 12 | (unsigned)p << 16 | (unsigned)v << 20 | (unsigned)s_ << 24;
@@ -106,8 +117,8 @@ constexpr unsigned ba_pack(int a, int w, int x, int y, int p, int v, int s_)
 // row m of [B A]: codes of its 7 columns (a, w, x, y, psi, v, s)
 __device__ __forceinline__ constexpr unsigned ba_rowcode(int m)
 {
-    return m == 0 ? ba_pack(0, 1, BAC_1, BAC_0, 2, 3, BAC_0)
-         : m == 1 ? ba_pack(4, 5, BAC_0, BAC_1, 6, 7, BAC_0)
+    return m == 0 ? ba_pack(0, 2, BAC_1, BAC_0, 4, 6, BAC_0)            // (dyn8 order: Xa Ya Xw Yw Xp Yp Xv Yv, tmpc_riccati.hpp)
+         : m == 1 ? ba_pack(1, 3, BAC_0, BAC_1, 5, 7, BAC_0)
          : m == 2 ? ba_pack(BAC_0, BAC_DT, BAC_0, BAC_0, BAC_1, BAC_0, BAC_0)
          : m == 3 ? ba_pack(BAC_DT, BAC_0, BAC_0, BAC_0, BAC_0, BAC_1, BAC_0)
                   : ba_pack(BAC_SH, BAC_0, BAC_0, BAC_0, BAC_0, BAC_SDT, BAC_1);
@@ -122,9 +133,8 @@ __device__ __forceinline__ int ba_off(int N, int k, int m, int j)
 __device__ __forceinline__ void ba_tab_init(double *tab, const Dims &d, int tid)
 {
     if (tid < BA_NCONST) {
-        const double dt = d.dt, h = d.hdt2, sdt = d.sdt, sh = d.shdt2;
-        //                          0    1    dt  h  sdt  sh  (pad)     | psi: a  w   psi  v  | v: a   w    psi  v  | s: a   w    psi  v
-        const double c[BA_NCONST] = {0.0, 1.0, dt, h, sdt, sh, 0.0, 0.0,   0.0, dt, 1.0, 0.0,   dt, 0.0, 0.0, 1.0,   sh, 0.0, 0.0, sdt};
+        const double dt = d.dt, sdt = d.sdt, sh = d.shdt2;
+        const double c[BA_NCONST] = {1.0, sdt, sh, 0.0, dt,   sh, dt, 0.0, 0.0, 0.0, 1.0, sdt,   0.0, dt, dt, 0.0, 1.0, 0.0, 0.0, 1.0};
         double val = 0.0;
 #pragma unroll
         for (int i = 0; i < BA_NCONST; i++) if (i == tid) val = c[i];

@@ -83,7 +83,7 @@ __host__ __device__ inline Layout make_layout(const Dims &d)
 }
 __host__ __device__ inline size_t block_doubles(const Layout &L) { return (size_t)L.lane_doubles * LW; }
 
-enum { D8_XA = 0, D8_XW, D8_XP, D8_XV, D8_YA, D8_YW, D8_YP, D8_YV };     // same order as the wave kernels' dyn8
+enum { D8_XA = 0, D8_XW, D8_XP, D8_XV, D8_YA, D8_YW, D8_YP, D8_YV };     // this family's own order (the wave kernels interleave X and Y: tmpc_riccati.hpp)
 
 struct Result { double pobj, res_eq; int exit_code, qp_status, sqp_iter, qp_iter; };
 

@@ -96,25 +96,28 @@ __device__ __forceinline__ bool chol_rows(double (&f)[NV], int lane, double *r0,
     return bad;
 }
 
-// dyn8[k] = (Xa, Xw, Xp, Xv, Ya, Yw, Yp, Yv): the only non-constant entries of [B A] for the unicycle
-// (tmpc_stage.hpp dyn_jacobian); the rest is identity / dt / dt^2/2.
-enum { D8_XA = 0, D8_XW, D8_XP, D8_XV, D8_YA, D8_YW, D8_YP, D8_YV };
+// dyn8[k] = (Xa, Ya, Xw, Yw, Xp, Yp, Xv, Yv): the only non-constant entries of [B A] for the unicycle
+// (tmpc_stage.hpp dyn_jacobian); the rest is identity / dt / dt^2/2.  A column's two entries are neighbours (one two-double load per
+// lane in the sequential loops), a row's four are at stride 2.
+enum { D8_XA = 0, D8_YA, D8_XW, D8_YW, D8_XP, D8_YP, D8_XV, D8_YV };
 
 // Compact layout (no dense [B A] in LDS): a lane's column / row of [B A] through the table `tab` (ba_off, tmpc_solve.hip).
-// Column j: entries 0, 1 are stage-dependent for j in {a, w, psi, v} (offset o + 8 k) and constants otherwise (stride 0); entries
-// 2..4 are constants for every column.  Row i (state index) in dyn8 column order (a, w, psi, v): stage-dependent for x, y.
+// Column j: entries 0, 1 are stage-dependent for j in {a, w, psi, v} (offset o0 + 8 k) and constants otherwise (stride 0), neighbours in
+// the table either way (o0, o0 + 1); entries 2..4 are constants for every column, neighbours too (o1, o1 + 1, o1 + 2).
+// Row i (state index) in dyn8 column order (a, w, psi, v) at o0, o0 + 2, o0 + 4, o0 + 6: stage-dependent for x, y.
 struct BaLane { int o0, o1, st; };
 __device__ __forceinline__ BaLane ba_column(int N, int j)
 {
     BaLane c;
-    c.o0 = ba_off(N, 0, 0, j); c.o1 = ba_off(N, 0, 1, j);
+    c.o0 = j == ZA ? D8_XA : j == ZW ? D8_XW : j == ZPSI ? D8_XP : j == ZV ? D8_XV : N * 8 + (j == ZX ? BAP_X : j == ZY ? BAP_Y : BAP_S);
+    c.o1 = N * 8 + (j == ZA ? BAT_A : j == ZW ? BAT_W : j == ZPSI ? BAT_PSI : j == ZV ? BAT_V : j == ZS ? BAT_S : BAT_XY);
     c.st = c.o0 < 8 ? 8 : 0;
     return c;
 }
-__device__ __forceinline__ BaLane ba_row4(int N, int i5)          // o0: base of (b_a, b_w, a_psi, a_v) of row i5
+__device__ __forceinline__ BaLane ba_row4(int N, int i5)          // o0: base of (b_a, b_w, a_psi, a_v) of row i5, at stride 2
 {
     BaLane c;
-    c.o0 = i5 < 2 ? 4 * i5 : N * 8 + BA_NGROUP0 + 4 * (i5 - 2); c.o1 = 0;
+    c.o0 = i5 < 2 ? i5 : N * 8 + (i5 == 2 ? BAR_PSI : i5 == 3 ? BAR_V : BAR_S); c.o1 = 0;
     c.st = i5 < 2 ? 8 : 0;
     return c;
 }
@@ -182,10 +185,14 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
     int bo[NX], bst[NX];
     if constexpr (VEC) {
         hrow = vec ? L.gh : L.Hh + pidx(ls, 0);       // (row start inside a stage's block; the block's offset is added per stage: hoff<CP>)
+        if constexpr (CP) {
+            // the table keeps a column's entries of rows x, y and of rows psi, v, s next to each other, as rb is: two bases per lane, three loads
+            // (2 + 2 + 1 doubles) where five bases took five
+            bo[0] = vec ? (int)(L.rb - L.tab) : bc.o0; bst[0] = vec ? NX : bc.st;
+            bo[2] = vec ? (int)(L.rb - L.tab) + 2 : bc.o1; bst[2] = vec ? NX : 0;
+        } else {
 #pragma unroll
-        for (int m = 0; m < NX; m++) {
-            if constexpr (CP) { bo[m] = vec ? (int)(L.rb - L.tab) + m : ba_off(N, 0, m, ls); bst[m] = vec ? NX : (bo[m] < 8 ? 8 : 0); }
-            else { bo[m] = vec ? (int)(L.rb - L.BA) + m : m * NV + ls; bst[m] = vec ? NX : NX * NV; }
+            for (int m = 0; m < NX; m++) { bo[m] = vec ? (int)(L.rb - L.BA) + m : m * NV + ls; bst[m] = vec ? NX : NX * NV; }
         }
     }
     // (load_stage reads stage k, then k - 1, ...; the last call re-loads stage 0)
@@ -195,14 +202,19 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
             const double *hr = hrow + (vec ? k * NV : hoff<CP>(k));          // (two wave-uniform offsets, one select per stage)
 #pragma unroll
             for (int j = 0; j < NV; j++) o.hk[j] = hr[j];
+            if constexpr (CP) {
+                const double *T0 = bbase + bo[0] + mul24(k, bst[0]), *T2 = bbase + bo[2] + mul24(k, bst[2]);
+                o.ba[0] = T0[0]; o.ba[1] = T0[1]; o.ba[2] = T2[0]; o.ba[3] = T2[1]; o.ba[4] = T2[2];
+            } else {
 #pragma unroll
-            for (int m = 0; m < NX; m++) o.ba[m] = bbase[bo[m] + mul24(k, bst[m])];
+                for (int m = 0; m < NX; m++) o.ba[m] = bbase[bo[m] + mul24(k, bst[m])];
+            }
         } else {
             const double *Hk = L.Hh + hoff<CP>(k);
 #pragma unroll
             for (int j = 0; j < NV; j++) o.hk[j] = Hk[pidx(ls, j <= ls ? j : ls)];
             if constexpr (CP) {
-                o.ba[0] = L.tab[bc.o0 + mul24(k, bc.st)]; o.ba[1] = L.tab[bc.o1 + mul24(k, bc.st)];
+                { const double *Tc = L.tab + bc.o0 + mul24(k, bc.st); o.ba[0] = Tc[0]; o.ba[1] = Tc[1]; }       // rows x, y of the own column: one load
 #pragma unroll
                 for (int m = 2; m < NX; m++) o.ba[m] = bac[m];
             } else {
@@ -484,8 +496,12 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         // Compact layout: L.pr aliases L.dpi -- p_k takes the slot of q_{k-1} = (P rb)_{k-1}, which stage k - 1's operand load
         // (always issued before stage k runs: the sets are filled at least one stage ahead, and LDS operations of a wave
         // execute in order) has fetched by then; the closing loop adds P dx in place.
-        struct Ops { double ghj, ba[NX], r0, r1, lx0, lx1, q; };
-        const int l01 = li == 1 ? 1 : 0;                                   // (lanes >= 2 follow lane 0: their values are not used)
+        // Operand merging: loads of disjoint lane sets leave in ONE LDS instruction with a per-lane address (an LDS instruction costs the same with one
+        // lane as with 64, and at eight trajectories per CU the launch follows the LDS instruction count of these loops).  The pivot data is used by
+        // lanes 0, 1 only and the Lxu pair by lanes 2..6 only, both sit in the stage's factor block: one pair (a0, a1) = lane 0 (1/L00, L10), lane 1
+        // (L10, 1/L11), lane 2 + i (Lxu_i0, Lxu_i1).  The arithmetic on every lane that counts is what it was (profiles/sweep_operand_merge_ab.jsonl).
+        struct Ops { double ghj, ba[NX], a0, a1, q; };
+        const int fbo = li < NU ? FB_R0 + li : FB_LXU + 2 * i5;            // (lanes >= 7 follow lane 2: their values are not used)
         const BaLane bc = ba_column(N, ls);
         double bac[NX];
         if constexpr (CP) {
@@ -496,7 +512,7 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
             const double *Fb = L.Hh + hoff<CP>(k);
             o.ghj = L.gh[uni(k * NV) + ls];
             if constexpr (CP) {
-                o.ba[0] = L.tab[bc.o0 + mul24(k, bc.st)]; o.ba[1] = L.tab[bc.o1 + mul24(k, bc.st)];
+                { const double *Tc = L.tab + bc.o0 + mul24(k, bc.st); o.ba[0] = Tc[0]; o.ba[1] = Tc[1]; }       // rows x, y of the own column: one load
 #pragma unroll
                 for (int l = 2; l < NX; l++) o.ba[l] = bac[l];
             } else {
@@ -504,17 +520,16 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
 #pragma unroll
                 for (int l = 0; l < NX; l++) o.ba[l] = BA[l * NV + ls];
             }
-            { const double *Pv = Fb + FB_R0 + l01; o.r0 = Pv[0]; o.r1 = Pv[1]; }      // lane 0: (1/L00, L10); lane 1: (L10, 1/L11)
-            o.lx0 = Fb[FB_LXU + 2 * i5]; o.lx1 = Fb[FB_LXU + 2 * i5 + 1];
+            o.a0 = Fb[fbo]; o.a1 = Fb[fbo + 1];
             o.q = L.dpi[uni((k + 1) * NX) + i5];
         };
         auto stage = [&](const Ops &o, int k) {
             const double Pb = p + o.q;                                     // (P_{k+1} rb_k + p_{k+1}), lane 2+i
             double fj = o.ghj;
             static_for<0, NX>([&](auto l_) { constexpr int l = decltype(l_)::value; fj += o.ba[l] * bcast16<NU + l>(Pb); });
-            const double y0 = bcast16<0>(fj * o.r0);                       // lane 0: fj 1/L00
-            const double y1 = bcast16<1>((fj - o.r0 * y0) * o.r1);         // lane 1: (fj - L10 y0) 1/L11   (its o.r0 is L10)
-            p = fj - o.lx0 * y0 - o.lx1 * y1;
+            const double y0 = bcast16<0>(fj * o.a0);                       // lane 0: fj 1/L00
+            const double y1 = bcast16<1>((fj - o.a0 * y0) * o.a1);         // lane 1: (fj - L10 y0) 1/L11   (its a0 is L10)
+            p = fj - o.a0 * y0 - o.a1 * y1;                                // lanes 2..6: fj - Lxu_i0 y0 - Lxu_i1 y1
             if (rowl && li == 0) { ysl<CP>(L, k)[0] = y0; ysl<CP>(L, k)[1] = y1; }
             if (xl) L.pr[k * NX + i5] = p;
         };
@@ -538,32 +553,32 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
     // forward sweep; dx_0 = 0 (dx lives in lanes 2..6).  dx+ = A dx + B du + rb with A = I + E (E: columns psi, v).
     if (sweeper) {
         double dx = 0.0;
-        // The lane's pair of Lxu has ONE register set, re-loaded for stage k + 1 right after its last use in stage k (two sets, like the other
-        // operands, pushed the compact kernels into scratch); the loads pass underneath the rest of the stage.
-        struct Ops { double y0, y1, r0, r1, a_psi, a_v, b_a, b_w, rbi; };
-        double lxu[2];
-        auto load_lxu = [&](int k) {
-            const double *Fb = L.Hh + hoff<CP>(k) + FB_LXU + 2 * i5;       // the lane's own pair
-            lxu[0] = Fb[0]; lxu[1] = Fb[1];
-        };
+        // Operand merging as in the backward sweep, two loads per stage fewer:
+        //   yr        lane 0: y0, lane 1: y1 (s0 counts on lane 0 only, s1 on lane 1 only), lanes 2..6: rb_i -- a per-lane (pointer, stride) pair, like
+        //             the factorisation's hrow / bo[] / bst[]; layout 3 keeps y inside the stage's block: another base and stride, the same load
+        //   (a0, a1)  lane 0: (1/L00, L10), lane 1: (L10, 1/L11), lanes 2..6: the lane's own pair of Lxu.  (Before, the Lxu pair had ONE register set of its
+        //             own, re-loaded right after its last use early in the stage, because two sets pushed the compact kernels into scratch; with y0, y1,
+        //             rb_i in one register the merged pair fits the double-buffered set: 14 doubles where 9 + 9 + 2 were live.)
+        struct Ops { double yr, a0, a1, a_psi, a_v, b_a, b_w; };
+        const double *yrb = li < NU ? ysl<CP>(L, 0) + li : L.rb + i5;
+        const int yrs = li < NU ? (CP == 3 ? hstride<CP>() : NU) : NX;
+        const int fbo = li < NU ? FB_R0 + li : FB_LXU + 2 * i5;
         const double i_psi = li == ZPSI ? 1.0 : 0.0, i_v = li == ZV ? 1.0 : 0.0;
-        const int l01f = li == 1 ? 1 : 0;
         double *dv_own = L.dv + ls;
         const BaLane br = ba_row4(N, i5);
         auto load_stage = [&](Ops &o, int k) {
             const double *Fb = L.Hh + hoff<CP>(k);
-            o.y0 = ysl<CP>(L, k)[0]; o.y1 = ysl<CP>(L, k)[1];
-            { const double *Pv = Fb + FB_R0 + l01f; o.r0 = Pv[0]; o.r1 = Pv[1]; }     // lane 0: (1/L00, L10); lane 1: (L10, 1/L11)
+            o.yr = yrb[mul24(k, yrs)];
+            o.a0 = Fb[fbo]; o.a1 = Fb[fbo + 1];
             if constexpr (CP) {
-                const double *Tr = L.tab + br.o0 + mul24(k, br.st);              // own row of [B A] as (b_a, b_w, a_psi, a_v)
-                o.a_psi = Tr[2]; o.a_v = Tr[3];
-                o.b_a = Tr[0]; o.b_w = Tr[1];
+                const double *Tr = L.tab + br.o0 + mul24(k, br.st);              // own row of [B A] as (b_a, b_w, a_psi, a_v), at stride 2
+                o.a_psi = Tr[4]; o.a_v = Tr[6];
+                o.b_a = Tr[0]; o.b_w = Tr[2];
             } else {
                 const double *BAr = L.BA + k * NX * NV + i5 * NV;          // own row of [B A]
                 o.a_psi = BAr[ZPSI]; o.a_v = BAr[ZV];                      // loads only: arithmetic here would wait for them
                 o.b_a = BAr[ZA]; o.b_w = BAr[ZW];
             }
-            o.rbi = L.rb[uni(k * NX) + i5];
         };
         auto stage = [&](const Ops &o, int k) {
             // du = -Luu^-T (Lxu^T dx + y)
@@ -572,24 +587,22 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
             // product form (round 4) has 13, four LDS instructions fewer.  At eight trajectories per CU the LDS unit is the busier one (65 % of the kernel
             // time, most of it these sweeps): cfg 2 1.288 -> 1.343 M solves/s (+4.3 %, profiles/round6_saturated_levers_ab.jsonl).
             // Every kernel family takes it (the fast and the compact kernel of a shape stay bitwise equal); the sums associate differently: rounding level.
-            const double xm = (li >= NU && li < NV) ? 1.0 : 0.0;
-            const double p0 = xm * (lxu[0] * dx), p1 = xm * (lxu[1] * dx);
-            double s0 = o.y0, s1 = o.y1;
+            // (p0, p1 are read from lanes 2..6 only -- bcast16<NU + m> --, where a 0 / 1 lane mask that used to multiply them was 1.0: gone, same bits)
+            const double p0 = o.a0 * dx, p1 = o.a1 * dx;
+            double s0 = o.yr, s1 = o.yr;
             static_for<0, NX>([&](auto m_) { constexpr int m = decltype(m_)::value; s0 += bcast16<NU + m>(p0); s1 += bcast16<NU + m>(p1); });
             double dxs[NX];
             dxs[ZPSI - NU] = bcast16<ZPSI>(dx); dxs[ZV - NU] = bcast16<ZV>(dx);
-            load_lxu(k + 1 < N ? k + 1 : N - 1);                           // (unconditional, clamped)
-            const double u1 = bcast16<1>(-s1 * o.r1);                      // lane 1: -s1 1/L11
-            const double u0 = bcast16<0>((-s0 - o.r1 * u1) * o.r0);        // lane 0: (-s0 - L10 u1) 1/L00   (its o.r1 is L10)
+            const double u1 = bcast16<1>(-s1 * o.a1);                      // lane 1: -s1 1/L11
+            const double u0 = bcast16<0>((-s0 - o.a1 * u1) * o.a0);        // lane 0: (-s0 - L10 u1) 1/L00   (its a1 is L10)
             if (rowl && li == 0) { L.dv[k * NV] = u0; L.dv[k * NV + 1] = u1; }
             if (xl) dv_own[k * NV] = dx;
             const double dpsi = dxs[ZPSI - NU], dvv = dxs[ZV - NU];
             const double e_psi = o.a_psi - i_psi, e_v = o.a_v - i_v;
-            dx = dx + e_psi * dpsi + e_v * dvv + o.b_a * u0 + o.b_w * u1 + o.rbi;   // lanes 2..6 meaningful
+            dx = dx + e_psi * dpsi + e_v * dvv + o.b_a * u0 + o.b_w * u1 + o.yr;   // lanes 2..6 meaningful (their yr is rb_i)
         };
         Ops oa, ob;
         load_stage(oa, 0);
-        load_lxu(0);
         int k = 0;
         for (; k + 1 < N; k += 2) {
             load_stage(ob, k + 1);
