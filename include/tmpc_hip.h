@@ -489,6 +489,76 @@ int tmpc_fit_path(tmpc_handle *h, int32_t n_scenes, int32_t n_pts_max, int32_t n
                   const void *d_left_xy, const void *d_right_xy, const void *d_v, void *d_path, void *d_path_count, void *d_path_length,
                   void *d_bounds, void *d_velocity, void *d_road_width, void *d_status);
 
+/* ---- free-space decomposition on device: costmap -> the decomp rows.  What DecompConstraints::update and setParameters
+ * (mpc_planner_modules/src/decomp_constraints.cpp:52-189) do for the static obstacles of the rosnavigation stack: the occupied cells of the
+ * costmap become points, a polyline on the reference path is laid along the warm start's speeds, every segment of it gets one convex polygon
+ * free of points, and the polygon's rows A p <= b go into the decomp rows of the stage behind the segment.  DecompUtil is not in the reference
+ * tree, and the reference uses a modified copy nobody here has read: this is a RESTATEMENT OF UPSTREAM DecompUtil's LineSegment algorithm
+ * (DESIGN.md U16), held bit for bit to mpc_planner_amd.modules (costmap_points, decomp_halfspaces) and by the tests to hand values and to the
+ * geometric properties any correct decomposition has; parity with the reference's own DecompUtil is not pinned.  All three calls are
+ * stream-ordered on the handle's stream, allocate nothing, do not synchronise, and check every argument before any launch. */
+/* getOccupiedGridCells (:122-148).  Needs no batch; also available in a generated solver.  Inputs (device):
+ *   d_cost     u8  [n_scenes][size_y][size_x]   the costmap_2d layout, index my * size_x + mx;  size_x, size_y >= 1, size_x * size_y <= 2^20
+ *   d_origin   f64 [n_scenes][2]                world position of the map's corner
+ *   resolution                                  cell size
+ * Outputs (device, caller-owned):
+ *   d_points   f64 [n_scenes][n_pts_max][2]     1 <= n_pts_max <= 16384
+ *   d_count    i32 [n_scenes]
+ *   d_overflow u8  [n_scenes]                   or NULL
+ * A cell is occupied iff its cost is not 0 (costmap_2d::FREE_SPACE); its point is the cell centre (origin_x + (mx + 0.5) resolution,
+ * origin_y + (my + 0.5) resolution) (Costmap2D::mapToWorld).  The points come in the reference's order, mx outer and my inner; the first
+ * n_pts_max occupied cells are kept, d_count is their number and d_overflow 1 iff there were more.  Entries at or beyond d_count are not
+ * touched.  One workgroup per scene: an order-preserving compaction (ballot and popcount prefix), no atomics.
+ * TMPC_ERR_INVALID: a NULL d_cost / d_origin / d_points / d_count, n_scenes <= 0, a size < 1 or size_x * size_y > 2^20, n_pts_max outside
+ * [1, 16384]. */
+int tmpc_costmap_points(tmpc_handle *h, int32_t n_scenes, int32_t size_x, int32_t size_y, const void *d_cost, const void *d_origin, double resolution,
+                        int32_t n_pts_max, void *d_points, void *d_count, void *d_overflow);
+/* DecompConstraints::update (:52-118) for n_scenes scenes.  Needs a batch: v_k is read from the handle's warm start, as tmpc_road_halfspaces
+ * reads the spline state; both models' strides.  Inputs (device):
+ *   d_main_of      i32 [n_scenes]                 the batch entry that stands for the scene's MAIN solver
+ *   d_path, d_path_count, d_path_length           the whole paths as tmpc_fit_path writes them, rows n_seg_max apart, 1 <= n_seg_max <= 1024
+ *   d_s0           f64 [n_scenes]                 state["spline"]; tmpc_track_path's d_closest_s can be passed as it is
+ *   d_state_x      f64 [n_scenes]                 the dummy's b = x + 100
+ *   d_points       f64 [n_scenes][n_pts_max][2],  d_count i32 [n_scenes] clipped to [0, n_pts_max]: what tmpc_costmap_points wrote
+ *   range                                         decomp/range: half width of the local box;  n_rows = decomp/max_constraints, 1 .. 64
+ * Outputs (device, caller-owned; every entry of a processed scene is written, dummies included):
+ *   d_rows         f64 [n_scenes][N][n_rows][3]   (a1, a2, b)
+ *   d_row_count    i32 [n_scenes][N]              rows that are not dummies
+ *   d_status       u8  [n_scenes][N]              0 complete; 1 truncated: more rows were found than n_rows (the reference logs a warning);
+ *                                                 2 degenerate: the stage has FEWER rows than the polygon needs, or none -- see below
+ * A scene whose d_main_of is outside [0, B) or whose path count is <= 0 is left wholly untouched.
+ * THE POLYLINE (:68-82).  N points P(s_k), s_0 = d_s0, s_{k+1} = s_k + v_k dt accumulated left to right, v_k = the warm start's v of stage k.
+ * P(s): the cubic of segment i = max{j < count : start_j <= s} (0 below the first knot) at t = s - start_i; for s >= length the path
+ * continues straight along its end tangent, P(length) + (s - length) P'(length) (U14-3).  Segment k, P(s_k) -> P(s_{k+1}), goes to stage
+ * k + 1; stage 0 is all dummies (1, 0, x + 100), count 0, status 0.
+ * ONE SEGMENT (U16).  e = unit direction, h = (e_y, -e_x), c = midpoint, f = half length; a segment whose length is not positive and finite
+ * is degenerate: all dummies, status 2 (DecompUtil's normals are NaN there and the reference's copy stops at row 0 -- a robot with v = 0 gets
+ * no static constraints in the reference; kept, and reported).  Local coordinates of a point o: u = (o - c).e, w = (o - c).h.  Box: |w| <=
+ * range + 1e-10 and |u| <= f + range + 1e-10.  Ellipse: a = b = f; while a box point has sqrt(d2) <= 1 (then: 1 - sqrt(d2) > 1e-10),
+ * d2 = (u / a)^2 + (w / b)^2, the one with the smallest d2 is chosen, b = |w| / sqrt(1 - (u / a)^2) if u < a, and the chosen point leaves.
+ * Polygon: among all box points, repeatedly the one with the smallest d2 gives the row (n, n.o) tangent to the ellipse through it, n = the
+ * normalised (u / a^2, w / b^2) turned back into the world; it and every point with n.(o' - o) >= 0 leave; the row is negated if c violates
+ * it; at most n_rows such rows.  Smallest d2: a NaN counts as +inf, the lowest point index wins among equals.  Then the four rows of the box:
+ * (h, h.(p1 + range h)), (-h, -h.(p1 - range h)), (e, e.(p2 + range e)), (-e, -e.(p1 - range e)).
+ * THE COPY (:90-114).  Of the rows found, the first min(found, n_rows) are copied until one has |A_i| < 1e-3 or a NaN first entry; that row and
+ * every later one is the dummy (an obstacle point ON the segment does this: status 2).
+ * One workgroup of 256 threads per (scene, stage); the points are streamed from global memory on every pass, the three sets are bitmasks in
+ * LDS, the argmin a reduction on (d2, index); no atomics, no unbounded loop.
+ * TMPC_ERR_INVALID: no batch, a NULL pointer, n_scenes <= 0, n_seg_max outside [1, 1024], n_pts_max outside [1, 16384], n_rows outside
+ * [1, 64], a range that is negative or not finite, a generated solver. */
+int tmpc_decomp_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scenes, int32_t n_seg_max, const void *d_path, const void *d_path_count,
+                           const void *d_path_length, const void *d_s0, const void *d_state_x, const void *d_points, const void *d_count,
+                           int32_t n_pts_max, double range, int32_t n_rows, void *d_rows, void *d_row_count, void *d_status);
+/* DecompConstraints::setParameters (:150-189): the rows d_rows [n_scenes][N][n_rows][3] of EVERY stage, stage 0 included, into the slack rows
+ * first_row .. first_row + n_rows - 1 (disc_0_decomp_{j}_a1 / _a2 / _b) of every entry b of the CURRENT batch with d_scene_of[b] (i32 [B])
+ * inside [0, n_scenes), and ego_disc_0_offset = disc_offset at every stage of those entries; nothing else is touched, an entry whose scene is
+ * outside that range not at all.  Requires first_row + n_rows <= the problem's slack rows (n_slk).  Parameter sharing as for
+ * tmpc_set_path_parameters: the rows are an entry's own columns, a map stays valid when every entry of a set names the same scene, and a
+ * caller with TMPC_SHARE_COPIES_NOT_MAINTAINED still names every entry, since the kernels read these rows from the entry itself.
+ * TMPC_ERR_INVALID: no batch, a NULL d_rows / d_scene_of, n_scenes <= 0, n_rows < 1, first_row < 0, rows that do not fit, a generated solver. */
+int tmpc_set_halfspace_rows(tmpc_handle *h, const void *d_rows, int32_t n_rows, int32_t first_row, const void *d_scene_of, int32_t n_scenes,
+                            double disc_offset);
+
 /* ---- scenario -> polygon construction of SH-MPC on device.  Replaces what the reference gets from the
  * external scenario_module (scenario_constraints.cpp:47 update, :76-79 setParameters; source absent -> restated, see
  * mpc_planner_amd/modules.py::scenario_halfspaces): for every trajectory b and stage k >= 1, each of the n_pts sampled

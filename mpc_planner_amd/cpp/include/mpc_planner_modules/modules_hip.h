@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <map>
 #include <memory>
 #include <string>
@@ -35,6 +36,7 @@
 #include <mpc_planner_solver/solver_interface.h>
 #include <mpc_planner_types/data_types.h>
 #include <mpc_planner_types/module_data.h>
+#include <mpc_planner_modules/free_space.h>
 #include <mpc_planner_modules/reference_path.h>
 #include <mpc_planner_types/realtime_data.h>
 
@@ -59,6 +61,8 @@ namespace MPCPlanner
         std::map<std::string, double> weights;               /* weights/<name> */
         bool dynamic_velocity_reference{false};              /* contouring/dynamic_velocity_reference */
         int num_segments{5};                                 /* contouring/num_segments */
+        double decomp_range{2.0};                            /* decomp/range: half width of the box DecompConstraints looks for obstacles in */
+        int decomp_max_constraints{12};                      /* decomp/max_constraints: rows per stage, at most the generated solver's decomp rows */
         bool add_road_constraints{false};                    /* contouring/add_road_constraints (true in every settings.yaml the reference ships; false here so
                                                                 that a caller who did not generate the two extra rows sees none: INTEGRATION.md section 2) */
         bool two_way_road{false};                            /* road/two_way */
@@ -730,6 +734,89 @@ namespace MPCPlanner
         BatchContext _batch;                                                     /* this module instance's batch: one state slot per scenario solver */
     private:
         double _disc_offset;
+    };
+#endif
+
+#if defined(SOLVER_NDECOMP) && SOLVER_NDECOMP > 0
+    /* ---- decomp_constraints.cpp:52-200 (the solver was generated with n_decomp rows).  DecompUtil is not in the reference tree: the polygons
+     * are FreeSpace::decompose's (mpc_planner_modules/free_space.h), upstream DecompUtil's LineSegment algorithm restated in
+     * the arithmetic tmpc_decomp_halfspaces_kernel compiles too; parity with the reference's own, modified DecompUtil is not pinned.  One ego
+     * disc, like every configuration the reference ships with this module. ---- */
+    class DecompConstraints
+    {
+    public:
+        DecompConstraints(std::shared_ptr<Solver> solver, const ModuleConfig &cfg)
+            : _solver(solver), _cfg(cfg), _range(cfg.decomp_range), _max_constraints(std::min(cfg.decomp_max_constraints, (int)SOLVER_NDECOMP))
+        {
+            _occ_pos.reserve(2000);                                               /* Reserve some space for the occupied positions (:28) */
+        }
+        /* (:52-120) the occupied cells, the polyline on the reference path along the main solver's predicted velocities, one polygon per
+         * segment.  The path is the whole path Contouring's path mode tracks (data.reference_path); without one, the window in
+         * module_data.path, whose last cubic continues beyond it.  _status[k]: FreeSpace::Status of stage k -- DEGENERATE marks a stage that is
+         * silently unconstrained in the reference (a robot that stands still, an obstacle cell on the path). */
+        void update(State &state, const RealTimeData &data, ModuleData &module_data)
+        {
+            _dummy_b = state.get("x") + 100.;
+            getOccupiedGridCells(data);                                           /* Retrieve occupied points from the costmap */
+            ReferencePathSpline path;
+            if (!data.reference_path.empty()) { path.segments = data.reference_path; path.length = data.reference_path_length; }
+            else { path.segments = module_data.path; path.length = std::numeric_limits<double>::infinity(); }
+            std::vector<double> v(_solver->N);
+            for (int k = 0; k < _solver->N; k++) v[k] = _solver->getEgoPrediction(k, "v");          /* Use the predicted velocity (:79) */
+            if (path.empty()) {
+                _rows.assign((size_t)_solver->N * _max_constraints * 3, 0.); _count.assign(_solver->N, 0); _status.assign(_solver->N, FreeSpace::DEGENERATE);
+                for (size_t r = 0; r < _rows.size(); r += 3) { _rows[r] = _dummy_a1; _rows[r + 1] = _dummy_a2; _rows[r + 2] = _dummy_b; }
+                return;
+            }
+            FreeSpace::decomposePath(path, state.get("spline"), v, _solver->dt, _occ_pos, _range, _max_constraints, state.get("x"), _rows, _count, _status);
+            int max_decomp_constraints = 0;
+            for (int k = 0; k < _solver->N; k++) if (_status[k] == FreeSpace::TRUNCATED) max_decomp_constraints = _max_constraints + 1;
+            _exceeded = max_decomp_constraints > _max_constraints;                /* the reference logs a warning (:116-117) */
+        }
+        /* (:122-148) */
+        bool getOccupiedGridCells(const RealTimeData &data)
+        {
+            _overflow = FreeSpace::occupiedCells(*data.costmap, _occ_pos);
+            return true;
+        }
+        /* (:150-189) stage 0 and unused rows are the dummies (1, 0, x + 100), which update() has already put into _rows */
+        void setParameters(const RealTimeData &data, const ModuleData &, int k)
+        {
+            int constraint_counter = 0;                                           /* Necessary for now to map the disc and obstacle index to a single index */
+            for (int d = 0; d < 1; d++) {
+                setSolverParameterEgoDiscOffset(k, _solver->_params, data.robot_area[d].offset, d);
+                for (int i = 0; i < _max_constraints; i++) {
+                    const double *row = &_rows[((size_t)k * _max_constraints + i) * 3];
+                    setSolverParameterDecompA1(k, _solver->_params, row[0], constraint_counter);
+                    setSolverParameterDecompA2(k, _solver->_params, row[1], constraint_counter);
+                    setSolverParameterDecompB(k, _solver->_params, row[2], constraint_counter);
+                    constraint_counter++;
+                }
+                for (int i = _max_constraints; i < (int)SOLVER_NDECOMP; i++) {   /* rows the solver has beyond decomp/max_constraints stay dummies */
+                    setSolverParameterDecompA1(k, _solver->_params, _dummy_a1, i); setSolverParameterDecompA2(k, _solver->_params, _dummy_a2, i);
+                    setSolverParameterDecompB(k, _solver->_params, _dummy_b, i);
+                }
+            }
+        }
+        /* (:191-200) */
+        bool isDataReady(const RealTimeData &data, std::string &missing_data)
+        {
+            if (data.costmap == nullptr) { missing_data += "Costmap "; return false; }
+            return true;
+        }
+        const std::vector<double> &occupiedPositions() const { return _occ_pos; }   /* (x, y) pairs */
+        const std::vector<int> &rowCounts() const { return _count; }
+        const std::vector<int> &status() const { return _status; }
+        bool exceeded() const { return _exceeded; }
+        std::shared_ptr<Solver> _solver;
+    private:
+        ModuleConfig _cfg;
+        double _range;
+        int _max_constraints;
+        std::vector<double> _occ_pos, _rows;                                      /* _rows [N][max_constraints][3] */
+        std::vector<int> _count, _status;
+        double _dummy_a1{1.}, _dummy_a2{0.}, _dummy_b{100.};
+        bool _overflow{false}, _exceeded{false};
     };
 #endif
 }

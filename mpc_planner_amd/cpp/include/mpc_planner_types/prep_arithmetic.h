@@ -1,6 +1,6 @@
 /* mpc_planner_types/prep_arithmetic.h -- the double-precision arithmetic of data preparation (road rows, obstacle preparation, path tracking,
- * path fitting), written ONCE for the device kernels (csrc/tmpc_aux_kernels.hpp) and the Solver-free C++ headers (reference_path.h,
- * data_preparation.h, Contouring in modules_hip.h): both compile these functions, so they cannot drift apart.  The independent statement the
+ * path fitting, free-space decomposition), written ONCE for the device kernels (csrc/tmpc_aux_kernels.hpp) and the Solver-free C++ headers
+ * (reference_path.h, free_space.h, data_preparation.h, Contouring in modules_hip.h): both compile these functions, so they cannot drift apart.  The independent statement the
  * tests compare both against is the numpy mirror, mpc_planner_amd/modules.py; every function keeps the mirror's operation order, and nothing is
  * fused into multiply-adds (the pragma under clang; build host code with -ffp-contract=off).  Plain functions on doubles: no containers, no
  * planner types.  A cubic is its eight coefficients c = (ax bx cx dx ay by cy dy): x(t) = ((ax t + bx) t + cx) t + dx, the same for y. */
@@ -180,5 +180,80 @@ namespace tmpc_arith
     }
     /* getDummyObstacle (:49-56): one coordinate of the dummy's position from the robot's */
     TMPC_ARITH_FN double dummy_coordinate(double x) { TMPC_ARITH_NO_FMA return x + 100.0; }
+
+    /* ---- free-space decomposition (DecompConstraints::update, decomp_constraints.cpp:52-148).  DecompUtil is not in the reference tree: upstream
+     * DecompUtil's LineSegment algorithm restated in the frame of the segment.  e = unit direction p1 -> p2, h = (e_y, -e_x),
+     * c = midpoint, f = half length; a point o has the local coordinates u = (o - c).e along the segment and w = (o - c).h across it; the
+     * ellipse has the semi-axes a (along, = f) and b (across). ---- */
+    constexpr double DECOMP_EPS = 1e-10;            /* DecompUtil's epsilon_ */
+    constexpr double DECOMP_TERMINATOR = 1e-3;      /* a row with a shorter normal (or NaN) ends the copy (decomp_constraints.cpp:98) */
+    /* centre of costmap cell m along one axis (costmap_2d::Costmap2D::mapToWorld) */
+    TMPC_ARITH_FN double cell_centre(double origin, int m, double resolution) { TMPC_ARITH_NO_FMA return origin + ((double)m + 0.5) * resolution; }
+    /* s_{k+1} = s_k + v_k dt (:81) */
+    TMPC_ARITH_FN double advance(double s, double v, double dt) { TMPC_ARITH_NO_FMA return s + v * dt; }
+    /* one coordinate of the path beyond its end: straight along the end tangent (U14-3) */
+    TMPC_ARITH_FN double continue_straight(double x_end, double dx_end, double s, double length) { TMPC_ARITH_NO_FMA return x_end + (s - length) * dx_end; }
+    /* frame of the segment p1 -> p2; false: the segment is degenerate (length zero, NaN or inf) and the outputs mean nothing */
+    TMPC_ARITH_FN bool decomp_frame(double p1x, double p1y, double p2x, double p2y, double &ex, double &ey, double &cx, double &cy, double &f)
+    {
+        TMPC_ARITH_NO_FMA
+        const double dx = p2x - p1x, dy = p2y - p1y;
+        const double len = sqrt(dx * dx + dy * dy);
+        ex = dx / len; ey = dy / len;
+        cx = (p1x + p2x) / 2.0; cy = (p1y + p2y) / 2.0;
+        f = len / 2.0;
+        return len > 0.0 && len < __builtin_huge_val();
+    }
+    TMPC_ARITH_FN void decomp_local(double ox, double oy, double cx, double cy, double ex, double ey, double &u, double &w)
+    {
+        TMPC_ARITH_NO_FMA
+        const double rx = ox - cx, ry = oy - cy;
+        u = rx * ex + ry * ey;
+        w = rx * ey - ry * ex;
+    }
+    /* add_local_bbox + points_inside: the box of half width R across and f + R along */
+    TMPC_ARITH_FN bool decomp_in_box(double u, double w, double f, double R) { TMPC_ARITH_NO_FMA return fabs(w) <= R + DECOMP_EPS && fabs(u) <= f + R + DECOMP_EPS; }
+    /* squared ellipse distance, and the key of the argmin rule: d2, a NaN counts as +inf */
+    TMPC_ARITH_FN double decomp_d2(double u, double w, double a, double b) { TMPC_ARITH_NO_FMA const double ua = u / a, wb = w / b; return ua * ua + wb * wb; }
+    TMPC_ARITH_FN double decomp_key(double d2) { return d2 == d2 ? d2 : __builtin_huge_val(); }
+    TMPC_ARITH_FN bool decomp_inside_first(double d2) { TMPC_ARITH_NO_FMA return sqrt(d2) <= 1.0; }
+    TMPC_ARITH_FN bool decomp_inside(double d2) { TMPC_ARITH_NO_FMA return 1.0 - sqrt(d2) > DECOMP_EPS; }
+    /* the ellipse shrunk through the point (u, w): the new b (unchanged unless u < a) */
+    TMPC_ARITH_FN double decomp_shrink(double u, double w, double a, double b)
+    {
+        TMPC_ARITH_NO_FMA
+        if (!(u < a)) return b;
+        const double ua = u / a;
+        return fabs(w) / sqrt(1.0 - ua * ua);
+    }
+    /* tangent row of the ellipse through the point o = (ox, oy) with local (u, w): unit normal n, beta = n.o; not yet flipped */
+    TMPC_ARITH_FN void decomp_row(double u, double w, double a, double b, double ex, double ey, double ox, double oy, double &nx, double &ny, double &beta)
+    {
+        TMPC_ARITH_NO_FMA
+        const double gu = u / (a * a), gw = w / (b * b);
+        const double nrm = sqrt(gu * gu + gw * gw);
+        const double nu = gu / nrm, nw = gw / nrm;
+        nx = nu * ex + nw * ey; ny = nu * ey - nw * ex;
+        beta = nx * ox + ny * oy;
+    }
+    /* n.(o - o*): a point stays in the remaining set iff this is < 0 */
+    TMPC_ARITH_FN double decomp_side(double nx, double ny, double ox, double oy, double sx, double sy) { TMPC_ARITH_NO_FMA return nx * (ox - sx) + ny * (oy - sy); }
+    /* LinearConstraint's flip: the centre of the segment has to satisfy the row */
+    TMPC_ARITH_FN void decomp_flip(double cx, double cy, double &nx, double &ny, double &beta)
+    {
+        TMPC_ARITH_NO_FMA
+        if (nx * cx + ny * cy - beta > 0.0) { nx = -nx; ny = -ny; beta = -beta; }
+    }
+    /* the four rows of the local box, in DecompUtil's order: (h, h.(p1 + R h)), (-h, -h.(p1 - R h)), (e, e.(p2 + R e)), (-e, -e.(p1 - R e)); row [4][3] */
+    TMPC_ARITH_FN void decomp_box_rows(double p1x, double p1y, double p2x, double p2y, double ex, double ey, double R, double *row)
+    {
+        const double hx = ey, hy = -ex;
+        row[0] = hx; row[1] = hy; row[2] = road_offset_plus(p1x, p1y, hx, hy, R);
+        row[3] = -hx; row[4] = -hy; row[5] = -road_offset_minus(p1x, p1y, hx, hy, R);
+        row[6] = ex; row[7] = ey; row[8] = road_offset_plus(p2x, p2y, ex, ey, R);
+        row[9] = -ex; row[10] = -ey; row[11] = -road_offset_minus(p1x, p1y, ex, ey, R);
+    }
+    /* does row (a1, a2, .) end the copy (:98)? */
+    TMPC_ARITH_FN bool decomp_terminator(double a1, double a2) { TMPC_ARITH_NO_FMA return sqrt(a1 * a1 + a2 * a2) < DECOMP_TERMINATOR || a1 != a1; }
 }
 #endif

@@ -1114,6 +1114,256 @@ __global__ __launch_bounds__(64) void tmpc_scenario_support_kernel(Dims d, int B
 }
 
 
+// ---- free-space decomposition on device: DecompConstraints::update (decomp_constraints.cpp:52-148) ---------------------------------------
+// DecompUtil is not in the reference tree: upstream DecompUtil's LineSegment algorithm is restated in the frame of the segment, DESIGN.md U16.
+// The arithmetic is tmpc_arith's decomp_*, the source mpc_planner_modules/free_space.h compiles too: every output is bit-equal to the
+// independent modules.py::costmap_points / decomp_halfspaces.
+constexpr int DECOMP_THREADS = 256, DECOMP_MAX_POINTS = 16384, DECOMP_MAX_ROWS = 64, COSTMAP_MAX_CELLS = 1 << 20;
+
+// getOccupiedGridCells (:122-148).  one workgroup per scene q: the cells in the reference's order e = mx size_y + my (mx outer, my inner), 256 per
+// sweep; an occupied cell's place in the list = occupied cells before the sweep + those of the lower waves (four counts through LDS) + those of
+// the lower lanes of its wave (popcount of the ballot below the lane): an order-preserving compaction without atomics.  The first n_pts_max
+// are written, nothing at or beyond count; the sweeps stop once the list has overflowed.
+__global__ __launch_bounds__(DECOMP_THREADS) void tmpc_costmap_points_kernel(int size_x, int size_y, double resolution, int n_pts_max, const uint8_t *cost,
+                                                                           const double *origin, double *points, int *count, uint8_t *overflow)
+{
+    __shared__ int s_wave[2][4];
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_cells = size_x * size_y;
+    const uint8_t *cq = cost + (size_t)q * n_cells;
+    const double ox = origin[(size_t)q * 2], oy = origin[(size_t)q * 2 + 1];
+    double *pq = points + (size_t)q * n_pts_max * 2;
+    int total = 0;
+    for (int base = 0, it = 0; base < n_cells && total <= n_pts_max; base += DECOMP_THREADS, it++) {
+        const int e = base + tid;
+        int mx = 0, my = 0;
+        bool occ = false;
+        if (e < n_cells) { mx = e / size_y; my = e - mx * size_y; occ = cq[(size_t)my * size_x + mx] != 0; }
+        const unsigned long long m = __ballot(occ);
+        if (lane == 0) s_wave[it & 1][wave] = __popcll(m);
+        __syncthreads();                                                  // (double-buffered counts: one barrier per sweep)
+        int before = total, all = 0;
+        for (int w = 0; w < 4; w++) { const int c = s_wave[it & 1][w]; all += c; if (w < wave) before += c; }
+        const int at = before + __popcll(m & ((1ull << lane) - 1ull));
+        if (occ && at < n_pts_max) {
+            pq[(size_t)at * 2] = tmpc_arith::cell_centre(ox, mx, resolution);
+            pq[(size_t)at * 2 + 1] = tmpc_arith::cell_centre(oy, my, resolution);
+        }
+        total += all;
+    }
+    if (tid == 0) {
+        count[q] = total < n_pts_max ? total : n_pts_max;
+        if (overflow) overflow[q] = total > n_pts_max ? 1 : 0;
+    }
+}
+
+// the (key, index) argmin of a workgroup of four waves: lexicographic, so the result does not depend on the order of the reduction; index
+// DECOMP_NONE = nobody.  s_key / s_idx: four partials; the barrier in front protects them from the previous call's readers.
+constexpr int DECOMP_NONE = 0x7fffffff;
+__device__ inline void decomp_block_argmin(double &key, int &idx, double *s_key, int *s_idx)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double ok = __shfl_xor(key, o, 64); const int oi = __shfl_xor(idx, o, 64);
+        if (ok < key || (ok == key && oi < idx)) { key = ok; idx = oi; }
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { s_key[threadIdx.x >> 6] = key; s_idx[threadIdx.x >> 6] = idx; }
+    __syncthreads();
+    key = s_key[0]; idx = s_idx[0];
+#pragma unroll
+    for (int w = 1; w < 4; w++) {
+        const double ok = s_key[w]; const int oi = s_idx[w];
+        if (ok < key || (ok == key && oi < idx)) { key = ok; idx = oi; }
+    }
+}
+
+// P(s) on a whole path (n segments, rows of 9, `len` the last knot): the cubic of segment i = max{j < n : start_j <= s} (0 below the first knot)
+// at t = s - start_i; from `len` on straight along the end tangent (U14-3).  The lookup runs over all lanes; s_key / s_idx as above.
+__device__ inline void decomp_path_point(const double *pq, int n, double len, double s, double &x, double &y, double *s_key, int *s_idx)
+{
+    if (s >= len) {
+        double ex, ey, edx, edy;
+        tmpc_arith::cubic(pq + (size_t)(n - 1) * 9, len - pq[(size_t)(n - 1) * 9 + 8], ex, ey, edx, edy);
+        x = tmpc_arith::continue_straight(ex, edx, s, len); y = tmpc_arith::continue_straight(ey, edy, s, len);
+        return;
+    }
+    int i = 0;
+    for (int j = threadIdx.x; j < n; j += DECOMP_THREADS) if (pq[(size_t)j * 9 + 8] <= s) i = j;
+    double key = 0.0; int neg = -i;                                        // the largest i = the smallest -i
+    decomp_block_argmin(key, neg, s_key, s_idx);
+    i = -neg;
+    double dx, dy;
+    tmpc_arith::cubic(pq + (size_t)i * 9, s - pq[(size_t)i * 9 + 8], x, y, dx, dy);
+}
+
+// one workgroup per (scene q, stage k).  Stage 0: dummies, count 0, status 0.  Stage k >= 1: the segment P(s_{k-1}) -> P(s_k) with s_0 = s0[q],
+// s_{j+1} = s_j + v_j dt, v_j the warm start of batch entry main_of[q] (`_solver->getEgoPrediction(j, "v")`, :79).  The scene's points (count
+// clipped to [0, n_pts_max]) are streamed from global memory on every pass and u, w, d2 recomputed, never stored; point i belongs to lane
+// i % 64 of wave (i / 64) % 4, which keeps its bit of the three sets (box, inside the ellipse, remaining) in LDS words only that wave touches
+// -- a ballot per 64 points, no atomics.  A wave skips a word that is empty.  The ellipse loop removes at least the chosen point per pass, the
+// polygon loop ends after n_rows rows: no loop without a bound.  Every lane computes the frame, the ellipse and the rows from the same
+// values in the same order, so they agree without a broadcast.
+__global__ __launch_bounds__(DECOMP_THREADS) void tmpc_decomp_halfspaces_kernel(Dims d, int B, int n_scenes, const double *x0, const int *main_of, int n_seg_max,
+                                                                              const double *path, const int *path_count, const double *path_length,
+                                                                              const double *s0, const double *state_x, const double *points, const int *count,
+                                                                              int n_pts_max, double R, int n_rows, double *rows, int *row_count, uint8_t *status)
+{
+#pragma clang fp contract(off)
+    __shared__ unsigned long long s_box[DECOMP_MAX_POINTS / 64], s_set[DECOMP_MAX_POINTS / 64];
+    __shared__ double s_key[4], s_row[(DECOMP_MAX_ROWS + 4) * 3];
+    __shared__ int s_idx[4], s_written;
+    const int N = d.N, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x / N, k = blockIdx.x - q * N;
+    if (q >= n_scenes) return;
+    const int b = main_of[q];
+    int n = path_count[q];
+    n = n > n_seg_max ? n_seg_max : n;
+    if (b < 0 || b >= B || n <= 0) return;                               // (uniform over the workgroup: nothing is read, nothing written)
+    const size_t unit = (size_t)q * N + k;
+    double *out = rows + unit * n_rows * 3;
+    const double dummy_b = tmpc_arith::dummy_coordinate(state_x[q]);
+    int found = 0, limit = 0;
+    bool valid = false;
+    if (k > 0) {
+        int cnt = count[q];
+        cnt = cnt < 0 ? 0 : (cnt > n_pts_max ? n_pts_max : cnt);
+        const double *pts = points + (size_t)q * n_pts_max * 2;
+        const double *pq = path + (size_t)q * n_seg_max * 9;
+        const double len = path_length[q];
+        double s = s0[q];
+        for (int j = 0; j < k - 1; j++) s = tmpc_arith::advance(s, x0[((size_t)b * (N + 1) + j) * ext_nv(d) + ZV], d.dt);
+        const double s_next = tmpc_arith::advance(s, x0[((size_t)b * (N + 1) + (k - 1)) * ext_nv(d) + ZV], d.dt);
+        double p1x, p1y, p2x, p2y, ex, ey, cx, cy, f;
+        decomp_path_point(pq, n, len, s, p1x, p1y, s_key, s_idx);
+        decomp_path_point(pq, n, len, s_next, p2x, p2y, s_key, s_idx);
+        valid = tmpc_arith::decomp_frame(p1x, p1y, p2x, p2y, ex, ey, cx, cy, f);
+        if (valid) {
+            const int n_words = (cnt + 63) >> 6;
+            double a = f, bb = f;
+            for (int c = wave; c < n_words; c += 4) {
+                const int i = c * 64 + lane;
+                bool in_box = false, inside = false;
+                if (i < cnt) {
+                    double u, w;
+                    tmpc_arith::decomp_local(pts[(size_t)i * 2], pts[(size_t)i * 2 + 1], cx, cy, ex, ey, u, w);
+                    in_box = tmpc_arith::decomp_in_box(u, w, f, R);
+                    inside = in_box && tmpc_arith::decomp_inside_first(tmpc_arith::decomp_d2(u, w, a, bb));
+                }
+                const unsigned long long mb = __ballot(in_box), mi = __ballot(inside);
+                if (lane == 0) { s_box[c] = mb; s_set[c] = mi; }
+            }
+            __syncthreads();                                                 // (after every rewrite of the sets: the words are read again below)
+            // the ellipse: shrink through the closest inside point until none is left
+            for (int pass = 0; pass < cnt; pass++) {
+                double key = __builtin_huge_val(); int idx = DECOMP_NONE;
+                for (int c = wave; c < n_words; c += 4) {
+                    const unsigned long long m = s_set[c];
+                    if (m == 0ull) continue;
+                    const int i = c * 64 + lane;
+                    if ((m >> lane) & 1ull) {
+                        double u, w;
+                        tmpc_arith::decomp_local(pts[(size_t)i * 2], pts[(size_t)i * 2 + 1], cx, cy, ex, ey, u, w);
+                        const double kk = tmpc_arith::decomp_key(tmpc_arith::decomp_d2(u, w, a, bb));
+                        if (kk < key || idx == DECOMP_NONE) { key = kk; idx = i; }      // ascending i per lane: strict '<' keeps the lowest index
+                    }
+                }
+                decomp_block_argmin(key, idx, s_key, s_idx);
+                if (idx == DECOMP_NONE) break;
+                double us, ws;
+                tmpc_arith::decomp_local(pts[(size_t)idx * 2], pts[(size_t)idx * 2 + 1], cx, cy, ex, ey, us, ws);
+                bb = tmpc_arith::decomp_shrink(us, ws, a, bb);
+                for (int c = wave; c < n_words; c += 4) {
+                    const unsigned long long m = s_set[c];
+                    if (m == 0ull) continue;
+                    const int i = c * 64 + lane;
+                    bool keep = false;
+                    if ((m >> lane) & 1ull) {
+                        double u, w;
+                        tmpc_arith::decomp_local(pts[(size_t)i * 2], pts[(size_t)i * 2 + 1], cx, cy, ex, ey, u, w);
+                        keep = i != idx && tmpc_arith::decomp_inside(tmpc_arith::decomp_d2(u, w, a, bb));
+                    }
+                    const unsigned long long mk = __ballot(keep);
+                    if (lane == 0) s_set[c] = mk;
+                }
+                __syncthreads();
+            }
+            // the polygon: the tangent row through the closest remaining point, which removes everything behind it
+            for (int c = wave; c < n_words; c += 4) if (lane == 0) s_set[c] = s_box[c];
+            __syncthreads();
+            for (; found < n_rows; found++) {
+                double key = __builtin_huge_val(); int idx = DECOMP_NONE;
+                for (int c = wave; c < n_words; c += 4) {
+                    const unsigned long long m = s_set[c];
+                    if (m == 0ull) continue;
+                    const int i = c * 64 + lane;
+                    if ((m >> lane) & 1ull) {
+                        double u, w;
+                        tmpc_arith::decomp_local(pts[(size_t)i * 2], pts[(size_t)i * 2 + 1], cx, cy, ex, ey, u, w);
+                        const double kk = tmpc_arith::decomp_key(tmpc_arith::decomp_d2(u, w, a, bb));
+                        if (kk < key || idx == DECOMP_NONE) { key = kk; idx = i; }
+                    }
+                }
+                decomp_block_argmin(key, idx, s_key, s_idx);
+                if (idx == DECOMP_NONE) break;
+                const double sx = pts[(size_t)idx * 2], sy = pts[(size_t)idx * 2 + 1];
+                double us, ws, nx, ny, beta;
+                tmpc_arith::decomp_local(sx, sy, cx, cy, ex, ey, us, ws);
+                tmpc_arith::decomp_row(us, ws, a, bb, ex, ey, sx, sy, nx, ny, beta);
+                for (int c = wave; c < n_words; c += 4) {
+                    const unsigned long long m = s_set[c];
+                    if (m == 0ull) continue;
+                    const int i = c * 64 + lane;
+                    bool keep = false;
+                    if ((m >> lane) & 1ull)
+                        keep = i != idx && tmpc_arith::decomp_side(nx, ny, pts[(size_t)i * 2], pts[(size_t)i * 2 + 1], sx, sy) < 0.0;
+                    const unsigned long long mk = __ballot(keep);
+                    if (lane == 0) s_set[c] = mk;
+                }
+                __syncthreads();
+                tmpc_arith::decomp_flip(cx, cy, nx, ny, beta);
+                if (tid == 0) { s_row[found * 3] = nx; s_row[found * 3 + 1] = ny; s_row[found * 3 + 2] = beta; }
+            }
+            if (tid == 0) tmpc_arith::decomp_box_rows(p1x, p1y, p2x, p2y, ex, ey, R, s_row + found * 3);
+            found += 4;
+            limit = found < n_rows ? found : n_rows;
+        }
+    }
+    // the copy (:90-114): rows until the first terminator, dummies behind it
+    if (tid == 0) {
+        int written = 0;
+        while (written < limit && !tmpc_arith::decomp_terminator(s_row[written * 3], s_row[written * 3 + 1])) written++;
+        s_written = written;
+        row_count[unit] = written;
+        status[unit] = k == 0 ? 0 : (!valid || written < limit) ? 2 : (found > n_rows ? 1 : 0);
+    }
+    __syncthreads();
+    const int written = s_written;
+    for (int e = tid; e < n_rows * 3; e += DECOMP_THREADS) {
+        const int r = e / 3, col = e - r * 3;
+        out[e] = r < written ? s_row[e] : (col == 0 ? 1.0 : col == 1 ? 0.0 : dummy_b);
+    }
+}
+
+// DecompConstraints::setParameters (:150-189) from tmpc_decomp_halfspaces_kernel's rows: one thread per (trajectory, stage, row): row r of stage k
+// of scene scene_of[b] into slack row first_row + r of entry b, and ego_disc_0_offset; an entry whose scene is outside [0, n_scenes) is left
+// untouched.  Nothing else is written.
+__global__ void tmpc_set_halfspace_rows_kernel(Dims d, int B, double *params, const double *rows, int n_rows, int first_row, const int *scene_of,
+                                               int n_scenes, double disc_offset)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = d.N;
+    if (e >= B * N * n_rows) return;
+    const int r = e % n_rows, k = (e / n_rows) % N, b = e / (n_rows * N);
+    const int sc = scene_of[b];
+    if (sc < 0 || sc >= n_scenes) return;
+    double *p = params + ((size_t)b * N + k) * d.npar;
+    const double *src = rows + (((size_t)sc * N + k) * n_rows + r) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; c++) p[ip_slk(d, first_row + r, c)] = src[c];
+    if (r == 0) p[ip_disc_offset(d)] = disc_offset;
+}
+
 // ---- f-2: cross-tick state on device ------------------------------------------------------------------------------
 // Warm start of the next tick from the previous tick's solution, without a host round trip.  One thread per
 // (trajectory, node).  mode[b]:

@@ -1404,6 +1404,68 @@ int tmpc_fit_path(tmpc_handle *h, int32_t n_scenes, int32_t n_pts_max, int32_t n
     return TMPC_OK;
 }
 
+int tmpc_costmap_points(tmpc_handle *h, int32_t n_scenes, int32_t size_x, int32_t size_y, const void *d_cost, const void *d_origin, double resolution,
+                        int32_t n_pts_max, void *d_points, void *d_count, void *d_overflow)
+{
+    if (!h) return TMPC_ERR_INVALID;
+    if (n_scenes <= 0) { h->err = "tmpc_costmap_points: n_scenes must be positive"; return TMPC_ERR_INVALID; }
+    if (size_x < 1 || size_y < 1 || (int64_t)size_x * size_y > tmpc::COSTMAP_MAX_CELLS) { h->err = "tmpc_costmap_points: size_x, size_y >= 1 and size_x x size_y <= 2^20"; return TMPC_ERR_INVALID; }
+    if (n_pts_max < 1 || n_pts_max > tmpc::DECOMP_MAX_POINTS) { h->err = "tmpc_costmap_points: 1 <= n_pts_max <= 16384"; return TMPC_ERR_INVALID; }
+    if (!d_cost || !d_origin) { h->err = "tmpc_costmap_points: NULL input (d_cost, d_origin)"; return TMPC_ERR_INVALID; }
+    if (!d_points || !d_count) { h->err = "tmpc_costmap_points: NULL output (d_points, d_count)"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_costmap_points_kernel, dim3((unsigned)n_scenes), dim3(tmpc::DECOMP_THREADS), 0, h->stream, size_x, size_y, resolution, n_pts_max,
+                       (const uint8_t *)d_cost, (const double *)d_origin, (double *)d_points, (int *)d_count, (uint8_t *)d_overflow);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
+int tmpc_decomp_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scenes, int32_t n_seg_max, const void *d_path, const void *d_path_count,
+                           const void *d_path_length, const void *d_s0, const void *d_state_x, const void *d_points, const void *d_count,
+                           int32_t n_pts_max, double range, int32_t n_rows, void *d_rows, void *d_row_count, void *d_status)
+{
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_decomp_halfspaces");
+    if (!h) return TMPC_ERR_INVALID;
+    if (h->B <= 0 || !h->x0) { h->err = "tmpc_decomp_halfspaces: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
+    if (n_scenes <= 0) { h->err = "tmpc_decomp_halfspaces: n_scenes must be positive"; return TMPC_ERR_INVALID; }
+    if (n_seg_max < 1 || n_seg_max > tmpc::PATH_MAX_SEGMENTS) { h->err = "tmpc_decomp_halfspaces: 1 <= n_seg_max <= 1024"; return TMPC_ERR_INVALID; }
+    if (n_pts_max < 1 || n_pts_max > tmpc::DECOMP_MAX_POINTS) { h->err = "tmpc_decomp_halfspaces: 1 <= n_pts_max <= 16384"; return TMPC_ERR_INVALID; }
+    if (n_rows < 1 || n_rows > tmpc::DECOMP_MAX_ROWS) { h->err = "tmpc_decomp_halfspaces: 1 <= n_rows <= 64"; return TMPC_ERR_INVALID; }
+    if (!(range >= 0.0) || !(range < __builtin_huge_val())) { h->err = "tmpc_decomp_halfspaces: range must be finite and not negative"; return TMPC_ERR_INVALID; }
+    if (!d_main_of || !d_path || !d_path_count || !d_path_length || !d_s0 || !d_state_x || !d_points || !d_count) {
+        h->err = "tmpc_decomp_halfspaces: NULL input (d_main_of, d_path, d_path_count, d_path_length, d_s0, d_state_x, d_points, d_count)"; return TMPC_ERR_INVALID;
+    }
+    if (!d_rows || !d_row_count || !d_status) { h->err = "tmpc_decomp_halfspaces: NULL output (d_rows, d_row_count, d_status)"; return TMPC_ERR_INVALID; }
+    const int64_t n = (int64_t)n_scenes * h->d.N;
+    if (n > 0x7fffffff) { h->err = "tmpc_decomp_halfspaces: n_scenes x N too large"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_decomp_halfspaces_kernel, dim3((unsigned)n), dim3(tmpc::DECOMP_THREADS), 0, h->stream, h->d, h->B, n_scenes, h->x0,
+                       (const int *)d_main_of, n_seg_max, (const double *)d_path, (const int *)d_path_count, (const double *)d_path_length,
+                       (const double *)d_s0, (const double *)d_state_x, (const double *)d_points, (const int *)d_count, n_pts_max, range, n_rows,
+                       (double *)d_rows, (int *)d_row_count, (uint8_t *)d_status);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
+int tmpc_set_halfspace_rows(tmpc_handle *h, const void *d_rows, int32_t n_rows, int32_t first_row, const void *d_scene_of, int32_t n_scenes,
+                            double disc_offset)
+{
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_set_halfspace_rows");
+    if (!h) return TMPC_ERR_INVALID;
+    if (h->B <= 0 || !h->params) { h->err = "tmpc_set_halfspace_rows: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
+    if (!d_rows || !d_scene_of || n_scenes <= 0) { h->err = "tmpc_set_halfspace_rows: bad argument (d_rows, d_scene_of, n_scenes > 0)"; return TMPC_ERR_INVALID; }
+    if (n_rows < 1 || first_row < 0 || (int64_t)first_row + n_rows > h->d.n_slk) {
+        h->err = "tmpc_set_halfspace_rows: the rows do not fit (n_rows >= 1, first_row >= 0, first_row + n_rows <= the problem's slack rows)"; return TMPC_ERR_INVALID;
+    }
+    const int64_t n = (int64_t)h->B * h->d.N * n_rows;
+    if (n > 0x7fffffff) { h->err = "tmpc_set_halfspace_rows: B x N x n_rows too large"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_set_halfspace_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B,
+                       const_cast<double *>(h->params), (const double *)d_rows, n_rows, first_row, (const int *)d_scene_of, n_scenes, disc_offset);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
 int tmpc_scenario_halfspaces(tmpc_handle *h, const void *d_samples, int32_t n_pts, int32_t n_rows, const void *d_scene_of,
                              const void *d_state_x, double radius, double disc_offset)
 {

@@ -43,7 +43,7 @@ def generate_solver(out_dir, N=20, max_obstacles=8, num_segments=5, guidance=Tru
                            n_scenario=n_scenario, n_decomp=n_decomp, gaussian=gaussian, add_halfspaces=add_halfspaces)
     return _write_host_side(out_dir, pm, N, slack, n_sqp, dt, n_lin=(max_obstacles + add_halfspaces if guidance else 0),
                             M=(max_obstacles if (ellipsoids or gaussian) else 0), n_slk=n_scenario + n_decomp, num_segments=num_segments,
-                            max_obstacles=max_obstacles, cost_model=int(bool(curvature_aware)), row_model=int(bool(gaussian)))
+                            max_obstacles=max_obstacles, cost_model=int(bool(curvature_aware)), row_model=int(bool(gaussian)), n_decomp=n_decomp)
 
 
 def generate_solver_from_modules(out_dir, name, modules, model, settings, n_sqp=10):
@@ -83,7 +83,7 @@ def _model_map(slack, model=None):
     return out
 
 
-def _write_host_side(out_dir, pm, N, slack, n_sqp, dt, n_lin, M, n_slk, num_segments, max_obstacles, model=None, cost_model=0, row_model=0):
+def _write_host_side(out_dir, pm, N, slack, n_sqp, dt, n_lin, M, n_slk, num_segments, max_obstacles, model=None, cost_model=0, row_model=0, n_decomp=0):
     npar = pm.length()
     nu, nx = 2, 5 + int(bool(slack))
     cfg = os.path.join(out_dir, "config"); inc = os.path.join(out_dir, "include", "mpc_planner_solver")
@@ -101,7 +101,8 @@ def _write_host_side(out_dir, pm, N, slack, n_sqp, dt, n_lin, M, n_slk, num_segm
                 f"#define SOLVER_N {N}\n#define SOLVER_NX {nx}\n#define SOLVER_NU {nu}\n#define SOLVER_NP {npar}\n"
                 f"#define SOLVER_NLIN {n_lin}\n#define SOLVER_M {M}\n"
                 f"#define SOLVER_NSLK {n_slk}\n#define SOLVER_SLACK {int(bool(slack))}\n#define SOLVER_MAX_OBSTACLES {max_obstacles}\n"
-                f"#define SOLVER_S {num_segments}\n#define SOLVER_NSQP {n_sqp}\n#define SOLVER_DT {dt}\n#define SOLVER_COST_MODEL {cost_model}\n#define SOLVER_ROW_MODEL {row_model}\n#endif\n")
+                f"#define SOLVER_S {num_segments}\n#define SOLVER_NSQP {n_sqp}\n#define SOLVER_DT {dt}\n#define SOLVER_COST_MODEL {cost_model}\n#define SOLVER_ROW_MODEL {row_model}\n"
+                + (f"#define SOLVER_NDECOMP {n_decomp}\n" if n_decomp else "") + "#endif\n")      # (of SOLVER_NSLK: the decomp rows, which follow the scenario rows; DecompConstraints is compiled with them)
     with open(os.path.join(inc, "mpc_planner_parameters.h"), "w") as h, \
             open(os.path.join(src, "mpc_planner_parameters.cpp"), "w") as c:
         h.write("/** autogenerated by mpc_planner_amd.generate_solver */\n#ifndef __MPC_PLANNER_PARAMETERS_H__\n"

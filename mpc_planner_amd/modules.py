@@ -987,3 +987,144 @@ def path_velocity_set_parameters(pm, params, window):
     for i in range(len(window)):
         for w, k in enumerate("abcd"):
             params[:, pm.index(f"spline_v{i}_{k}")] = window[i, w]
+
+
+# ---- DecompConstraints::update on a costmap: occupied cells, path polyline, one convex polygon per segment (decomp_constraints.cpp:52-148) ----
+# DecompUtil is not in the reference tree: upstream DecompUtil's LineSegment algorithm restated in the frame of the segment, assumptions in
+# DESIGN.md U16.  Host mirrors of tmpc_costmap_points_kernel / tmpc_decomp_halfspaces_kernel (csrc/tmpc_aux_kernels.hpp) and of
+# mpc_planner_modules/free_space.h, bit for bit: plain IEEE doubles, no fused multiply-add, the operation order below (tmpc_arith's decomp_*).
+
+DECOMP_EPS = 1e-10           # DecompUtil's epsilon_
+DECOMP_TERMINATOR = 1e-3     # a row with a shorter normal (or NaN) ends the copy (decomp_constraints.cpp:98)
+DECOMP_MAX_POINTS = 16384
+COSTMAP_FREE_SPACE = 0       # costmap_2d::FREE_SPACE
+
+
+def costmap_points(cost, origin, resolution, n_pts_max=None):
+    """getOccupiedGridCells (decomp_constraints.cpp:122-148): cost u8 [size_y][size_x] (costmap_2d: index my * size_x + mx); every cell whose
+    cost is not FREE_SPACE (0) becomes its centre (origin_x + (mx + 0.5) resolution, origin_y + (my + 0.5) resolution), mx outer, my inner.
+    n_pts_max: keep the first n_pts_max.  Returns (points [count][2], count, overflow)."""
+    cost = np.asarray(cost)
+    mx, my = np.nonzero(cost.T != COSTMAP_FREE_SPACE)                    # row-major over [size_x][size_y]: mx outer, my inner
+    total = len(mx)
+    if n_pts_max is not None:
+        mx, my = mx[:n_pts_max], my[:n_pts_max]
+    pts = np.stack([float(origin[0]) + (mx.astype(float) + 0.5) * float(resolution),
+                    float(origin[1]) + (my.astype(float) + 0.5) * float(resolution)], 1)
+    return pts, len(pts), bool(total > len(pts))
+
+
+def decomp_path_points(path, length, s0, v, dt):
+    """The polyline of DecompConstraints::update (:68-82): P(s_k), k < len(v), s_0 = s0, s_{k+1} = s_k + v_k dt accumulated left to right, on
+    a whole path [n][9] as fit_path returns it.  Segment i = max{j : start_j <= s} (0 below the first knot), the cubic at t = s - start_i;
+    for s >= length the path continues straight along its end tangent, P(length) + (s - length) P'(length) from the last cubic at
+    t = L_last (U14-3).  Returns (points [len(v)][2], s [len(v)])."""
+    path = np.asarray(path, float)
+    n = len(path)
+    length = float(length)
+    ex, ey, edx, edy = _path_end(path, _path_segment_length(path, length, n - 1))
+    pts = np.zeros((len(v), 2)); ss = np.zeros(len(v))
+    s = float(s0)
+    with np.errstate(all="ignore"):
+        for k in range(len(v)):
+            ss[k] = s
+            if s >= length:
+                pts[k] = (ex + (s - length) * edx, ey + (s - length) * edy)
+            else:
+                i = 0
+                for j in range(n):
+                    if path[j, 8] <= s:
+                        i = j
+                x, y, _, _ = _path_cubic([float(c) for c in path[i, :8]], s - float(path[i, 8]))
+                pts[k] = (x, y)
+            s = s + float(v[k]) * float(dt)
+    return pts, ss
+
+
+def _decomp_argmin(key, members):
+    """The argmin rule: the smallest key (NaN counts as +inf), the lowest point index among equal keys; members: ascending indices."""
+    k = key[members]
+    return int(members[int(np.argmin(np.where(k == k, k, np.inf)))])
+
+
+def decomp_segment(p1, p2, points, R, n_rows, state_x=0.0):
+    """One segment of EllipsoidDecomp2D::dilate + set_constraints as DecompConstraints::update copies it (:83-114; DESIGN.md U16): the rows
+    A p <= b of the convex polygon around p1 -> p2 among `points` [m][2], at most n_rows obstacle rows followed by the four rows of the
+    local box of half width R.  Returns (rows [n_rows][3], count, status): rows i < count as found, the rest the dummy (1, 0, state_x + 100);
+    status 0 complete, 1 truncated (more rows found than n_rows), 2 degenerate (an invalid segment, or a row with |A_i| < 1e-3 or NaN ended
+    the copy early)."""
+    p1x, p1y, p2x, p2y = float(p1[0]), float(p1[1]), float(p2[0]), float(p2[1])
+    o = np.asarray(points, float).reshape(-1, 2)
+    R = float(R)
+    out = np.zeros((n_rows, 3)); out[:] = (1.0, 0.0, float(state_x) + 100.0)
+    with np.errstate(all="ignore"):
+        dx, dy = p2x - p1x, p2y - p1y
+        ln = float(np.sqrt(dx * dx + dy * dy))
+        if not (ln > 0.0 and ln < np.inf):
+            return out, 0, 2
+        ex, ey = dx / ln, dy / ln
+        cx, cy = (p1x + p2x) / 2.0, (p1y + p2y) / 2.0
+        f = ln / 2.0
+        rx, ry = o[:, 0] - cx, o[:, 1] - cy
+        u = rx * ex + ry * ey
+        w = rx * ey - ry * ex
+        box = (np.abs(w) <= R + DECOMP_EPS) & (np.abs(u) <= f + R + DECOMP_EPS)
+        a = b = f
+
+        def d2():
+            ua, wb = u / a, w / b
+            return ua * ua + wb * wb
+
+        inside = box & (np.sqrt(d2()) <= 1.0)
+        while inside.any():
+            j = _decomp_argmin(d2(), np.nonzero(inside)[0])
+            if u[j] < a:
+                ua = u[j] / a
+                b = float(abs(w[j]) / np.sqrt(1.0 - ua * ua))
+            inside &= (1.0 - np.sqrt(d2()) > DECOMP_EPS)
+            inside[j] = False
+        found = []
+        left = box.copy()
+        key = d2()
+        while left.any() and len(found) < n_rows:
+            j = _decomp_argmin(key, np.nonzero(left)[0])
+            gu, gw = u[j] / (a * a), w[j] / (b * b)
+            nrm = np.sqrt(gu * gu + gw * gw)
+            nu, nw = gu / nrm, gw / nrm
+            nx, ny = nu * ex + nw * ey, nu * ey - nw * ex
+            beta = nx * o[j, 0] + ny * o[j, 1]
+            left &= (nx * (o[:, 0] - o[j, 0]) + ny * (o[:, 1] - o[j, 1]) < 0.0)
+            left[j] = False
+            if nx * cx + ny * cy - beta > 0.0:
+                nx, ny, beta = -nx, -ny, -beta
+            found.append((nx, ny, beta))
+        hx, hy = ey, -ex
+        found.append((hx, hy, hx * (p1x + hx * R) + hy * (p1y + hy * R)))
+        found.append((-hx, -hy, -(hx * (p1x - hx * R) + hy * (p1y - hy * R))))
+        found.append((ex, ey, ex * (p2x + ex * R) + ey * (p2y + ey * R)))
+        found.append((-ex, -ey, -(ex * (p1x - ex * R) + ey * (p1y - ey * R))))
+        limit = min(len(found), n_rows)
+        count = 0
+        while count < limit:
+            a1, a2, _ = found[count]
+            if np.sqrt(a1 * a1 + a2 * a2) < DECOMP_TERMINATOR or a1 != a1:
+                break
+            out[count] = found[count]
+            count += 1
+    return out, count, (2 if count < limit else (1 if len(found) > n_rows else 0))
+
+
+def decomp_halfspaces(path, length, s0, v, dt, points, R, n_rows, state_x=0.0):
+    """DecompConstraints::update for one scene (host mirror of tmpc_decomp_halfspaces): the polyline decomp_path_points(path, length, s0,
+    v[:N], dt) of N = len(v) points, segment k into stage k + 1 by decomp_segment, stage 0 all dummies with count 0 and status 0.
+    Returns dict(rows [N][n_rows][3], count [N] i32, status [N] u8, and a1, a2, b [N][n_rows] with NaN where a row is a dummy -- what
+    halfspace_rows_set_parameters takes)."""
+    N = len(v)
+    pts, _ = decomp_path_points(path, length, s0, v, dt)
+    rows = np.zeros((N, n_rows, 3)); rows[:] = (1.0, 0.0, float(state_x) + 100.0)
+    count = np.zeros(N, np.int32); status = np.zeros(N, np.uint8)
+    for k in range(N - 1):
+        rows[k + 1], count[k + 1], status[k + 1] = decomp_segment(pts[k], pts[k + 1], points, R, n_rows, state_x)
+    live = np.arange(n_rows)[None, :] < count[:, None]
+    nan = lambda x: np.where(live, x, np.nan)
+    return dict(rows=rows, count=count, status=status, a1=nan(rows[:, :, 0]), a2=nan(rows[:, :, 1]), b=nan(rows[:, :, 2]))

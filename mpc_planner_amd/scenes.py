@@ -395,6 +395,43 @@ def with_long_path(sc, rng, n_segments=12, seg_len=2.0, shift=0.0, search_range=
     return out
 
 
+def with_costmap(sc, seed, size=100, resolution=0.1):
+    """A scene with the static world of the rosnavigation stack: a costmap_2d occupancy grid (u8 [size][size], index [my][mx], 0 = FREE_SPACE)
+    around the scene's own reference path (sc["path"] with sc["path_length"] if it has a whole path, else sc["segments"]).  The map starts
+    2 m behind the robot and is centred on it across.  Two walls (cost 254, LETHAL_OBSTACLE, 0.3 m thick) run along the path at random half
+    widths 0.9 - 1.6 m to its left and right, and up to six pillars (radius 0.15 - 0.4 m, cost 253, INSCRIBED_INFLATED_OBSTACLE) stand
+    anywhere on the map with their rim at least 0.45 m off the path.  Returns a new dict (the scene is left as it is) with costmap,
+    costmap_origin [2], costmap_resolution, costmap_half_widths (left, right)."""
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    path = np.asarray(sc["path"] if "path" in sc else sc["segments"], float)
+    length = float(sc["path_length"]) if "path_length" in sc else float(2.0 * path[-1, 8] - path[-2, 8]) if len(path) > 1 else 6.0
+    span = size * resolution
+    origin = np.array([float(sc["xinit"][0, 0]) - 2.0, float(sc["xinit"][0, 1]) - span / 2.0])
+    ss = np.arange(-span, min(length, 2.0 * span), resolution / 2.0)
+    pp = np.array([md._road_segment_eval(path[:, :8], path[:, 8], float(s)) for s in ss])              # x, y, dx, dy
+    centre = origin[None, None, :] + (np.stack(np.meshgrid(np.arange(size), np.arange(size), indexing="ij"), -1) + 0.5) * resolution   # [mx][my][2]
+    lateral = np.zeros((size, size))
+    for mx in range(size):                                                  # signed distance to the path, left of travel positive
+        d = centre[mx, :, None, :] - pp[None, :, :2]
+        j = np.argmin((d * d).sum(-1), axis=1)
+        dj = d[np.arange(size), j]
+        lateral[mx] = np.sign(pp[j, 2] * dj[:, 1] - pp[j, 3] * dj[:, 0]) * np.sqrt((dj * dj).sum(-1))
+    half = rng.uniform(0.9, 1.6, 2)
+    cost = np.zeros((size, size), np.uint8)                                 # [mx][my]
+    cost[(lateral >= half[0]) & (lateral < half[0] + 0.3)] = 254
+    cost[(lateral <= -half[1]) & (lateral > -half[1] - 0.3)] = 254
+    for _ in range(int(rng.integers(0, 7))):
+        r = rng.uniform(0.15, 0.4)
+        c = origin + rng.uniform(0.0, span, 2)
+        d = centre - c[None, None, :]
+        disc = (d * d).sum(-1) <= r * r
+        if disc.any() and np.abs(lateral[disc]).min() >= 0.45:
+            cost[disc] = 253
+    out = dict(sc)
+    out.update(costmap=np.ascontiguousarray(cost.T), costmap_origin=origin, costmap_resolution=float(resolution), costmap_half_widths=half)
+    return out
+
+
 def _make_scene_kw(args):
     idx, kw = args
     return make_scene(idx, **kw)

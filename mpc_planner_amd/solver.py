@@ -48,7 +48,8 @@ EXPORTS = ["tmpc_default_dims", "tmpc_default_dims_ex", "tmpc_create", "tmpc_des
            "tmpc_reset_multipliers", "tmpc_get_stream", "tmpc_kernel_info", "tmpc_set_slots", "tmpc_set_param_sharing", "tmpc_copy_state", "tmpc_scenario_empty_stages", "tmpc_sample_scenarios",
            "tmpc_scenario_discard", "tmpc_scenario_discarded", "tmpc_linearize_topology_ex", "tmpc_clear_slot", "tmpc_gather_best",
            "tmpc_create_v2", "tmpc_set_param_sharing_ex", "tmpc_latency_mode_capacity", "tmpc_has_lane_kernels", "tmpc_debug_lds_passes", "tmpc_debug_poison_lds", "tmpc_has_lab_switches",
-           "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters", "tmpc_track_path", "tmpc_set_path_parameters", "tmpc_fit_path"]
+           "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters", "tmpc_track_path", "tmpc_set_path_parameters", "tmpc_fit_path",
+           "tmpc_costmap_points", "tmpc_decomp_halfspaces", "tmpc_set_halfspace_rows"]
 
 
 class TmpcObstacleOptions(C.Structure):
@@ -135,6 +136,10 @@ def load_library(path=None):
         lib.tmpc_set_path_parameters.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
     if hasattr(lib, "tmpc_fit_path"):
         lib.tmpc_fit_path.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 13
+    if hasattr(lib, "tmpc_decomp_halfspaces"):
+        lib.tmpc_costmap_points.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, vp, vp, vp]
+        lib.tmpc_decomp_halfspaces.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 7 + [C.c_int32, C.c_double, C.c_int32, vp, vp, vp]
+        lib.tmpc_set_halfspace_rows.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_double]
     if hasattr(lib, "tmpc_scenario_discarded"):        # (absent from reference builds of earlier rounds used in A/B runs)
         lib.tmpc_scenario_discarded.argtypes = [vp, vp]
     if hasattr(lib, "tmpc_copy_state"):        # (absent from reference builds of earlier rounds used in A/B runs)
@@ -492,6 +497,42 @@ class BatchedSolver:
         self._check(self.lib.tmpc_fit_path(self._h, int(n_scenes), int(n_pts_max), int(n_seg_max), vp(d_xy), vp(d_count), vp(d_s), vp(d_left_xy),
                                            vp(d_right_xy), vp(d_v), vp(d_path), vp(d_path_count), vp(d_path_length), vp(d_bounds), vp(d_velocity),
                                            vp(d_road_width), vp(d_status)), "tmpc_fit_path")
+
+    def costmap_points(self, n_scenes, size_x, size_y, d_cost, d_origin, resolution, n_pts_max, d_points, d_count, d_overflow=None):
+        """Occupied costmap cells to points on device (tmpc_costmap_points; raw device pointers; getOccupiedGridCells,
+        decomp_constraints.cpp:122-148): d_cost u8 [n_scenes][size_y][size_x], d_origin [n_scenes][2] -> the centres of the cells whose cost is
+        not 0, mx outer and my inner, the first n_pts_max of them into d_points [n_scenes][n_pts_max][2], their number into d_count (i32),
+        d_overflow (u8) 1 iff there were more.  Equal bit for bit to modules.costmap_points.  Needs no batch.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_costmap_points"):
+            raise TmpcError("this library has no tmpc_costmap_points (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        self._check(self.lib.tmpc_costmap_points(self._h, int(n_scenes), int(size_x), int(size_y), vp(d_cost), vp(d_origin), float(resolution),
+                                                 int(n_pts_max), vp(d_points), vp(d_count), vp(d_overflow)), "tmpc_costmap_points")
+
+    def decomp_halfspaces(self, d_main_of, n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_s0, d_state_x, d_points, d_count, n_pts_max,
+                          decomp_range, n_rows, d_rows, d_row_count, d_status):
+        """DecompConstraints::update on device (tmpc_decomp_halfspaces; raw device pointers; DESIGN.md U16): per scene the polyline on the whole
+        path d_path / d_path_count / d_path_length (fit_path's layout) from d_s0 along the speeds of the warm start of batch entry
+        d_main_of[scene], one convex polygon per segment among the scene's d_count points of d_points [n_scenes][n_pts_max][2], its rows into
+        d_rows [n_scenes][N][n_rows][3] (dummies (1, 0, d_state_x + 100) included), d_row_count (i32) and d_status (u8: 0 complete, 1
+        truncated, 2 degenerate) [n_scenes][N].  Equal bit for bit to modules.decomp_halfspaces.  Stream-ordered, no synchronisation."""
+        if not hasattr(self.lib, "tmpc_decomp_halfspaces"):
+            raise TmpcError("this library has no tmpc_decomp_halfspaces (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        self._check(self.lib.tmpc_decomp_halfspaces(self._h, vp(d_main_of), int(n_scenes), int(n_seg_max), vp(d_path), vp(d_path_count),
+                                                    vp(d_path_length), vp(d_s0), vp(d_state_x), vp(d_points), vp(d_count), int(n_pts_max),
+                                                    float(decomp_range), int(n_rows), vp(d_rows), vp(d_row_count), vp(d_status)),
+                    "tmpc_decomp_halfspaces")
+
+    def set_halfspace_rows(self, d_rows, n_rows, d_scene_of, n_scenes, first_row=0, disc_offset=0.0):
+        """DecompConstraints::setParameters on device (tmpc_set_halfspace_rows; raw device pointers): d_rows [n_scenes][N][n_rows][3] of every
+        stage into the slack rows first_row .. first_row + n_rows - 1 of every entry of the current batch whose d_scene_of is inside
+        [0, n_scenes), and ego_disc_0_offset; nothing else.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_set_halfspace_rows"):
+            raise TmpcError("this library has no tmpc_set_halfspace_rows (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        self._check(self.lib.tmpc_set_halfspace_rows(self._h, vp(d_rows), int(n_rows), int(first_row), vp(d_scene_of), int(n_scenes),
+                                                     float(disc_offset)), "tmpc_set_halfspace_rows")
 
     def scenario_halfspaces(self, d_samples, n_pts, n_rows, d_scene_of, d_state_x, radius, disc_offset=0.0):
         """Device scenario -> halfspace reduction of SH-MPC (raw device pointers; samples [n_scenes][N][n_pts][2]);

@@ -9,7 +9,10 @@ launches between two HIP events on the handle's stream (launch gaps included: an
 n segments (default 64; 1024 is the cap) of 2 m, searched 2 segments either side of the previous one (local) or over every segment (global: the
 previous segment is put back to -1 before every launch, a 512-int copy that the event times include and the profile lists separately).
 `--fit [--points n]`: the path-fit kernel alone (tmpc_fit_path), 512 scenes of n waypoints (default 65; 1025 is the cap) with bounds and a velocity
-profile -- seven curves per scene --, chord knots; needs no batch.  One JSON line: the mean of 50 launches between two HIP events."""
+profile -- seven curves per scene --, chord knots; needs no batch.  One JSON line: the mean of 50 launches between two HIP events.
+`--decomp [--cells n]`: the free-space kernels alone (tmpc_costmap_points, tmpc_decomp_halfspaces, tmpc_set_halfspace_rows) at cfg 3's shape (N = 30,
+slack model, 12 decomp rows): 512 scenes x 64 trajectories, n x n maps (default 100) from scenes.with_costmap, 16 generated ones repeated, the
+polyline along each scene's own warm start.  One JSON line per kernel with the event time, the points per scene and the rows per stage."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -132,6 +135,51 @@ def fit_kernel(n_pts, n_scenes=512):
     so.close()
 
 
+def decomp_kernels(cells, n_scenes=512, traj=64, N=30, S=5, n_rows=12, n_pts_max=16384):
+    dims = solver.default_dims(N=N, S=S, n_lin=8, M=8, n_slk=n_rows, slack=1)
+    B = n_scenes * traj
+    so = solver.BatchedSolver(dims, B_max=B)
+    f64 = dict(dtype=torch.float64, device=dev)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    gen = [scenes.with_costmap(scenes.make_scene(i, N=N, M=8, B=1, slack=True, n_decomp=n_rows), 5000 + i, size=cells, resolution=10.0 / cells) for i in range(16)]
+    rep = n_scenes // 16
+    x0 = torch.zeros((B, N + 1, 8), **f64)
+    x0[::traj] = up(np.tile(np.stack([g["x0"][0] for g in gen]), (rep, 1, 1)))            # each scene's first entry carries its warm start
+    xinit = torch.zeros((B, 6), **f64); params = torch.zeros((B, N, dims.npar), **f64)
+    so.set_batch_device(B, xinit.data_ptr(), x0.data_ptr(), params.data_ptr())
+    cost = up(np.tile(np.stack([g["costmap"] for g in gen]), (rep, 1, 1))); origin = up(np.tile(np.stack([g["costmap_origin"] for g in gen]), (rep, 1)))
+    path = up(np.tile(np.stack([g["segments"] for g in gen]), (rep, 1, 1))); pc = up(np.full(n_scenes, S, np.int32)); length = up(np.full(n_scenes, 6.0 * S))
+    s0 = torch.zeros(n_scenes, **f64); sx = torch.zeros(n_scenes, **f64)
+    main = up(np.arange(0, B, traj, dtype=np.int32)); scene_of = up(np.repeat(np.arange(n_scenes, dtype=np.int32), traj))
+    pts = torch.zeros((n_scenes, n_pts_max, 2), **f64); cnt = torch.zeros(n_scenes, dtype=torch.int32, device=dev); ov = torch.zeros(n_scenes, dtype=torch.uint8, device=dev)
+    rows = torch.zeros((n_scenes, N, n_rows, 3), **f64); rc = torch.zeros((n_scenes, N), dtype=torch.int32, device=dev); st = torch.zeros((n_scenes, N), dtype=torch.uint8, device=dev)
+    points = lambda: so.costmap_points(n_scenes, cells, cells, cost.data_ptr(), origin.data_ptr(), 10.0 / cells, n_pts_max, pts.data_ptr(), cnt.data_ptr(), ov.data_ptr())
+    decomp = lambda: so.decomp_halfspaces(main.data_ptr(), n_scenes, S, path.data_ptr(), pc.data_ptr(), length.data_ptr(), s0.data_ptr(), sx.data_ptr(), pts.data_ptr(),
+                                          cnt.data_ptr(), n_pts_max, 2.0, n_rows, rows.data_ptr(), rc.data_ptr(), st.data_ptr())
+    write = lambda: so.set_halfspace_rows(rows.data_ptr(), n_rows, scene_of.data_ptr(), n_scenes)
+    hs = torch.cuda.ExternalStream(so.stream_ptr(), device=dev)
+    for name, call in (("tmpc_costmap_points_kernel", points), ("tmpc_decomp_halfspaces_kernel", decomp), ("tmpc_set_halfspace_rows_kernel", write)):
+        for _ in range(5):
+            call()
+        so.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(hs):
+            e0.record()
+        for _ in range(20):
+            call()
+        with torch.cuda.stream(hs):
+            e1.record()
+        so.synchronize()
+        print(json.dumps(dict(kernel=name, n_scenes=n_scenes, trajectories=B, cells=cells, N=N, n_rows=n_rows, points_mean=float(cnt.double().mean().item()),
+                              points_max=int(cnt.max().item()), overflow=int(ov.sum().item()), rows_mean=float(rc[:, 1:].double().mean().item()),
+                              status_counts=[int((st[:, 1:] == v).sum().item()) for v in (0, 1, 2)], us_per_launch_events=e0.elapsed_time(e1) * 1e3 / 20)), flush=True)
+    so.close()
+
+
+if "--decomp" in sys.argv:
+    decomp_kernels(int(sys.argv[sys.argv.index("--cells") + 1]) if "--cells" in sys.argv else 100)
+    print("done")
+    sys.exit(0)
 if "--fit" in sys.argv:
     fit_kernel(int(sys.argv[sys.argv.index("--points") + 1]) if "--points" in sys.argv else 65)
     print("done")
