@@ -431,11 +431,15 @@ int tmpc_set_obstacle_parameters(tmpc_handle *h, const void *d_obstacle_pos, con
  * Equal bit for bit to mpc_planner_amd.modules.track_path (no FMA contraction, same operation order).  One wave per scene, one lane per
  * candidate segment (strided beyond 64 candidates), a 64-lane argmin on (D, segment).  options == NULL: the defaults below.
  * TMPC_ERR_INVALID: a NULL required pointer, one of d_bounds / d_bound_window without the other, n_scenes <= 0, n_seg_max outside [1, 1024],
- * search_range outside [0, 31], pos_stride < 2, an options->size this library cannot honour (like tmpc_obstacle_options), a problem without
- * path segments (S = 0), a generated solver. */
+ * search_range outside [0, 31], pos_stride < 2, an options->size this library cannot honour (like tmpc_obstacle_options; the 8-byte first
+ * revision, without window_segments, is still taken), a problem without path segments (S = 0), window_segments outside [0, 64] or, in a
+ * hand-written build, neither 0 nor the handle's S; a generated solver called without window_segments.
+ * IN A GENERATED SOLVER the handle has no S: the caller supplies it as options->window_segments in [1, 64] (the stack's
+ * contouring/num_segments), and the call then does exactly the above; with 0 or options == NULL it refuses. */
 typedef struct tmpc_path_options {
     uint32_t size;                 /* sizeof(tmpc_path_options) of the caller's header */
     int32_t search_range;          /* R: segments either side of the previous one that are searched; default 2, 0 .. 31 */
+    int32_t window_segments;       /* S of d_window / d_bound_window; default 0: the handle's S.  Since the second revision of this struct */
 } tmpc_path_options;
 int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const void *d_path, const void *d_path_count, const void *d_path_length,
                     const void *d_bounds, const void *d_pos, int32_t pos_stride, const tmpc_path_options *options, void *d_segment,
@@ -454,6 +458,54 @@ int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const v
  * d_closest_s / d_state without the other, a problem without path segments, a generated solver. */
 int tmpc_set_path_parameters(tmpc_handle *h, const void *d_window, const void *d_scene_of, int32_t n_scenes, const void *d_closest_s,
                              void *d_state);
+
+/* ---- the velocity profile along the reference path: what PathReferenceVelocity::setParameters (mpc_planner_modules/src/
+ * path_reference_velocity.cpp:59-95) writes into the spline_v{i}_{a..d} columns every tick, and the value GuidanceConstraints::update hands to
+ * the guidance planner, path_velocity(state.spline) (guidance_constraints.cpp:91-94).  tk::spline::operator() is not in the reference tree: the
+ * evaluation is restated, DESIGN.md U17.  Needs no batch, uses the stream of the handle only, S is an argument (1 <= S <= 64): also available in
+ * a generated solver.  Stream-ordered, no allocation, no synchronisation.  Inputs (device):
+ *   d_velocity     f64 [n_scenes][n_seg_max][4]   (a b c d) of v(s) per segment as tmpc_fit_path writes it, or NULL: no scene has a profile
+ *   d_path         f64 [n_scenes][n_seg_max][9]   the paths (only the `start` column is read);  1 <= n_seg_max <= 1024
+ *   d_path_count   i32 [n_scenes]                 segments of the scene's path, clipped to [0, n_seg_max]
+ *   d_path_length  f64 [n_scenes]                 the last knot; part of a path's triple and required, but not read: beyond it v continues the
+ *                                                 last cubic (U17)
+ *   d_segment      i32 [n_scenes]                 the closest segment as tmpc_track_path wrote it; clamped into [0, count - 1] before use, so that
+ *                                                 -1 or a stale value never indexes out of range
+ *   d_closest_s    f64 [n_scenes]                 as tmpc_track_path wrote it
+ *   d_has_velocity u8  [n_scenes]                 or NULL: every scene has a profile if d_velocity is given (reference_path.hasVelocity())
+ *   reference_velocity                            CONFIG["weights"]["reference_velocity"]
+ * A scene is WITHOUT A PROFILE if d_velocity is NULL, its flag is 0 or its count <= 0.  Outputs (device, caller-owned, every entry written):
+ *   d_window       f64 [n_scenes][S][4]           slot w = velocity segment `segment + w`; a slot at or beyond count is (0, 0, 0, 0) -- "brake at
+ *                                                 the end" (:71-78); without a profile every slot is (0, 0, 0, reference_velocity) (:86-95)
+ *   d_v_ref        f64 [n_scenes]                 or NULL: with a profile v(s) at s = closest_s -- the cubic of segment i = max{j <= count - 1 :
+ *                                                 start_j <= s}, 0 if there is none, at t = s - start_i, ((a t + b) t + c) t + d in Horner form;
+ *                                                 without a profile reference_velocity
+ * Equal bit for bit to mpc_planner_amd.modules.path_velocity_window (called with a segment inside the path) and path_velocity_at (no FMA
+ * contraction).  One wave per scene; the lookup is a ballot over strided start_j <= s tests.
+ * TMPC_ERR_INVALID, before any launch: a NULL required pointer (d_path, d_path_count, d_path_length, d_segment, d_closest_s, d_window),
+ * n_scenes <= 0, n_seg_max outside [1, 1024], S outside [1, 64]. */
+int tmpc_path_velocity_window(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, int32_t S, const void *d_velocity, const void *d_path,
+                              const void *d_path_count, const void *d_path_length, const void *d_segment, const void *d_closest_s,
+                              const void *d_has_velocity, double reference_velocity, void *d_window, void *d_v_ref);
+
+/* ---- caller-chosen columns of the CURRENT batch's parameter rows, in place: the parameter writer of generated solvers, whose row layout is
+ * the module stack's and whose column numbers the caller has in the stack's parameter map (<name>_meta.json "parameter_map"); available in
+ * every build.  Nothing but the named columns is touched.
+ *   cols           i32 [n_cols], HOST             1 <= n_cols <= 128, every entry in [0, npar), all distinct (a duplicate would make the value
+ *                                                 written depend on thread order: refused); copied before the call returns
+ *   d_values       f64 [n_scenes][n_cols]         per_stage 0: row of scene d_scene_of[b] into every stage k < N of entry b
+ *                  f64 [n_scenes][N][n_cols]      per_stage 1: stage k from row k -- for rows produced per stage, such as those
+ *                                                 tmpc_decomp_halfspaces and tmpc_road_halfspaces leave in caller buffers
+ *   d_scene_of     i32 [B]                        an entry whose scene is outside [0, n_scenes) is left untouched
+ * With cols = the spline columns and d_values = tmpc_track_path's d_window it writes what tmpc_set_path_parameters writes; with the
+ * spline_v{i}_{a..d} columns and tmpc_path_velocity_window's d_window, PathReferenceVelocity::setParameters.  Parameter sharing as for
+ * tmpc_set_path_parameters: a map stays valid when every entry of a set names the same scene, and a caller with
+ * TMPC_SHARE_COPIES_NOT_MAINTAINED can name the lead entries only.  One thread per (entry, stage, column); both models' strides.
+ * Stream-ordered, no allocation, no synchronisation.
+ * TMPC_ERR_INVALID, before any launch: no batch, a NULL cols / d_values / d_scene_of, n_scenes <= 0, n_cols outside [1, 128], a column outside
+ * [0, npar), a duplicate column, per_stage neither 0 nor 1. */
+int tmpc_scatter_parameters(tmpc_handle *h, const int32_t *cols, int32_t n_cols, const void *d_values, int32_t per_stage, const void *d_scene_of,
+                            int32_t n_scenes);
 
 /* ---- reference paths fitted on device: waypoints -> the cubic segments tmpc_track_path reads.  What Contouring::onDataReceived
  * (mpc_planner_modules/src/contouring.cpp:126-157) and PathReferenceVelocity::onDataReceived (path_reference_velocity.cpp:28-40) do when a

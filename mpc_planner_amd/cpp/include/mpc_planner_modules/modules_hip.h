@@ -4,6 +4,7 @@
  *
  *   MPCBaseModule::setParameters          mpc_planner_modules/src/mpc_base.cpp:23-35
  *   Contouring::update / setParameters / constructRoadConstraints      mpc_planner_modules/src/contouring.cpp:28-124, 181-262
+ *   PathReferenceVelocity::update / onDataReceived / setParameters      path_reference_velocity.cpp:17-95
  *   EllipsoidConstraints::update / setParameters      ellipsoid_constraints.cpp:23-90
  *   LinearizedConstraints::update / projectToSafety / setParameters      linearized_constraints.cpp:49-189
  *   GuidanceConstraints::optimize / initializeSolverWithGuidance / FindBestPlanner      guidance_constraints.cpp:264-434
@@ -235,6 +236,51 @@ namespace MPCPlanner
         int _closest_segment{-1};
         bool _path_mode{false};
     };
+
+#ifdef SOLVER_PATH_VELOCITY         /* the stack has the spline_v{i}_{a..d} columns (PathReferenceVelocityModule) */
+    /* ---- path_reference_velocity.cpp:17-95.  The velocity along the path as a natural cubic spline on the centreline's knots
+     * (PathVelocityProfile, mpc_planner_modules/reference_path.h), its window into the spline_v columns.  The batched device
+     * twin is BatchedPathTracking::setVelocityParameters (tmpc_path_velocity_window + tmpc_scatter_parameters). ---- */
+    class PathReferenceVelocity
+    {
+    public:
+        PathReferenceVelocity(std::shared_ptr<Solver> solver, const ModuleConfig &cfg) : _solver(solver), _cfg(cfg) {}
+        /* (:17-26) publish the profile for the modules that read it (GuidanceConstraints: path_velocity(state.spline)) */
+        void update(State &, const RealTimeData &, ModuleData &module_data)
+        {
+            if (module_data.path_velocity == nullptr && _velocity_spline != nullptr) module_data.path_velocity = _velocity_spline;
+        }
+        /* (:28-40) a new path with a velocity at every waypoint: v(s) through (t_i, v_i), t = the centreline's knots (the path's s if given,
+         * else chord lengths: ReferencePathSpline::knots).  An invalid path (or another number of velocities) leaves no profile. */
+        void onDataReceived(RealTimeData &data, std::string &&data_name)
+        {
+            if (data_name != "reference_path") return;
+            const ReferencePath &points = data.reference_path_points;
+            if (!points.hasVelocity()) return;
+            auto profile = std::make_shared<PathVelocityProfile>();
+            _velocity_spline = profile->fit(ReferencePathSpline::knots(points.x, points.y, points.s), points.v) ? profile : nullptr;
+        }
+        /* (:42-95) the num_segments cubics from module_data.current_path_segment on, zeros at or beyond the path's end ("brake at the end");
+         * without a profile v = d = weights/reference_velocity in every slot */
+        void setParameters(const RealTimeData &data, const ModuleData &module_data, int k) { setParameters(_solver->_params, data, module_data, k); }
+        /* the same into any parameter block (Solver-free: tests, callers that stage rows themselves) */
+        void setParameters(AcadosParameters &params, const RealTimeData &data, const ModuleData &module_data, int k) const
+        {
+            const bool profile = data.reference_path_points.hasVelocity() && _velocity_spline != nullptr;
+            const int first = module_data.current_path_segment < 0 ? 0 : module_data.current_path_segment;
+            for (int i = 0; i < _cfg.num_segments; i++) {
+                double a = 0., b = 0., c = 0., d = _cfg.weights.at("reference_velocity");
+                if (profile) _velocity_spline->getParameters(first + i, a, b, c, d);
+                setSolverParameterSplineVA(k, params, a, i); setSolverParameterSplineVB(k, params, b, i);
+                setSolverParameterSplineVC(k, params, c, i); setSolverParameterSplineVD(k, params, d, i);
+            }
+        }
+        std::shared_ptr<Solver> _solver;
+    private:
+        ModuleConfig _cfg;
+        std::shared_ptr<PathVelocityProfile> _velocity_spline;
+    };
+#endif
 
 #ifndef SOLVER_ROW_MODEL          /* (dims headers written before the Gaussian rows existed) */
 #define SOLVER_ROW_MODEL 0

@@ -5,7 +5,7 @@
  * header.  RosTools::Spline2D is not in the reference tree: the search is restated, its assumptions are DESIGN.md U14.  The arithmetic is that
  * of mpc_planner_types/prep_arithmetic.h, the one source tmpc_track_path_kernel and tmpc_fit_path_kernel compile too; the independent
  * statement both are tested against, bit for bit, is mpc_planner_amd/modules.py (closest_point_on_segment, find_closest_point, path_window,
- * fit_cubic) -- where the compiler does not fuse multiply-adds (build with -ffp-contract=off on a target that has them).
+ * fit_cubic; PathVelocityProfile: path_velocity_at, path_velocity_window) -- where the compiler does not fuse multiply-adds (build with -ffp-contract=off on a target that has them).
  */
 #ifndef MPC_REFERENCE_PATH_HIP_H
 #define MPC_REFERENCE_PATH_HIP_H
@@ -175,6 +175,44 @@ namespace MPCPlanner
             double x, y, dx, dy;
             cubic(segments[n - 1], segmentLength(n - 1), x, y, dx, dy);
             return tmpc_arith::within_distance(x, y, p(0), p(1), 1.0);
+        }
+    };
+
+    /* The velocity profile along a path: what the reference keeps as a tk::spline through (s_i, v_i) (PathReferenceVelocity::onDataReceived,
+     * path_reference_velocity.cpp:28-40), here the natural cubic spline of fitCubic on the centreline's knots with the evaluation
+     * of DESIGN.md U17: tk::spline::operator() is not in the reference tree.  Bit for bit modules.py::fit_cubic / path_velocity_at /
+     * path_velocity_window and tmpc_path_velocity_window_kernel. */
+    struct PathVelocityProfile
+    {
+        std::vector<double> start, a, b, c, d;                  /* one cubic per segment: v(s) = ((a t + b) t + c) t + d on t = s - start */
+        double length{0.};                                      /* the last knot */
+
+        bool empty() const { return start.empty(); }
+        int numSegments() const { return (int)start.size(); }
+        /* through (t_i, v_i); false -- and the profile empty -- on invalid knots or another number of values */
+        bool fit(const std::vector<double> &t, const std::vector<double> &v)
+        {
+            start.clear(); length = 0.;
+            if (!ReferencePathSpline::fitCubic(t, v, a, b, c, d)) { a.clear(); b.clear(); c.clear(); d.clear(); return false; }
+            start.assign(t.begin(), t.end() - 1);
+            length = t.back();
+            return true;
+        }
+        /* (a b c d) of segment `index`; at or beyond the last segment (0, 0, 0, 0): brake at the end (:71-78).  index >= 0 */
+        void getParameters(int index, double &pa, double &pb, double &pc, double &pd) const
+        {
+            if (index < numSegments()) { pa = a[index]; pb = b[index]; pc = c[index]; pd = d[index]; }
+            else { pa = 0.; pb = 0.; pc = 0.; pd = 0.; }
+        }
+        /* v(s): the cubic of segment i = max{j : start_j <= s}, 0 if there is none; beyond the last knot the last cubic continues (U17).
+         * An empty profile has no value: 0. */
+        double operator()(double s) const
+        {
+            if (empty()) return 0.;
+            int i = 0;
+            for (int j = 0; j < numSegments(); j++) if (start[j] <= s) i = j;
+            const double k[4] = {a[i], b[i], c[i], d[i]};
+            return tmpc_arith::cubic_value(k, s - start[i]);
         }
     };
 }

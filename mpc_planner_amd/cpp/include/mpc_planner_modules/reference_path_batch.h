@@ -5,7 +5,11 @@
  * enqueues tmpc_track_path -- closest point from the previous segment, the window of S segments, the bound window, the objective-reached flag
  * -- and setParameters() enqueues tmpc_set_path_parameters, which writes the spline columns of the handle's current batch and, optionally,
  * the `spline` entry of a device state buffer: what Contouring::update / setSplineParameters do per scene on the host (contouring.cpp:28-48,
- * :94-124), bit for bit.  boundWindow() is then ready for tmpc_road_halfspaces (d_bound_segments).  For callers of the C-ABI
+ * :94-124), bit for bit.  boundWindow() is then ready for tmpc_road_halfspaces (d_bound_segments).  With a velocity at every waypoint of
+ * every path, setWaypoints() also fits the velocity profiles (PathReferenceVelocity::onDataReceived) and setVelocityParameters() enqueues
+ * tmpc_path_velocity_window and tmpc_scatter_parameters: the spline_v columns of a generated stack, and referenceVelocity() for the guidance
+ * planner (path_reference_velocity.cpp:59-95, guidance_constraints.cpp:91-94).  In a generated solver, whose handle has no S, track() passes the
+ * twin's S as tmpc_path_options::window_segments and setSplineParameters() takes the place of setParameters().  For callers of the C-ABI
  * (include/tmpc_hip.h) that keep a launch of many scenes on the device; needs the HIP runtime header (compile with -D__HIP_PLATFORM_AMD__
  * and the ROCm include directory).  Everything is enqueued on the handle's stream; setPaths() and setParameters() wait for their own uploads
  * (the staging memory is their own), not for the kernels.
@@ -32,7 +36,8 @@ namespace MPCPlanner
         }
         ~BatchedPathTracking()
         {
-            for (void *p : {_d_path, _d_count, _d_length, _d_segment, _d_closest_s, _d_window, _d_reached, _d_bounds, _d_bound_window, _d_waypoints, _d_status, _d_road_width}) if (p) (void)hipFree(p);
+            for (void *p : {_d_path, _d_count, _d_length, _d_segment, _d_closest_s, _d_window, _d_reached, _d_bounds, _d_bound_window, _d_waypoints, _d_status, _d_road_width,
+                            _d_velocity, _d_velocity_window, _d_v_ref}) if (p) (void)hipFree(p);
         }
         BatchedPathTracking(const BatchedPathTracking &) = delete;
         BatchedPathTracking &operator=(const BatchedPathTracking &) = delete;
@@ -44,6 +49,7 @@ namespace MPCPlanner
         {
             const size_t Q = (size_t)_Q, R = (size_t)_R;
             if (paths.size() != Q) fail("setPaths: one path per scene");
+            _with_velocity = false;                                           // fitted cubics carry no velocity profile
             std::vector<double> path(Q * R * 9, 0.), length(Q, 0.), bounds(_with_bounds ? Q * 2 * R * 8 : 0, 0.);
             std::vector<int> count(Q), segment(Q, -1);
             for (size_t q = 0; q < Q; q++) {
@@ -67,7 +73,9 @@ namespace MPCPlanner
          * waypoints of all scenes, their bounds, their s and the counts in one staging block), one kernel.  Waypoints beyond n_seg_max + 1
          * are not seen.  Knots: the paths' s if EVERY path carries one, chord lengths if none does.  with_bounds: left / right hold one
          * Boundary per scene with the centreline's point count.  An invalid scene (fewer than two waypoints, a repeated waypoint) gets
-         * count 0: track() leaves it alone; status() tells.  Every scene's previous segment goes back to -1. */
+         * count 0: track() leaves it alone; status() tells.  Every scene's previous segment goes back to -1.  When EVERY path has a velocity
+         * at each waypoint (ReferencePath::hasVelocity) the velocity profiles are fitted in the same launch, on the centreline's knots;
+         * otherwise no scene has a profile and setVelocityParameters() writes the constant reference velocity. */
         void setWaypoints(const std::vector<ReferencePath> &paths, const std::vector<Boundary> *left = nullptr, const std::vector<Boundary> *right = nullptr)
         {
             const size_t Q = (size_t)_Q, P = (size_t)_R + 1;
@@ -76,14 +84,18 @@ namespace MPCPlanner
             size_t with_s = 0;
             for (const ReferencePath &p : paths) with_s += p.hasDistance() ? 1 : 0;
             if (with_s != 0 && with_s != Q) fail("setWaypoints: s for every path or for none");
-            // one staging block: xy [Q][P][2], s [Q][P], left [Q][P][2], right [Q][P][2] (doubles), then count and segment [Q] each (ints)
-            const size_t o_xy = 0, o_s = o_xy + Q * P * 2, o_left = o_s + Q * P, o_right = o_left + Q * P * 2, n_dbl = o_right + Q * P * 2;
+            size_t with_v = 0;
+            for (const ReferencePath &p : paths) with_v += p.hasVelocity() ? 1 : 0;
+            _with_velocity = with_v == Q;
+            // one staging block: xy [Q][P][2], s [Q][P], left [Q][P][2], right [Q][P][2], v [Q][P] (doubles), then count and segment [Q] each (ints)
+            const size_t o_xy = 0, o_s = o_xy + Q * P * 2, o_left = o_s + Q * P, o_right = o_left + Q * P * 2, o_v = o_right + Q * P * 2, n_dbl = o_v + Q * P;
             const size_t bytes = n_dbl * 8 + 2 * Q * sizeof(int);
             std::vector<double> stage(n_dbl + (2 * Q * sizeof(int) + 7) / 8, 0.);
             int *count = reinterpret_cast<int *>(stage.data() + n_dbl), *segment = count + Q;
             for (size_t q = 0; q < Q; q++) {
                 const ReferencePath &p = paths[q];
                 if (p.y.size() != p.x.size() || (p.hasDistance() && p.s.size() != p.x.size())) fail("setWaypoints: x, y and s of one length");
+                if (_with_velocity && p.v.size() != p.x.size()) fail("setWaypoints: a velocity per waypoint");
                 const size_t n = p.x.size() < P ? p.x.size() : P;
                 count[q] = (int)n; segment[q] = -1;
                 if (_with_bounds)
@@ -91,6 +103,7 @@ namespace MPCPlanner
                 for (size_t i = 0; i < n; i++) {
                     stage[o_xy + (q * P + i) * 2] = p.x[i]; stage[o_xy + (q * P + i) * 2 + 1] = p.y[i];
                     if (with_s) stage[o_s + q * P + i] = p.s[i];
+                    if (_with_velocity) stage[o_v + q * P + i] = p.v[i];
                     if (_with_bounds) {
                         stage[o_left + (q * P + i) * 2] = (*left)[q].x[i]; stage[o_left + (q * P + i) * 2 + 1] = (*left)[q].y[i];
                         stage[o_right + (q * P + i) * 2] = (*right)[q].x[i]; stage[o_right + (q * P + i) * 2 + 1] = (*right)[q].y[i];
@@ -98,13 +111,15 @@ namespace MPCPlanner
                 }
             }
             if (!_d_waypoints) { alloc(_d_waypoints, bytes); alloc(_d_status, Q); alloc(_d_road_width, Q * 8); }
+            if (_with_velocity && !_d_velocity) alloc(_d_velocity, Q * (size_t)_R * 4 * 8);
             void *stream = this->stream();
             copy(_d_waypoints, stage.data(), bytes, stream);
             double *base = static_cast<double *>(_d_waypoints);
             int *d_count_in = reinterpret_cast<int *>(base + n_dbl);
             if (hipMemcpyAsync(_d_segment, d_count_in + Q, Q * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) fail("hipMemcpyAsync");
             if (tmpc_fit_path(_h, _Q, (int)P, _R, base + o_xy, d_count_in, with_s ? base + o_s : nullptr, _with_bounds ? base + o_left : nullptr,
-                              _with_bounds ? base + o_right : nullptr, nullptr, _d_path, _d_count, _d_length, _with_bounds ? _d_bounds : nullptr, nullptr,
+                              _with_bounds ? base + o_right : nullptr, _with_velocity ? base + o_v : nullptr, _d_path, _d_count, _d_length,
+                              _with_bounds ? _d_bounds : nullptr, _with_velocity ? _d_velocity : nullptr,
                               _with_bounds ? _d_road_width : nullptr, _d_status)) fail(tmpc_last_error(_h));
             sync(stream);                                                     // the staging vector ends with this call
         }
@@ -131,7 +146,7 @@ namespace MPCPlanner
         void track(const void *d_pos, int pos_stride, int search_range = 2)
         {
             tmpc_path_options opt{};
-            opt.size = sizeof(opt); opt.search_range = search_range;
+            opt.size = sizeof(opt); opt.search_range = search_range; opt.window_segments = _S;     /* a generated solver's handle has no S of its own */
             if (tmpc_track_path(_h, _Q, _R, _d_path, _d_count, _d_length, _d_bounds, d_pos, pos_stride, &opt, _d_segment, _d_closest_s, _d_window, _d_bound_window,
                                 _d_reached)) fail(tmpc_last_error(_h));
         }
@@ -144,6 +159,30 @@ namespace MPCPlanner
         {
             if (tmpc_set_path_parameters(_h, _d_window, uploadSceneOf(scene_of), _Q, d_state ? _d_closest_s : nullptr, d_state)) fail(tmpc_last_error(_h));
         }
+
+        /* The same columns in a GENERATED solver, where tmpc_set_path_parameters refuses: cols = the 9 S columns of the stack's parameter map in
+         * the window's order, spline_x{i}_a .. _d, spline_y{i}_a .. _d, spline{i}_start for i = 0 .. S - 1 (tmpc_scatter_parameters). */
+        void setSplineParameters(const std::vector<int> &scene_of, const std::vector<int32_t> &cols)
+        {
+            if ((int)cols.size() != 9 * _S) fail("setSplineParameters: 9 S columns");
+            if (tmpc_scatter_parameters(_h, cols.data(), (int32_t)cols.size(), _d_window, 0, uploadSceneOf(scene_of), _Q)) fail(tmpc_last_error(_h));
+        }
+        /* PathReferenceVelocity::setParameters for every scene, after track(): the S velocity cubics from the segment found on -- zeros beyond
+         * the path's end, (0, 0, 0, reference_velocity) without profiles -- into cols, the 4 S columns spline_v{i}_a .. _d, i = 0 .. S - 1, of every
+         * stage of every entry of the CURRENT batch whose scene_of is inside [0, n_scenes); and referenceVelocity().  Enqueued. */
+        void setVelocityParameters(const std::vector<int> &scene_of, const std::vector<int32_t> &cols, double reference_velocity)
+        {
+            if ((int)cols.size() != 4 * _S) fail("setVelocityParameters: 4 S columns");
+            if (!_d_velocity_window) { alloc(_d_velocity_window, (size_t)_Q * _S * 4 * 8); alloc(_d_v_ref, (size_t)_Q * 8); }
+            if (tmpc_path_velocity_window(_h, _Q, _R, _S, _with_velocity ? _d_velocity : nullptr, _d_path, _d_count, _d_length, _d_segment, _d_closest_s, nullptr,
+                                          reference_velocity, _d_velocity_window, _d_v_ref)) fail(tmpc_last_error(_h));
+            if (tmpc_scatter_parameters(_h, cols.data(), (int32_t)cols.size(), _d_velocity_window, 0, uploadSceneOf(scene_of), _Q)) fail(tmpc_last_error(_h));
+        }
+        /* after setVelocityParameters(): f64 [n_scenes], the profile at closest_s (or reference_velocity): what the guidance planner is given
+         * (guidance_constraints.cpp:91-94); the window [n_scenes][S][4]; the fitted profiles [n_scenes][n_seg_max][4] or nullptr.  Device buffers */
+        const void *referenceVelocity() const { return _d_v_ref; }
+        const void *velocityWindow() const { return _d_velocity_window; }
+        const void *velocities() const { return _with_velocity ? _d_velocity : nullptr; }
 
         /* device buffers, valid after track(): the window [n_scenes][S][9], the bound window [n_scenes][2][S][8] (what tmpc_road_halfspaces takes
          * as d_bound_segments; nullptr without bounds), closest_s [n_scenes], the segment found (i32) and the reached flag (u8) per scene */
@@ -163,10 +202,11 @@ namespace MPCPlanner
 
     private:
         int _Q, _R, _S;
-        bool _with_bounds;
+        bool _with_bounds, _with_velocity{false};
         void *_d_path{nullptr}, *_d_count{nullptr}, *_d_length{nullptr}, *_d_segment{nullptr}, *_d_closest_s{nullptr}, *_d_window{nullptr}, *_d_reached{nullptr};
         void *_d_bounds{nullptr}, *_d_bound_window{nullptr};
         void *_d_waypoints{nullptr}, *_d_status{nullptr}, *_d_road_width{nullptr};       /* setWaypoints(): allocated on its first call */
+        void *_d_velocity{nullptr}, *_d_velocity_window{nullptr}, *_d_v_ref{nullptr};    /* the velocity profiles: allocated on first use */
     };
 }
 #endif

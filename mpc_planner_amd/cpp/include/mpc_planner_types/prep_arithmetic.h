@@ -32,6 +32,9 @@ namespace tmpc_arith
         dy = (3.0 * c[4] * t + 2.0 * c[5]) * t + c[6];
     }
 
+    /* ---- scalar cubic c = (a b c d): its value at t, Horner form (the velocity profile v(s) on t = s - start) ---- */
+    TMPC_ARITH_FN double cubic_value(const double c[4], double t) { TMPC_ARITH_NO_FMA return ((c[0] * t + c[1]) * t + c[2]) * t + c[3]; }
+
     /* ---- closest point of the cubic on t in [0, L] to (px, py) (RosTools::Spline2D::findClosestPoint restated): D = |P(t) - p|^2,
      * g = (P(t) - p).P'(t).  Nine coarse samples t_j = L (j / 8), the bracket around the best (lowest j on ties), an end of the bracket if g does
      * not change sign inside it, else exactly 40 bisections (no data-dependent exit) and the bracket's midpoint; the coarse sample wins if its D

@@ -568,6 +568,72 @@ __global__ __launch_bounds__(64) void tmpc_fit_path_kernel(int n_pts_max, int n_
     }
 }
 
+// ---- the velocity profile along the path: PathReferenceVelocity::setParameters (path_reference_velocity.cpp:59-95) and the value the guidance
+// planner is given, path_velocity(state.spline) (guidance_constraints.cpp:91-94).  tk::spline::operator() is not in the reference tree: the
+// evaluation is restated as DESIGN.md U17.  Bit-equal to the independent modules.py::path_velocity_window / path_velocity_at.
+constexpr int VELOCITY_MAX_WINDOW = 64;
+
+// One wave per scene q.  A scene has a profile iff velocity is given, its flag (all ones if has_velocity is NULL) is set and count > 0.
+// With one: slot w < S of window [n_scenes][S][4] = velocity segment seg + w, seg = segment[q] clamped into [0, n - 1], or (0, 0, 0, 0) at or
+// beyond n ("brake at the end"); v_ref[q] = the cubic of segment i = max{j < n : start_j <= s} (0 if there is none, U12's lookup) at
+// t = s - start_i, s = closest_s[q] -- the lanes test start_j <= s sixty-four segments at a time, a ballot gives the highest j of each
+// round, so 1024 segments cost 16 comparisons per lane and the result does not depend on the knots being sorted.  Without one: every slot
+// (0, 0, 0, reference_velocity), v_ref = reference_velocity.  The lanes stride over the S x 4 copies; lane 0 evaluates the cubic.  No LDS.
+__global__ __launch_bounds__(64) void tmpc_path_velocity_window_kernel(int S, int n_seg_max, const double *velocity, const double *path, const int *count,
+                                                                       const int *segment, const double *closest_s, const uint8_t *has_velocity,
+                                                                       double reference_velocity, double *window, double *v_ref)
+{
+#pragma clang fp contract(off)
+    const int q = blockIdx.x, lane = threadIdx.x;
+    int n = count[q];
+    n = n > n_seg_max ? n_seg_max : n;
+    const bool profile = velocity != nullptr && n > 0 && (has_velocity == nullptr || has_velocity[q] != 0);
+    double *wq = window + (size_t)q * S * 4;
+    if (!profile) {
+        for (int e = lane; e < S * 4; e += 64) wq[e] = (e & 3) == 3 ? reference_velocity : 0.0;
+        if (v_ref && lane == 0) v_ref[q] = reference_velocity;
+        return;
+    }
+    const double *vq = velocity + (size_t)q * n_seg_max * 4;
+    int seg = segment[q];
+    seg = seg < 0 ? 0 : (seg > n - 1 ? n - 1 : seg);
+    for (int e = lane; e < S * 4; e += 64) {
+        const int i = seg + (e >> 2);
+        wq[e] = i < n ? vq[(size_t)i * 4 + (e & 3)] : 0.0;
+    }
+    if (!v_ref) return;
+    const double *pq = path + (size_t)q * n_seg_max * 9;
+    const double s = closest_s[q];
+    int found = 0;
+    for (int base = 0; base < n; base += 64) {                             // n is the scene's: every lane of the wave runs the same rounds
+        const int j = base + lane;
+        const unsigned long long hit = __ballot(j < n && pq[(size_t)j * 9 + 8] <= s);
+        if (hit) found = base + 63 - __builtin_clzll(hit);                 // ascending rounds: the last hit is the highest j
+    }
+    if (lane == 0) v_ref[q] = tmpc_arith::cubic_value(vq + (size_t)found * 4, s - pq[(size_t)found * 9 + 8]);
+}
+
+// ---- caller-chosen columns of the current batch's parameter rows: the writer for generated solvers, whose column numbers the caller has in the
+// stack's parameter map.  The column list travels by value (at most 128 entries: 516 bytes of kernel arguments).
+constexpr int SCATTER_MAX_COLS = 128;
+struct ScatterCols { int n; int col[SCATTER_MAX_COLS]; };
+
+// one thread per (entry b, stage k < N, listed column c): params[b][k][col[c]] = values[scene_of[b]][c] (per_stage 0: values [n_scenes][n_cols])
+// or values[scene_of[b]][k][c] (per_stage 1: values [n_scenes][N][n_cols]); an entry whose scene is outside [0, n_scenes) is left untouched.
+// The host has checked every column against npar and the list for duplicates, so no two threads write one address.  Both models' strides.
+__global__ void tmpc_scatter_parameters_kernel(Dims d, int B, double *params, ScatterCols cols, const double *values, const int *scene_of, int n_scenes,
+                                               int per_stage)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = d.N, nc = cols.n;
+    if (e >= B * N * nc) return;
+    const int c = e % nc, k = (e / nc) % N, b = e / (nc * N);
+    const int sc = scene_of[b];
+    if (sc < 0 || sc >= n_scenes) return;
+    const double *src = values + (per_stage ? ((size_t)sc * N + k) * nc : (size_t)sc * nc);
+    params[((size_t)b * N + k) * d.npar + cols.col[c]] = src[c];
+}
+
 
 // ---- f-3: scenario -> polygon on device (SH-MPC, BASELINE config 5) ------------------------------------------------
 // The reference delegates this to the external scenario_module (scenario_constraints.cpp:47,76-79; source absent), so

@@ -482,11 +482,18 @@ struct tmpc_handle {
 #endif
 
 // An options struct of the C-ABI (its first field: uint32_t size).  `o` holds the defaults and keeps them when the caller passes NULL; like
-// tmpc_create_v2, the caller's struct may be longer (a newer header) only with a zero tail, and there is no shorter revision.
-template <class Options> static bool read_options(tmpc_handle *h, const char *fn, const char *type, const Options *options, Options &o)
+// tmpc_create_v2, the caller's struct may be longer (a newer header) only with a zero tail, and shorter only at `first_revision`, the size of
+// the struct before fields were appended to it: the appended fields then keep their defaults.
+template <class Options> static bool read_options(tmpc_handle *h, const char *fn, const char *type, const Options *options, Options &o,
+                                                  uint32_t first_revision = sizeof(Options))
 {
     if (!options) return true;
-    if (options->size < sizeof(o)) { h->err = std::string(fn) + ": options->size is smaller than " + type; return false; }
+    if (options->size < sizeof(o)) {
+        if (options->size != first_revision) { h->err = std::string(fn) + ": options->size is smaller than " + type; return false; }
+        memcpy(&o, options, first_revision);
+        o.size = sizeof(o);
+        return true;
+    }
     const unsigned char *tail = reinterpret_cast<const unsigned char *>(options);
     for (uint32_t i = sizeof(o); i < options->size; i++)
         if (tail[i]) { h->err = std::string(fn) + ": options holds a non-zero field this library does not know"; return false; }
@@ -1342,21 +1349,28 @@ int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const v
                     const void *d_bounds, const void *d_pos, int32_t pos_stride, const tmpc_path_options *options, void *d_segment,
                     void *d_closest_s, void *d_window, void *d_bound_window, void *d_reached)
 {
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_track_path");
     if (!h) return TMPC_ERR_INVALID;
-    tmpc_path_options o{};                                            // NULL: the defaults (search_range 2)
+    tmpc_path_options o{};                                            // NULL: the defaults (search_range 2, the handle's S)
     o.size = sizeof(o); o.search_range = 2;
-    if (!read_options(h, "tmpc_track_path", "tmpc_path_options", options, o)) return TMPC_ERR_INVALID;
+    if (!read_options(h, "tmpc_track_path", "tmpc_path_options", options, o, (uint32_t)offsetof(tmpc_path_options, window_segments))) return TMPC_ERR_INVALID;
+    if (o.window_segments < 0 || o.window_segments > tmpc::VELOCITY_MAX_WINDOW) { h->err = "tmpc_track_path: 0 <= window_segments <= 64"; return TMPC_ERR_INVALID; }
+#ifdef TMPC_GENERATED_STAGE
+    if (o.window_segments == 0) TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_track_path");     // such a handle has no S: the caller has to supply it
+    const int S = o.window_segments;
+#else
+    if (o.window_segments != 0 && o.window_segments != h->d.S) { h->err = "tmpc_track_path: window_segments must be 0 or the handle's S"; return TMPC_ERR_INVALID; }
+    const int S = h->d.S;
+#endif
     if (n_scenes <= 0) { h->err = "tmpc_track_path: n_scenes must be positive"; return TMPC_ERR_INVALID; }
     if (n_seg_max < 1 || n_seg_max > tmpc::PATH_MAX_SEGMENTS) { h->err = "tmpc_track_path: 1 <= n_seg_max <= 1024"; return TMPC_ERR_INVALID; }
     if (o.search_range < 0 || o.search_range > 31) { h->err = "tmpc_track_path: 0 <= search_range <= 31"; return TMPC_ERR_INVALID; }
     if (pos_stride < 2) { h->err = "tmpc_track_path: pos_stride >= 2 (x and y first)"; return TMPC_ERR_INVALID; }
-    if (h->d.S <= 0) { h->err = "tmpc_track_path: the problem has no path segments (S = 0)"; return TMPC_ERR_INVALID; }
+    if (S <= 0) { h->err = "tmpc_track_path: the problem has no path segments (S = 0)"; return TMPC_ERR_INVALID; }
     if (!d_path || !d_path_count || !d_path_length || !d_pos) { h->err = "tmpc_track_path: NULL input (d_path, d_path_count, d_path_length, d_pos)"; return TMPC_ERR_INVALID; }
     if (!d_segment || !d_closest_s || !d_window) { h->err = "tmpc_track_path: NULL output (d_segment, d_closest_s, d_window)"; return TMPC_ERR_INVALID; }
     if ((d_bounds == nullptr) != (d_bound_window == nullptr)) { h->err = "tmpc_track_path: d_bounds and d_bound_window go together (both or neither)"; return TMPC_ERR_INVALID; }
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(tmpc::tmpc_track_path_kernel, dim3((unsigned)n_scenes), dim3(64), 0, h->stream, h->d.S, n_seg_max, o.search_range,
+    hipLaunchKernelGGL(tmpc::tmpc_track_path_kernel, dim3((unsigned)n_scenes), dim3(64), 0, h->stream, S, n_seg_max, o.search_range,
                        (const double *)d_path, (const int *)d_path_count, (const double *)d_path_length, (const double *)d_bounds, (const double *)d_pos,
                        pos_stride, (int *)d_segment, (double *)d_closest_s, (double *)d_window, (double *)d_bound_window, (uint8_t *)d_reached);
     TMPC_HIP_CHECK(h, hipGetLastError());
@@ -1377,6 +1391,51 @@ int tmpc_set_path_parameters(tmpc_handle *h, const void *d_window, const void *d
     hipLaunchKernelGGL(tmpc::tmpc_set_path_parameters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B,
                        const_cast<double *>(h->params), (const double *)d_window, (const int *)d_scene_of, n_scenes, (const double *)d_closest_s,
                        (double *)d_state);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
+int tmpc_path_velocity_window(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, int32_t S, const void *d_velocity, const void *d_path,
+                              const void *d_path_count, const void *d_path_length, const void *d_segment, const void *d_closest_s,
+                              const void *d_has_velocity, double reference_velocity, void *d_window, void *d_v_ref)
+{
+    if (!h) return TMPC_ERR_INVALID;
+    if (n_scenes <= 0) { h->err = "tmpc_path_velocity_window: n_scenes must be positive"; return TMPC_ERR_INVALID; }
+    if (n_seg_max < 1 || n_seg_max > tmpc::PATH_MAX_SEGMENTS) { h->err = "tmpc_path_velocity_window: 1 <= n_seg_max <= 1024"; return TMPC_ERR_INVALID; }
+    if (S < 1 || S > tmpc::VELOCITY_MAX_WINDOW) { h->err = "tmpc_path_velocity_window: 1 <= S <= 64"; return TMPC_ERR_INVALID; }
+    if (!d_path || !d_path_count || !d_path_length || !d_segment || !d_closest_s) {
+        h->err = "tmpc_path_velocity_window: NULL input (d_path, d_path_count, d_path_length, d_segment, d_closest_s)"; return TMPC_ERR_INVALID;
+    }
+    if (!d_window) { h->err = "tmpc_path_velocity_window: NULL output (d_window)"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_path_velocity_window_kernel, dim3((unsigned)n_scenes), dim3(64), 0, h->stream, S, n_seg_max, (const double *)d_velocity,
+                       (const double *)d_path, (const int *)d_path_count, (const int *)d_segment, (const double *)d_closest_s,
+                       (const uint8_t *)d_has_velocity, reference_velocity, (double *)d_window, (double *)d_v_ref);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
+int tmpc_scatter_parameters(tmpc_handle *h, const int32_t *cols, int32_t n_cols, const void *d_values, int32_t per_stage, const void *d_scene_of,
+                            int32_t n_scenes)
+{
+    if (!h) return TMPC_ERR_INVALID;
+    if (h->B <= 0 || !h->params) { h->err = "tmpc_scatter_parameters: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
+    if (!cols || !d_values || !d_scene_of || n_scenes <= 0) { h->err = "tmpc_scatter_parameters: bad argument (cols, d_values, d_scene_of, n_scenes > 0)"; return TMPC_ERR_INVALID; }
+    if (n_cols < 1 || n_cols > tmpc::SCATTER_MAX_COLS) { h->err = "tmpc_scatter_parameters: 1 <= n_cols <= 128"; return TMPC_ERR_INVALID; }
+    if (per_stage != 0 && per_stage != 1) { h->err = "tmpc_scatter_parameters: per_stage is 0 or 1"; return TMPC_ERR_INVALID; }
+    tmpc::ScatterCols list{};
+    list.n = n_cols;
+    for (int i = 0; i < n_cols; i++) {
+        if (cols[i] < 0 || cols[i] >= h->d.npar) { h->err = "tmpc_scatter_parameters: a column outside [0, npar)"; return TMPC_ERR_INVALID; }
+        for (int j = 0; j < i; j++)
+            if (cols[j] == cols[i]) { h->err = "tmpc_scatter_parameters: a duplicate column (the value written would depend on thread order)"; return TMPC_ERR_INVALID; }
+        list.col[i] = cols[i];
+    }
+    const int64_t n = (int64_t)h->B * h->d.N * n_cols;
+    if (n > 0x7fffffff) { h->err = "tmpc_scatter_parameters: B x N x n_cols too large"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_scatter_parameters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B,
+                       const_cast<double *>(h->params), list, (const double *)d_values, (const int *)d_scene_of, n_scenes, per_stage);
     TMPC_HIP_CHECK(h, hipGetLastError());
     return TMPC_OK;
 }

@@ -102,7 +102,8 @@ def _write_host_side(out_dir, pm, N, slack, n_sqp, dt, n_lin, M, n_slk, num_segm
                 f"#define SOLVER_NLIN {n_lin}\n#define SOLVER_M {M}\n"
                 f"#define SOLVER_NSLK {n_slk}\n#define SOLVER_SLACK {int(bool(slack))}\n#define SOLVER_MAX_OBSTACLES {max_obstacles}\n"
                 f"#define SOLVER_S {num_segments}\n#define SOLVER_NSQP {n_sqp}\n#define SOLVER_DT {dt}\n#define SOLVER_COST_MODEL {cost_model}\n#define SOLVER_ROW_MODEL {row_model}\n"
-                + (f"#define SOLVER_NDECOMP {n_decomp}\n" if n_decomp else "") + "#endif\n")      # (of SOLVER_NSLK: the decomp rows, which follow the scenario rows; DecompConstraints is compiled with them)
+                + (f"#define SOLVER_NDECOMP {n_decomp}\n" if n_decomp else "")
+                + ("#define SOLVER_PATH_VELOCITY 1\n" if "spline_v_a" in pm.parameter_bundles else "") + "#endif\n")      # (of SOLVER_NSLK: the decomp rows, which follow the scenario rows; DecompConstraints is compiled with them)
     with open(os.path.join(inc, "mpc_planner_parameters.h"), "w") as h, \
             open(os.path.join(src, "mpc_planner_parameters.cpp"), "w") as c:
         h.write("/** autogenerated by mpc_planner_amd.generate_solver */\n#ifndef __MPC_PLANNER_PARAMETERS_H__\n"

@@ -969,7 +969,8 @@ def path_velocity_window(velocity, count, segment, S, reference_velocity):
     """PathReferenceVelocity::setParameters (path_reference_velocity.cpp:59-95) for stacks that carry the spline_v{i}_{a..d} columns
     (codegen.stacks.contouring_path_velocity_ellipsoids): [S][4], slot w = velocity segment `segment + w` (velocity [count][4] as
     fit_path returns it); a slot beyond the last segment is (0, 0, 0, 0) -- "brake at the end"; without a profile (velocity None) every
-    slot is (0, 0, 0, reference_velocity).  Host only: no hand-written kernel shape has these columns."""
+    slot is (0, 0, 0, reference_velocity).  Host mirror of tmpc_path_velocity_window, which clamps the segment into [0, count - 1] first
+    and also takes count <= 0 or a cleared flag for "no profile": pass a segment inside the path, and None for such a scene."""
     out = np.zeros((S, 4))
     if velocity is None:
         out[:, 3] = float(reference_velocity)
@@ -980,6 +981,48 @@ def path_velocity_window(velocity, count, segment, S, reference_velocity):
         if 0 <= i < int(count):
             out[w] = velocity[i]
     return out
+
+
+def path_velocity_at(velocity, path, count, length, s, reference_velocity):
+    """The velocity reference at path parameter s: what GuidanceConstraints::update hands to the guidance planner,
+    path_velocity(state.spline) (guidance_constraints.cpp:91-94), else CONFIG reference_velocity.  tk::spline::operator() is not in the
+    reference tree: restated as DESIGN.md U17.  velocity [count][4] and path [count][9] as fit_path returns them.  Segment
+    i = max{j <= count - 1 : start_j <= s}, 0 if there is none (the lookup of U12); t = s - start_i; ((a t + b) t + c) t + d, no fused
+    multiply-add.  At s >= length the last cubic continues (`length` is not read: tk::spline extrapolates there, and closest_s never
+    exceeds it).  Without a profile (velocity None or count <= 0): reference_velocity.  Host mirror of tmpc_path_velocity_window's d_v_ref."""
+    if velocity is None or int(count) <= 0:
+        return float(reference_velocity)
+    velocity = np.asarray(velocity, float).reshape(-1, 4)
+    path = np.asarray(path, float).reshape(-1, 9)
+    s = float(s)
+    i = 0
+    for j in range(int(count)):
+        if path[j, 8] <= s:
+            i = j
+    a, b, c, d = (float(x) for x in velocity[i])
+    with np.errstate(all="ignore"):
+        t = s - float(path[i, 8])
+        return ((a * t + b) * t + c) * t + d
+
+
+def scatter_parameters(params, cols, values, scene_of, per_stage=False):
+    """Caller-chosen columns of parameter rows, in place (host mirror of tmpc_scatter_parameters): params [B][N][npar]; cols distinct column
+    numbers in [0, npar); values [n_scenes][n_cols] into every stage of every entry b with scene_of[b] inside [0, n_scenes), or with
+    per_stage values [n_scenes][N][n_cols], stage k from row k.  Other entries and other columns are left alone."""
+    cols = [int(c) for c in cols]
+    B, N, npar = params.shape
+    if not 1 <= len(cols) <= 128 or len(set(cols)) != len(cols) or min(cols) < 0 or max(cols) >= npar:
+        raise ValueError("scatter_parameters: 1 .. 128 distinct columns inside [0, npar)")
+    values = np.asarray(values, float)
+    n_scenes = values.shape[0]
+    values = values.reshape(n_scenes, N, len(cols)) if per_stage else values.reshape(n_scenes, 1, len(cols))
+    for b in range(B):
+        q = int(scene_of[b])
+        if 0 <= q < n_scenes:
+            for k in range(N):
+                row = values[q, k if per_stage else 0]
+                for c, col in enumerate(cols):
+                    params[b, k, col] = row[c]
 
 
 def path_velocity_set_parameters(pm, params, window):

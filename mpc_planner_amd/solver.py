@@ -49,7 +49,7 @@ EXPORTS = ["tmpc_default_dims", "tmpc_default_dims_ex", "tmpc_create", "tmpc_des
            "tmpc_scenario_discard", "tmpc_scenario_discarded", "tmpc_linearize_topology_ex", "tmpc_clear_slot", "tmpc_gather_best",
            "tmpc_create_v2", "tmpc_set_param_sharing_ex", "tmpc_latency_mode_capacity", "tmpc_has_lane_kernels", "tmpc_debug_lds_passes", "tmpc_debug_poison_lds", "tmpc_has_lab_switches",
            "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters", "tmpc_track_path", "tmpc_set_path_parameters", "tmpc_fit_path",
-           "tmpc_costmap_points", "tmpc_decomp_halfspaces", "tmpc_set_halfspace_rows"]
+           "tmpc_costmap_points", "tmpc_decomp_halfspaces", "tmpc_set_halfspace_rows", "tmpc_path_velocity_window", "tmpc_scatter_parameters"]
 
 
 class TmpcObstacleOptions(C.Structure):
@@ -60,7 +60,7 @@ class TmpcObstacleOptions(C.Structure):
 
 class TmpcPathOptions(C.Structure):
     """tmpc_path_options (include/tmpc_hip.h)."""
-    _fields_ = [("size", C.c_uint32), ("search_range", C.c_int32)]
+    _fields_ = [("size", C.c_uint32), ("search_range", C.c_int32), ("window_segments", C.c_int32)]
 
 
 class TmpcError(RuntimeError):
@@ -136,6 +136,9 @@ def load_library(path=None):
         lib.tmpc_set_path_parameters.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
     if hasattr(lib, "tmpc_fit_path"):
         lib.tmpc_fit_path.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 13
+    if hasattr(lib, "tmpc_path_velocity_window"):
+        lib.tmpc_path_velocity_window.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 7 + [C.c_double, vp, vp]
+        lib.tmpc_scatter_parameters.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32, vp, C.c_int32]
     if hasattr(lib, "tmpc_decomp_halfspaces"):
         lib.tmpc_costmap_points.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, vp, vp, vp]
         lib.tmpc_decomp_halfspaces.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 7 + [C.c_int32, C.c_double, C.c_int32, vp, vp, vp]
@@ -457,17 +460,18 @@ class BatchedSolver:
                     "tmpc_set_obstacle_parameters")
 
     def track_path(self, n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_pos, pos_stride, d_segment, d_closest_s, d_window,
-                   d_bounds=None, d_bound_window=None, d_reached=None, search_range=2):
+                   d_bounds=None, d_bound_window=None, d_reached=None, search_range=2, window_segments=0):
         """Contouring::update on whole reference paths (tmpc_track_path; raw device pointers): per scene the closest point of d_path
         [n_scenes][n_seg_max][9] (d_path_count segments, parameter length d_path_length) to d_pos [n_scenes][pos_stride] -- searched over
         every segment where d_segment is negative, else search_range segments either side of it -- into d_segment (in / out) and d_closest_s,
         the window of S segments from there into d_window [n_scenes][S][9] (padded straight along the end tangent), with d_bounds
         [n_scenes][2][n_seg_max][8] the bound cubics of the window into d_bound_window [n_scenes][2][S][8] (what road_halfspaces takes), and
-        the objective-reached flag into d_reached (u8).  Equal bit for bit to modules.track_path.  Needs no batch.  Stream-ordered."""
+        the objective-reached flag into d_reached (u8).  Equal bit for bit to modules.track_path.  Needs no batch.  Stream-ordered.
+        window_segments: 0 = the handle's S; a generated solver has none and needs the stack's contouring/num_segments here (1 .. 64)."""
         if not hasattr(self.lib, "tmpc_track_path"):
             raise TmpcError("this library has no tmpc_track_path (a missing kernel is an error, there is no host fallback)")
         vp = lambda p_: C.c_void_p(p_) if p_ else None
-        opt = TmpcPathOptions(C.sizeof(TmpcPathOptions), int(search_range))
+        opt = TmpcPathOptions(C.sizeof(TmpcPathOptions), int(search_range), int(window_segments))
         self._check(self.lib.tmpc_track_path(self._h, int(n_scenes), int(n_seg_max), vp(d_path), vp(d_path_count), vp(d_path_length), vp(d_bounds),
                                              vp(d_pos), int(pos_stride), C.byref(opt), vp(d_segment), vp(d_closest_s), vp(d_window),
                                              vp(d_bound_window), vp(d_reached)), "tmpc_track_path")
@@ -482,6 +486,34 @@ class BatchedSolver:
         vp = lambda p_: C.c_void_p(p_) if p_ else None
         self._check(self.lib.tmpc_set_path_parameters(self._h, vp(d_window), vp(d_scene_of), int(n_scenes), vp(d_closest_s), vp(d_state)),
                     "tmpc_set_path_parameters")
+
+    def path_velocity_window(self, n_scenes, n_seg_max, S, d_path, d_path_count, d_path_length, d_segment, d_closest_s, d_window, d_velocity=None,
+                             d_has_velocity=None, reference_velocity=0.0, d_v_ref=None):
+        """PathReferenceVelocity::setParameters on device (tmpc_path_velocity_window; raw device pointers; DESIGN.md U17): per scene the S
+        velocity cubics from d_segment on -- d_velocity [n_scenes][n_seg_max][4] as fit_path wrote it, d_segment / d_closest_s as track_path
+        wrote them -- into d_window [n_scenes][S][4], (0, 0, 0, 0) at or beyond the path's end, (0, 0, 0, reference_velocity) for a scene
+        without a profile (d_velocity None, d_has_velocity[scene] == 0 or count <= 0); with d_v_ref the profile's value at closest_s (or
+        reference_velocity) into d_v_ref [n_scenes], what the guidance planner is given.  Equal bit for bit to modules.path_velocity_window
+        and modules.path_velocity_at.  Needs no batch; also in a generated solver.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_path_velocity_window"):
+            raise TmpcError("this library has no tmpc_path_velocity_window (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        self._check(self.lib.tmpc_path_velocity_window(self._h, int(n_scenes), int(n_seg_max), int(S), vp(d_velocity), vp(d_path), vp(d_path_count),
+                                                       vp(d_path_length), vp(d_segment), vp(d_closest_s), vp(d_has_velocity),
+                                                       float(reference_velocity), vp(d_window), vp(d_v_ref)), "tmpc_path_velocity_window")
+
+    def scatter_parameters(self, cols, d_values, d_scene_of, n_scenes, per_stage=False):
+        """Caller-chosen columns of the current batch's parameter rows, in place (tmpc_scatter_parameters; cols a host sequence of at most 128
+        distinct column numbers, e.g. from a generated stack's meta["parameter_map"]; raw device pointers otherwise): d_values
+        [n_scenes][len(cols)] into every stage of every entry whose d_scene_of is inside [0, n_scenes), or with per_stage d_values
+        [n_scenes][N][len(cols)], stage k from row k; nothing else.  The parameter writer of generated solvers.  Equal bit for bit to
+        modules.scatter_parameters.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_scatter_parameters"):
+            raise TmpcError("this library has no tmpc_scatter_parameters (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        arr = None if cols is None else (C.c_int32 * max(len(cols), 1))(*[int(c) for c in cols])
+        self._check(self.lib.tmpc_scatter_parameters(self._h, arr, 0 if cols is None else len(cols), vp(d_values), 1 if per_stage else 0,
+                                                     vp(d_scene_of), int(n_scenes)), "tmpc_scatter_parameters")
 
     def fit_path(self, n_scenes, n_pts_max, n_seg_max, d_xy, d_count, d_path, d_path_count, d_path_length, d_s=None, d_left_xy=None,
                  d_right_xy=None, d_v=None, d_bounds=None, d_velocity=None, d_road_width=None, d_status=None):

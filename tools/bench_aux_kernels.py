@@ -12,7 +12,11 @@ previous segment is put back to -1 before every launch, a 512-int copy that the 
 profile -- seven curves per scene --, chord knots; needs no batch.  One JSON line: the mean of 50 launches between two HIP events.
 `--decomp [--cells n]`: the free-space kernels alone (tmpc_costmap_points, tmpc_decomp_halfspaces, tmpc_set_halfspace_rows) at cfg 3's shape (N = 30,
 slack model, 12 decomp rows): 512 scenes x 64 trajectories, n x n maps (default 100) from scenes.with_costmap, 16 generated ones repeated, the
-polyline along each scene's own warm start.  One JSON line per kernel with the event time, the points per scene and the rows per stage."""
+polyline along each scene's own warm start.  One JSON line per kernel with the event time, the points per scene and the rows per stage.
+`--velocity [--segments n]`: the velocity-profile kernel and the column scatter alone (tmpc_path_velocity_window, tmpc_scatter_parameters) at
+512 scenes x 64 trajectories, S = 5, N = 20: 512 paths of n segments (default 64) fitted on device with a velocity at every waypoint, closest_s
+anywhere on the path, v_ref requested; the scatter writes the window's S x 4 = 20 values into 20 columns of every stage of every entry.  One
+JSON line per kernel: the mean of 50 launches between two HIP events."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -176,6 +180,56 @@ def decomp_kernels(cells, n_scenes=512, traj=64, N=30, S=5, n_rows=12, n_pts_max
     so.close()
 
 
+def velocity_kernels(n_seg, n_scenes=512, traj=64, N=20, S=5):
+    rng = np.random.default_rng(13)
+    B = n_scenes * traj
+    so = solver.BatchedSolver(solver.default_dims(), B_max=B)
+    f64 = dict(dtype=torch.float64, device=dev)
+    xinit = torch.zeros((B, 5), **f64); x0 = torch.zeros((B, N + 1, 7), **f64); params = torch.zeros((B, N, so.dims.npar), **f64)
+    so.set_batch_device(B, xinit.data_ptr(), x0.data_ptr(), params.data_ptr())
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    n_pts = n_seg + 1
+    heading = np.cumsum(rng.normal(size=(n_scenes, n_pts)) * 0.15, 1); step = rng.uniform(0.5, 3.0, (n_scenes, n_pts))
+    t_xy = up(np.cumsum(np.stack([np.cos(heading) * step, np.sin(heading) * step], 2), 1)); t_v = up(rng.uniform(0.5, 3.0, (n_scenes, n_pts)))
+    t_cnt = up(np.full(n_scenes, n_pts, np.int32))
+    path = torch.zeros((n_scenes, n_seg, 9), **f64); pc = torch.zeros(n_scenes, dtype=torch.int32, device=dev); length = torch.zeros(n_scenes, **f64)
+    vel = torch.zeros((n_scenes, n_seg, 4), **f64)
+    so.fit_path(n_scenes, n_pts, n_seg, t_xy.data_ptr(), t_cnt.data_ptr(), path.data_ptr(), pc.data_ptr(), length.data_ptr(), d_v=t_v.data_ptr(),
+                d_velocity=vel.data_ptr())
+    so.synchronize()
+    assert int(pc.min().item()) == n_seg
+    seg_np = rng.integers(0, n_seg, n_scenes)
+    seg = up(seg_np.astype(np.int32))
+    starts = path[:, :, 8].cpu().numpy()
+    cs = up(starts[np.arange(n_scenes), seg_np] + 0.1)
+    win = torch.zeros((n_scenes, S, 4), **f64); v_ref = torch.zeros(n_scenes, **f64)
+    scene_of = up(np.repeat(np.arange(n_scenes, dtype=np.int32), traj))
+    cols = list(range(8, 8 + 4 * S))
+    window = lambda: so.path_velocity_window(n_scenes, n_seg, S, path.data_ptr(), pc.data_ptr(), length.data_ptr(), seg.data_ptr(), cs.data_ptr(), win.data_ptr(),
+                                             d_velocity=vel.data_ptr(), reference_velocity=2.0, d_v_ref=v_ref.data_ptr())
+    scatter = lambda: so.scatter_parameters(cols, win.data_ptr(), scene_of.data_ptr(), n_scenes)
+    hs = torch.cuda.ExternalStream(so.stream_ptr(), device=dev)
+    for name, call in (("tmpc_path_velocity_window_kernel", window), ("tmpc_scatter_parameters_kernel", scatter)):
+        for _ in range(10):
+            call()
+        so.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(hs):
+            e0.record()
+        for _ in range(50):
+            call()
+        with torch.cuda.stream(hs):
+            e1.record()
+        so.synchronize()
+        print(json.dumps(dict(kernel=name, n_scenes=n_scenes, trajectories=B, segments=n_seg, S=S, N=N, columns=len(cols),
+                              us_per_launch_events=e0.elapsed_time(e1) * 1e3 / 50)), flush=True)
+    so.close()
+
+
+if "--velocity" in sys.argv:
+    velocity_kernels(int(sys.argv[sys.argv.index("--segments") + 1]) if "--segments" in sys.argv else 64)
+    print("done")
+    sys.exit(0)
 if "--decomp" in sys.argv:
     decomp_kernels(int(sys.argv[sys.argv.index("--cells") + 1]) if "--cells" in sys.argv else 100)
     print("done")
