@@ -38,6 +38,7 @@
 #include <mpc_planner_types/data_types.h>
 #include <mpc_planner_types/module_data.h>
 #include <mpc_planner_modules/free_space.h>
+#include <mpc_planner_modules/guidance_handoff.h>
 #include <mpc_planner_modules/reference_path.h>
 #include <mpc_planner_types/realtime_data.h>
 
@@ -561,6 +562,27 @@ namespace MPCPlanner
         }
         /* stands in for global_guidance_->Update() + GetGuidanceTrajectory(i): the trajectories found for this tick */
         void setGuidanceTrajectories(const std::vector<GuidanceTrajectory> &t) { _guidance = t; mapGuidanceTrajectoriesToPlanners(); }   /* :106-108 */
+        /* The same from the search's raw output: every trajectory's positions / velocities are sampled from the time spline through its
+         * nodes at t = k dt, k = 0 .. N (GuidanceSpline; bit for bit what tmpc_sample_guidance writes).  A trajectory whose
+         * node list is invalid (fewer than two nodes, more than 64, a knot spacing that is not positive and finite) gets zeros.  Returns
+         * the number of invalid trajectories. */
+        int setGuidanceNodes(std::vector<GuidanceTrajectory> t)
+        {
+            int invalid = 0;
+            for (GuidanceTrajectory &g : t) {
+                GuidanceSpline spline;
+                spline.fit(g.nodes);
+                std::vector<double> pos, vel;
+                invalid += spline.sample(_solver->N, _solver->dt, pos, vel);
+                g.positions.clear(); g.velocities.clear();
+                for (int k = 0; k <= _solver->N; k++) {
+                    g.positions.emplace_back(pos[(size_t)k * 2], pos[(size_t)k * 2 + 1]);
+                    g.velocities.emplace_back(vel[(size_t)k * 2], vel[(size_t)k * 2 + 1]);
+                }
+            }
+            setGuidanceTrajectories(t);
+            return invalid;
+        }
         /* guidance_constraints.cpp:192-250 -- which planner continues which homotopy class.  Pass 1: a trajectory whose class equals
          * the guidance_ID of a planner's last result reserves that planner (existing_guidance: its previous MPC solution is a valid
          * warm start, consumed at :310).  Pass 2: the trajectories left over go to the planners left over -- with the reference's

@@ -80,10 +80,12 @@ namespace MPCPlanner
      * mpc_planner_modules/reference_path.h) */
 
     /* What GuidanceConstraints reads from the (external) guidance_planner per trajectory (guidance_constraints.cpp:340-360,
-     * 390-414): position / velocity of its spline at t = k dt, k = 0..N, the topology class and the selection flag. */
+     * 390-414): position / velocity of its spline at t = k dt, k = 0..N, the topology class and the selection flag.  `nodes`: the
+     * space-time nodes of the search, from which GuidanceConstraints::setGuidanceNodes fills positions / velocities. */
     struct GuidanceTrajectory
     {
         std::vector<Vector2d> positions, velocities;
+        std::vector<GuidanceNode> nodes;
         int topology_class{0};
         bool previously_selected{false};
         int color{0};

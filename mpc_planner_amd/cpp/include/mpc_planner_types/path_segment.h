@@ -25,5 +25,9 @@ namespace MPCPlanner
         bool hasDistance() const { return !s.empty(); }
     };
     typedef ReferencePath Boundary;
+
+    /* One space-time node of a guidance trajectory as the guidance search delivers it: the time spline through the nodes is
+     * mpc_planner_modules/guidance_handoff.h's GuidanceSpline. */
+    struct GuidanceNode { double t, x, y; };
 }
 #endif

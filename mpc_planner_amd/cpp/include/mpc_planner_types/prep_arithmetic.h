@@ -1,6 +1,6 @@
 /* mpc_planner_types/prep_arithmetic.h -- the double-precision arithmetic of data preparation (road rows, obstacle preparation, path tracking,
- * path fitting, free-space decomposition), written ONCE for the device kernels (csrc/tmpc_aux_kernels.hpp) and the Solver-free C++ headers
- * (reference_path.h, free_space.h, data_preparation.h, Contouring in modules_hip.h): both compile these functions, so they cannot drift apart.  The independent statement the
+ * path fitting, free-space decomposition, the guidance hand-off), written ONCE for the device kernels (csrc/tmpc_aux_kernels.hpp) and the Solver-free C++ headers
+ * (reference_path.h, free_space.h, guidance_handoff.h, data_preparation.h, Contouring in modules_hip.h): both compile these functions, so they cannot drift apart.  The independent statement the
  * tests compare both against is the numpy mirror, mpc_planner_amd/modules.py; every function keeps the mirror's operation order, and nothing is
  * fused into multiply-adds (the pragma under clang; build host code with -ffp-contract=off).  Plain functions on doubles: no containers, no
  * planner types.  A cubic is its eight coefficients c = (ax bx cx dx ay by cy dy): x(t) = ((ax t + bx) t + cx) t + dx, the same for y. */
@@ -258,5 +258,108 @@ namespace tmpc_arith
     }
     /* does row (a1, a2, .) end the copy (:98)? */
     TMPC_ARITH_FN bool decomp_terminator(double a1, double a2) { TMPC_ARITH_NO_FMA return sqrt(a1 * a1 + a2 * a2) < DECOMP_TERMINATOR || a1 != a1; }
+
+    /* ---- guidance hand-off: the time spline through a guidance trajectory's nodes, and GuidanceConstraints' bookkeeping around
+     * the solve (guidance_constraints.cpp:192-250, :283-387, :416-434).  + - x / and comparisons only ---- */
+    /* the sample time of node k, and the velocity of a scalar cubic c = (a b c d) at tau (its position is cubic_value) */
+    TMPC_ARITH_FN double sample_time(int k, double dt) { TMPC_ARITH_NO_FMA return (double)k * dt; }
+    TMPC_ARITH_FN double cubic_slope(const double c[4], double tau) { TMPC_ARITH_NO_FMA return (3.0 * c[0] * tau + 2.0 * c[1]) * tau + c[2]; }
+    /* the braking command's velocity, std::max(v - deceleration dt, 0.) (ros1_jackalsimulator.cpp:191-199) */
+    TMPC_ARITH_FN double braking_velocity(double v, double deceleration, double dt)
+    {
+        TMPC_ARITH_NO_FMA
+        const double w = v - deceleration * dt;
+        return w < 0.0 ? 0.0 : w;
+    }
+
+    /* mapGuidanceTrajectoriesToPlanners (:192-250) over P <= 64 planners with last tick's IDs and n_traj <= 63 trajectories' classes, literally,
+     * the second loop without its `break` included: bit p of the result is planners_[p].existing_guidance.  The sets are 64-bit masks. */
+    TMPC_ARITH_FN unsigned long long guidance_existing(const int *ids, int P, const int *cls, int n_traj)
+    {
+        unsigned long long taken = 0, existing = 0, remaining = 0;
+        for (int i = 0; i < n_traj; i++) {
+            bool found = false;
+            for (int p = 0; p < P; p++)
+                if (ids[p] == cls[i] && !((taken >> p) & 1ull)) {
+                    taken |= 1ull << p; existing |= 1ull << p; found = true;
+                    break;
+                }
+            if (!found) remaining |= 1ull << i;
+        }
+        for (int i = 0; i < n_traj; i++) {
+            if (!((remaining >> i) & 1ull)) continue;
+            for (int p = 0; p < P; p++)
+                if (!((taken >> p) & 1ull)) { taken |= 1ull << p; existing &= ~(1ull << p); }
+        }
+        return existing;
+    }
+
+    /* One scene of tmpc_guidance_plan; `first` = q P is the scene's first batch entry and every output points at that entry.  cls / prev
+     * [n_paths] (prev may be null), ids [P] and sel [3] the cross-tick state (read only).  Steps 1-7 of the header's description. */
+    TMPC_ARITH_FN void guidance_plan_scene(int first, int n_paths, int use_tmpcpp, int warmstart_with_mpc_solution, int shift, double weight_consistency,
+                                           int traj_count, const int *cls, const unsigned char *prev, const int *ids, const int *sel, int *mode,
+                                           int *src, unsigned char *init_enabled, unsigned char *rows_dummy, unsigned char *disabled, int *guidance_id,
+                                           double *weight)
+    {
+        const int P = n_paths + (use_tmpcpp ? 1 : 0);
+        const int n_traj = traj_count < 0 ? 0 : (traj_count > n_paths ? n_paths : traj_count);
+        const unsigned long long existing = guidance_existing(ids, P, cls, n_traj);
+        const int warm_mode = shift ? 1 : 2;
+        const bool was_feasible = sel[2] >= 0;
+        for (int p = 0; p < P; p++) {
+            const bool original = use_tmpcpp && p == P - 1;
+            const bool off = p >= n_traj && !original;
+            const bool guided = !original && !off;
+            int m = was_feasible ? warm_mode : 3, s = was_feasible ? first + sel[2] : first + p;
+            unsigned char init = 0;
+            if (guided) {
+                if (warmstart_with_mpc_solution && ((existing >> p) & 1ull)) { m = warm_mode; s = first + p; }
+                else init = 1;
+            }
+            bool selected = false;
+            if (guided) selected = prev ? prev[p] != 0 : (sel[0] >= 0 && sel[1] == 0 && cls[p] == sel[0]);
+            mode[p] = m; src[p] = s; init_enabled[p] = init;
+            rows_dummy[p] = (original || off) ? 1 : 0;
+            disabled[p] = off ? 1 : 0;
+            guidance_id[p] = original ? 2 * n_paths : (off ? -1 : cls[p]);
+            weight[p] = selected ? weight_consistency : 1.0;
+        }
+    }
+
+    /* FindBestPlanner (:416-434) over one scene's P planners: index of the winner or -1 */
+    TMPC_ARITH_FN int guidance_best(int P, const double *pobj, const int *exit_code, const unsigned char *disabled, const double *weight)
+    {
+        TMPC_ARITH_NO_FMA
+        double best_solution = 1e10;
+        int best = -1;
+        for (int p = 0; p < P; p++) {
+            if (disabled[p]) continue;
+            const double objective = pobj[p] * weight[p];
+            if (exit_code[p] == 1 && objective < best_solution) { best_solution = objective; best = p; }
+        }
+        return best;
+    }
+
+    /* One scene of tmpc_guidance_decide: every pointer at the scene's first entry (xtraj / utraj: its first trajectory, x_entry / u_entry doubles
+     * per trajectory, nx doubles per node, nu per input node; v is state 3, w input 1).  Steps 1-5 of the header's description. */
+    TMPC_ARITH_FN void guidance_decide_scene(int P, int use_tmpcpp, const double *pobj, const int *exit_code, const unsigned char *disabled,
+                                             const int *guidance_id, const double *weight, const double *xtraj, int x_entry, int nx, const double *utraj,
+                                             int u_entry, double v_state, double deceleration, double control_dt, int enable_output, int *best_out,
+                                             int *exit_out, double *cmd, int *ids, int *sel)
+    {
+        const int best = guidance_best(P, pobj, exit_code, disabled, weight);
+        *best_out = best;
+        *exit_out = best >= 0 ? exit_code[best] : (disabled[0] ? -1 : exit_code[0]);
+        if (best >= 0 && enable_output) {
+            cmd[0] = xtraj[(long long)best * x_entry + nx + 3];
+            cmd[1] = utraj[(long long)best * u_entry + 1];
+        } else {
+            cmd[0] = braking_velocity(v_state, deceleration, control_dt);
+            cmd[1] = 0.0;
+        }
+        for (int p = 0; p < P; p++) ids[p] = guidance_id[p];
+        if (best >= 0) { sel[0] = guidance_id[best]; sel[1] = (use_tmpcpp && best == P - 1) ? 1 : 0; }
+        sel[2] = best;
+    }
 }
 #endif

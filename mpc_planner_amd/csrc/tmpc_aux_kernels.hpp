@@ -634,6 +634,116 @@ __global__ void tmpc_scatter_parameters_kernel(Dims d, int B, double *params, Sc
     params[((size_t)b * N + k) * d.npar + cols.col[c]] = src[c];
 }
 
+// ---- the guidance hand-off: what GuidanceConstraints does with the output of the guidance search either side of the solve.
+// The arithmetic and the bookkeeping are tmpc_arith's, shared with mpc_planner_modules/guidance_handoff.h; bit-equal to the independent
+// modules.py::sample_guidance / guidance_plan / guidance_decide.
+constexpr int GUIDANCE_MAX_NODES = 64;
+constexpr int GUIDANCE_MAX_PATHS = 63;                                     // P = n_paths + 1 <= 64: the planner sets are 64-bit masks
+
+// One wave per guidance trajectory j: nodes [n_traj][n_nodes_max][3] = (t, x, y), count[j] of them (n_nodes_max <= 64: one lane per node).
+// (1) knots into LDS, h_i by the lanes; INVALID if the count is outside [2, n_nodes_max] or any h_i fails spacing_valid: status 1, both
+// rows zeros.  (2) the right-hand sides of x and y by the lanes, (3) lanes 0 / 1 carry x / y through the Thomas recurrence of U15 (both
+// compute the same cp, lane 0 keeps it), (4) the lanes write the rows (a b c d) into LDS, (5) one lane per sample k <= N (strided): the
+// segment i = max{j <= count - 2 : t_j <= k dt}, 0 if none, tau = k dt - t_i, position and velocity in Horner form.  LDS 5.5 KB.
+__global__ __launch_bounds__(64) void tmpc_sample_guidance_kernel(int N, double dt, int n_nodes_max, const double *nodes, const int *count,
+                                                                  double *gpos, double *gvel, int *status)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_t[GUIDANCE_MAX_NODES], s_h[GUIDANCE_MAX_NODES], s_cp[GUIDANCE_MAX_NODES], s_c[2][GUIDANCE_MAX_NODES][4];
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const int n = count[j];
+    const double *nq = nodes + (size_t)j * n_nodes_max * 3;
+    double *pos = gpos + (size_t)j * (N + 1) * 2, *vel = gvel + (size_t)j * (N + 1) * 2;
+    bool invalid = n < 2 || n > n_nodes_max;                               // (uniform over the block)
+    if (!invalid) {
+        if (lane < n) s_t[lane] = nq[lane * 3];
+        __syncthreads();
+        bool bad = false;
+        if (lane < n - 1) {
+            const double h = s_t[lane + 1] - s_t[lane];
+            bad = !tmpc_arith::spacing_valid(h);
+            s_h[lane] = h;
+        }
+        invalid = __syncthreads_or(bad ? 1 : 0) != 0;
+    }
+    if (invalid) {
+        for (int e = lane; e < (N + 1) * 2; e += 64) { pos[e] = 0.0; vel[e] = 0.0; }
+        if (lane == 0) status[j] = 1;
+        return;
+    }
+    if (lane >= 1 && lane <= n - 2)
+        for (int c = 0; c < 2; c++)
+            s_c[c][lane][1] = tmpc_arith::spline_rhs(nq[(lane - 1) * 3 + 1 + c], nq[lane * 3 + 1 + c], nq[(lane + 1) * 3 + 1 + c], s_h[lane - 1], s_h[lane]);
+    __syncthreads();
+    if (lane < 2) {
+        double g = 0.0, cp = 0.0;
+        for (int i = 1; i <= n - 2; i++) {
+            tmpc_arith::thomas_forward(tmpc_arith::spline_off(s_h[i - 1]), tmpc_arith::spline_diag(s_h[i - 1], s_h[i]), tmpc_arith::spline_off(s_h[i]),
+                                       s_c[lane][i][1], cp, g);
+            s_c[lane][i][1] = g;
+            if (lane == 0) s_cp[i] = cp;
+        }
+    }
+    __syncthreads();
+    if (lane < 2) {
+        double m = 0.0;                                                    // m_{n-1}
+        for (int i = n - 2; i >= 1; i--) { m = tmpc_arith::thomas_backward(s_c[lane][i][1], s_cp[i], m); s_c[lane][i][1] = m; }
+        s_c[lane][0][1] = 0.0;                                             // m_0
+    }
+    __syncthreads();
+    if (lane < n - 1)
+        for (int c = 0; c < 2; c++) {
+            const double m0 = s_c[c][lane][1], m1 = lane + 1 < n - 1 ? s_c[c][lane + 1][1] : 0.0;
+            tmpc_arith::spline_row(m0, m1, s_h[lane], nq[lane * 3 + 1 + c], nq[(lane + 1) * 3 + 1 + c], s_c[c][lane][0], s_c[c][lane][2], s_c[c][lane][3]);
+        }
+    __syncthreads();
+    for (int k = lane; k <= N; k += 64) {
+        const double t = tmpc_arith::sample_time(k, dt);
+        int i = 0;
+        for (int jj = 0; jj <= n - 2; jj++) if (s_t[jj] <= t) i = jj;
+        const double tau = t - s_t[i];
+        for (int c = 0; c < 2; c++) {
+            pos[k * 2 + c] = tmpc_arith::cubic_value(s_c[c][i], tau);
+            vel[k * 2 + c] = tmpc_arith::cubic_slope(s_c[c][i], tau);
+        }
+    }
+    if (lane == 0) status[j] = 0;
+}
+
+// the options of tmpc_guidance_plan / tmpc_guidance_decide, by value
+struct GuidanceOptions { int n_paths, use_tmpcpp, warmstart_with_mpc_solution, shift; double weight_consistency; };
+
+// One thread per scene q (the mapping is a sequential scan over the scene's planners: nothing to share between lanes); entry b = q P + p.
+__global__ void tmpc_guidance_plan_kernel(int n_scenes, GuidanceOptions o, const int *traj_count, const int *topology_class,
+                                          const uint8_t *previously_selected, const int *planner_ids, const int *selection, int *mode, int *src,
+                                          uint8_t *init_enabled, uint8_t *rows_dummy, uint8_t *disabled, int *guidance_id, double *weight)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_scenes) return;
+    const int P = o.n_paths + (o.use_tmpcpp ? 1 : 0);
+    const size_t f = (size_t)q * P;
+    tmpc_arith::guidance_plan_scene((int)f, o.n_paths, o.use_tmpcpp, o.warmstart_with_mpc_solution, o.shift, o.weight_consistency, traj_count[q],
+                                    topology_class + (size_t)q * o.n_paths, previously_selected ? previously_selected + (size_t)q * o.n_paths : nullptr,
+                                    planner_ids + f, selection + (size_t)q * 3, mode + f, src + f, init_enabled + f, rows_dummy + f, disabled + f,
+                                    guidance_id + f, weight + f);
+}
+
+// One thread per scene q: FindBestPlanner over its P entries, the exit code, the command, the state commit.
+__global__ void tmpc_guidance_decide_kernel(int n_scenes, GuidanceOptions o, int N, int nxe, const double *pobj, const int *exit_code,
+                                            const uint8_t *disabled, const int *guidance_id, const double *weight, const double *state,
+                                            const double *xtraj, const double *utraj, double deceleration, double control_dt, int enable_output,
+                                            int *best, int *exit_out, double *cmd, int *planner_ids, int *selection)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_scenes) return;
+    const int P = o.n_paths + (o.use_tmpcpp ? 1 : 0);
+    const size_t f = (size_t)q * P;
+    const int x_entry = (N + 1) * nxe, u_entry = N * NU;
+    tmpc_arith::guidance_decide_scene(P, o.use_tmpcpp, pobj + f, exit_code + f, disabled + f, guidance_id + f, weight + f, xtraj + f * x_entry, x_entry,
+                                      nxe, utraj + f * u_entry, u_entry, state[(size_t)q * nxe + 3], deceleration, control_dt, enable_output, best + q,
+                                      exit_out + q, cmd + (size_t)q * 2, planner_ids + f, selection + (size_t)q * 3);
+}
+
 
 // ---- f-3: scenario -> polygon on device (SH-MPC, BASELINE config 5) ------------------------------------------------
 // The reference delegates this to the external scenario_module (scenario_constraints.cpp:47,76-79; source absent), so

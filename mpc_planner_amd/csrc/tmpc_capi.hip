@@ -451,6 +451,7 @@ struct tmpc_handle {
     bool share_strict = false;       // tmpc_set_param_sharing_ex(.., TMPC_SHARE_COPIES_NOT_MAINTAINED): a solve that cannot honour the map is an error
     bool st_valid = false;           // lane kernels (state = their workspace, per launch): it holds the result of a previous call ...
     int st_B = 0;                    // ... for slots [0, st_B)
+    int solved_B = 0;                // entries the last solve launch covered; 0 after tmpc_set_batch* (tmpc_guidance_decide reads the solution)
     // SH-MPC bookkeeping: the sample behind each scenario row of the last tmpc_scenario_halfspaces (i32 [B][N][scn_rows])
     unsigned char *scn_discard = nullptr;     // [B_max][scn_discard_S] scenarios discarded for each trajectory (tmpc_scenario_discard); applies to the next tmpc_scenario_halfspaces
     int scn_discard_S = 0, scn_discard_B = 0, scn_discard_n = 0;
@@ -771,6 +772,7 @@ int tmpc_set_batch(tmpc_handle *h, int32_t B, const double *xinit, const double 
     TMPC_HIP_CHECK(h, hipMemcpyAsync(h->o_params, params, (size_t)B * N * h->d.npar * 8, hipMemcpyHostToDevice, h->stream));
     }
     h->xinit = h->o_xinit; h->x0 = h->o_x0; h->params = h->o_params; h->B = B;
+    h->solved_B = 0;
     h->scn_B = 0;                      // new parameter rows: the scenario-row bookkeeping of the previous batch no longer describes them
     h->scn_discard_B = 0;
     h->share_B = 0;                    // ... nor does a parameter-sharing map given for them
@@ -781,6 +783,7 @@ int tmpc_set_batch_device(tmpc_handle *h, int32_t B, const void *d_xinit, const 
 {
     if (!h || B <= 0 || B > h->B_max || !d_xinit || !d_x0 || !d_params) { if (h) h->err = "tmpc_set_batch_device: bad argument"; return TMPC_ERR_INVALID; }
     h->xinit = (const double *)d_xinit; h->x0 = (const double *)d_x0; h->params = (const double *)d_params; h->B = B;
+    h->solved_B = 0;
     h->scn_B = 0; h->scn_discard_B = 0; h->share_B = 0;
     return TMPC_OK;
 }
@@ -837,6 +840,7 @@ static int launch_solve(tmpc_handle *h, int n_iter, int st_flags)
         }
     }
     if (rec) { TMPC_HIP_CHECK(h, hipEventRecord(h->ev[h->ev_used + 1], h->stream)); h->ev_used += 2; }
+    h->solved_B = h->B;
     return TMPC_OK;
 }
 
@@ -1669,6 +1673,80 @@ int tmpc_init_with_guidance(tmpc_handle *h, const void *d_gpos, const void *d_gv
     const int n = h->B * (h->d.N + 1);
     hipLaunchKernelGGL(tmpc::tmpc_init_with_guidance_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d, h->B,
                        (const double *)d_gpos, (const double *)d_gvel, (const uint8_t *)d_enabled, const_cast<double *>(h->x0));
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
+int tmpc_sample_guidance(tmpc_handle *h, int32_t n_traj, int32_t n_nodes_max, const void *d_nodes, const void *d_node_count, void *d_gpos,
+                         void *d_gvel, void *d_status)
+{
+    if (!h) return TMPC_ERR_INVALID;
+    if (n_traj <= 0) { h->err = "tmpc_sample_guidance: n_traj must be positive"; return TMPC_ERR_INVALID; }
+    if (n_nodes_max < 2 || n_nodes_max > tmpc::GUIDANCE_MAX_NODES) { h->err = "tmpc_sample_guidance: 2 <= n_nodes_max <= 64"; return TMPC_ERR_INVALID; }
+    if (!d_nodes || !d_node_count) { h->err = "tmpc_sample_guidance: NULL input (d_nodes, d_node_count)"; return TMPC_ERR_INVALID; }
+    if (!d_gpos || !d_gvel || !d_status) { h->err = "tmpc_sample_guidance: NULL output (d_gpos, d_gvel, d_status)"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_sample_guidance_kernel, dim3((unsigned)n_traj), dim3(64), 0, h->stream, h->d.N, h->d.dt, n_nodes_max,
+                       (const double *)d_nodes, (const int *)d_node_count, (double *)d_gpos, (double *)d_gvel, (int *)d_status);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
+// the checks tmpc_guidance_plan and tmpc_guidance_decide share: the scene count and the options (NULL is refused: n_paths has no default)
+static bool read_guidance_options(tmpc_handle *h, const char *fn, int32_t n_scenes, const tmpc_guidance_options *opt, tmpc::GuidanceOptions &g)
+{
+    if (n_scenes <= 0) { h->err = std::string(fn) + ": n_scenes must be positive"; return false; }
+    if (!opt) { h->err = std::string(fn) + ": NULL options"; return false; }
+    tmpc_guidance_options o{};
+    if (!read_options(h, fn, "tmpc_guidance_options", opt, o)) return false;
+    if (o.n_paths < 1 || o.n_paths > tmpc::GUIDANCE_MAX_PATHS) { h->err = std::string(fn) + ": 1 <= n_paths <= 63"; return false; }
+    g = tmpc::GuidanceOptions{o.n_paths, o.use_tmpcpp ? 1 : 0, o.warmstart_with_mpc_solution ? 1 : 0, o.shift_previous_solution_forward ? 1 : 0,
+                              o.selection_weight_consistency};
+    return true;
+}
+
+int tmpc_guidance_plan(tmpc_handle *h, int32_t n_scenes, const tmpc_guidance_options *opt, const void *d_traj_count, const void *d_topology_class,
+                       const void *d_previously_selected, const void *d_planner_ids, const void *d_selection, void *d_mode, void *d_src,
+                       void *d_init_enabled, void *d_rows_dummy, void *d_disabled, void *d_guidance_id, void *d_weight)
+{
+    if (!h) return TMPC_ERR_INVALID;
+    tmpc::GuidanceOptions g{};
+    if (!read_guidance_options(h, "tmpc_guidance_plan", n_scenes, opt, g)) return TMPC_ERR_INVALID;
+    if (!d_traj_count || !d_topology_class || !d_planner_ids || !d_selection) {
+        h->err = "tmpc_guidance_plan: NULL input (d_traj_count, d_topology_class, d_planner_ids, d_selection)"; return TMPC_ERR_INVALID;
+    }
+    if (!d_mode || !d_src || !d_init_enabled || !d_rows_dummy || !d_disabled || !d_guidance_id || !d_weight) {
+        h->err = "tmpc_guidance_plan: NULL output (d_mode, d_src, d_init_enabled, d_rows_dummy, d_disabled, d_guidance_id, d_weight)"; return TMPC_ERR_INVALID;
+    }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_guidance_plan_kernel, dim3((unsigned)((n_scenes + 63) / 64)), dim3(64), 0, h->stream, n_scenes, g,
+                       (const int *)d_traj_count, (const int *)d_topology_class, (const uint8_t *)d_previously_selected, (const int *)d_planner_ids,
+                       (const int *)d_selection, (int *)d_mode, (int *)d_src, (uint8_t *)d_init_enabled, (uint8_t *)d_rows_dummy, (uint8_t *)d_disabled,
+                       (int *)d_guidance_id, (double *)d_weight);
+    TMPC_HIP_CHECK(h, hipGetLastError());
+    return TMPC_OK;
+}
+
+int tmpc_guidance_decide(tmpc_handle *h, int32_t n_scenes, const tmpc_guidance_options *opt, const void *d_pobj, const void *d_exit_code,
+                         const void *d_disabled, const void *d_guidance_id, const void *d_weight, const void *d_state, double deceleration,
+                         double control_dt, int32_t enable_output, void *d_best, void *d_exit, void *d_cmd, void *d_planner_ids, void *d_selection)
+{
+    if (!h) return TMPC_ERR_INVALID;
+    tmpc::GuidanceOptions g{};
+    if (!read_guidance_options(h, "tmpc_guidance_decide", n_scenes, opt, g)) return TMPC_ERR_INVALID;
+    if (!d_pobj || !d_exit_code || !d_disabled || !d_guidance_id || !d_weight || !d_state) {
+        h->err = "tmpc_guidance_decide: NULL input (d_pobj, d_exit_code, d_disabled, d_guidance_id, d_weight, d_state)"; return TMPC_ERR_INVALID;
+    }
+    if (!d_best || !d_exit || !d_cmd || !d_planner_ids || !d_selection) {
+        h->err = "tmpc_guidance_decide: NULL output (d_best, d_exit, d_cmd, d_planner_ids, d_selection)"; return TMPC_ERR_INVALID;
+    }
+    if (h->B <= 0 || h->solved_B != h->B) { h->err = "tmpc_guidance_decide: no solved batch (tmpc_solve after tmpc_set_batch*)"; return TMPC_ERR_INVALID; }
+    if ((int64_t)n_scenes * (g.n_paths + g.use_tmpcpp) != h->B) { h->err = "tmpc_guidance_decide: the batch is not n_scenes x P entries"; return TMPC_ERR_INVALID; }
+    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(tmpc::tmpc_guidance_decide_kernel, dim3((unsigned)((n_scenes + 63) / 64)), dim3(64), 0, h->stream, n_scenes, g, h->d.N,
+                       tmpc::ext_nx(h->d), (const double *)d_pobj, (const int *)d_exit_code, (const uint8_t *)d_disabled, (const int *)d_guidance_id,
+                       (const double *)d_weight, (const double *)d_state, h->xtraj, h->utraj, deceleration, control_dt, enable_output ? 1 : 0,
+                       (int *)d_best, (int *)d_exit, (double *)d_cmd, (int *)d_planner_ids, (int *)d_selection);
     TMPC_HIP_CHECK(h, hipGetLastError());
     return TMPC_OK;
 }

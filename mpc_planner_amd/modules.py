@@ -574,6 +574,132 @@ def map_guidance_trajectories_to_planners(planner_guidance_ids, topology_classes
     return mapping, taken, existing
 
 
+# ---- the guidance hand-off: host mirrors of tmpc_sample_guidance / tmpc_guidance_plan / tmpc_guidance_decide, bit for bit ------
+GUIDANCE_MAX_NODES = 64
+GUIDANCE_MAX_PATHS = 63
+
+
+def sample_guidance(nodes, N, dt, n_nodes_max=GUIDANCE_MAX_NODES):
+    """One guidance trajectory's nodes [n][3] = (t, x, y) to what initialize_solver_with_guidance reads: position and velocity [N + 1][2] at
+    t = k dt (GetGuidanceTrajectory(id).spline.GetTrajectory(), guidance_constraints.cpp:390-414).  RosTools::Spline2D is not in the reference
+    tree: restated as U18 -- x(t), y(t) the natural cubic splines of fit_cubic over the knots t_i; sample k on segment
+    i = max{j <= n - 2 : t_j <= t}, 0 if there is none (so the first / last cubic continues outside the node span), tau = t - t_i, position
+    ((a tau + b) tau + c) tau + d, velocity (3 a tau + 2 b) tau + c, no fused multiply-add.  Returns (pos, vel, status): status 1 and zero
+    rows if n is outside [2, n_nodes_max] or a knot spacing is not positive and finite (path_knots_valid).  Host mirror of tmpc_sample_guidance."""
+    nodes = np.asarray(nodes, float).reshape(-1, 3)
+    n = len(nodes)
+    pos, vel = np.zeros((N + 1, 2)), np.zeros((N + 1, 2))
+    if n < 2 or n > n_nodes_max or not path_knots_valid(nodes[:, 0]):
+        return pos, vel, 1
+    t = nodes[:, 0]
+    curves = [fit_cubic(t, nodes[:, 1]), fit_cubic(t, nodes[:, 2])]
+    with np.errstate(all="ignore"):
+        for k in range(N + 1):
+            tk = float(k) * float(dt)
+            i = 0
+            for j in range(n - 1):
+                if t[j] <= tk:
+                    i = j
+            tau = tk - float(t[i])
+            for c, cur in enumerate(curves):
+                a, b, cc, d = (float(x) for x in cur[i])
+                pos[k, c] = ((a * tau + b) * tau + cc) * tau + d
+                vel[k, c] = (3.0 * a * tau + 2.0 * b) * tau + cc
+    return pos, vel, 0
+
+
+def guidance_plan(traj_count, topology_class, planner_ids, selection, n_paths, use_tmpcpp=True, warmstart_with_mpc_solution=False,
+                  shift_previous_solution_forward=True, selection_weight_consistency=1.0, previously_selected=None):
+    """What every planner of every scene does this tick (host mirror of tmpc_guidance_plan): mapGuidanceTrajectoriesToPlanners and the
+    per-planner branches of GuidanceConstraints::optimize (guidance_constraints.cpp:192-250, :283-317, :343-360) with the main solver's start
+    (planner.cpp:78-86), `enable_constraints = true`.  Entry b = q P + p, P = n_paths + use_tmpcpp, the non-guided planner last; planner p
+    follows trajectory p.  traj_count [Q], topology_class [Q][n_paths], previously_selected [Q][n_paths] or None; the cross-tick state
+    planner_ids [Q][P] (each planner's last guidance ID, -1 at the start) and selection [Q][3] = (selected ID, selected was the non-guided
+    planner, last best index; (-1, 0, -1) at the start) is read only.  Returns a dict of flat [Q P] arrays: mode / src for the warm start
+    (main start: last best >= 0 ? (shift ? 1 : 2, q P + best) : (3, b); a guided, enabled planner with warmstart_with_mpc_solution and
+    existing_guidance: its own solution), init_enabled (guidance initialisation), rows_dummy (non-guided or disabled), disabled,
+    guidance_id (2 n_paths / class / -1), weight, and existing_guidance."""
+    Q = len(traj_count)
+    P = int(n_paths) + (1 if use_tmpcpp else 0)
+    out = dict(mode=np.zeros(Q * P, np.int32), src=np.zeros(Q * P, np.int32), init_enabled=np.zeros(Q * P, np.uint8),
+               rows_dummy=np.zeros(Q * P, np.uint8), disabled=np.zeros(Q * P, np.uint8), guidance_id=np.zeros(Q * P, np.int32),
+               weight=np.ones(Q * P), existing_guidance=np.zeros(Q * P, np.uint8))
+    warm_mode = 1 if shift_previous_solution_forward else 2
+    for q in range(Q):
+        n_traj = min(max(int(traj_count[q]), 0), int(n_paths))
+        classes = [int(c) for c in topology_class[q][:n_traj]]
+        _, _, existing = map_guidance_trajectories_to_planners([int(i) for i in planner_ids[q][:P]], classes)
+        sel_id, sel_original, last_best = (int(v) for v in selection[q][:3])
+        for p in range(P):
+            b = q * P + p
+            original = bool(use_tmpcpp) and p == P - 1
+            disabled = p >= n_traj and not original                                   # (:286-293)
+            mode, src = (warm_mode, q * P + last_best) if last_best >= 0 else (3, b)  # the copy of the main solver (planner.cpp:78-86)
+            init = 0
+            weight = 1.0
+            if original:
+                gid = 2 * int(n_paths)                                                # (:349)
+            elif disabled:
+                gid = -1                                                              # SolverResult::Reset
+            else:
+                if warmstart_with_mpc_solution and existing[p]:
+                    mode, src = warm_mode, b                                          # (:310-311)
+                else:
+                    init = 1                                                          # (:312-313)
+                gid = classes[p]
+                if previously_selected is not None:
+                    chosen = bool(previously_selected[q][p])
+                else:
+                    chosen = sel_id >= 0 and sel_original == 0 and gid == sel_id
+                if chosen:
+                    weight = float(selection_weight_consistency)                      # (:358-359)
+            out["mode"][b], out["src"][b], out["init_enabled"][b] = mode, src, init
+            out["rows_dummy"][b] = 1 if (original or disabled) else 0
+            out["disabled"][b], out["guidance_id"][b], out["weight"][b] = (1 if disabled else 0), gid, weight
+            out["existing_guidance"][b] = 1 if existing[p] else 0
+    return out
+
+
+def guidance_decide(pobj, exit_code, disabled, guidance_id, weight, state, xtraj, utraj, planner_ids, selection, n_paths, use_tmpcpp=True,
+                    deceleration=3.0, control_dt=0.05, enable_output=True):
+    """The decision after the solve (host mirror of tmpc_guidance_decide): FindBestPlanner (guidance_constraints.cpp:416-434) over each scene's
+    P entries of the flat [Q P] arrays -- disabled skipped, success exit_code == 1, objective pobj x weight, initial value 1e10, strict '<' --,
+    decide()'s exit code (:366-387: the winner's; without one planner 0's, -1 if that one is disabled), the command of
+    ros1_jackalsimulator.cpp:181-201 from xtraj [Q P][N + 1][nx] / utraj [Q P][N][nu] and state [Q][nx], and the cross-tick state.
+    Returns dict(best [Q], exit [Q], cmd [Q][2], planner_ids [Q][P], selection [Q][3]); the state arrays are new copies."""
+    P = int(n_paths) + (1 if use_tmpcpp else 0)
+    Q = len(state)
+    ids = np.array(planner_ids, np.int32).reshape(Q, P).copy()
+    sel = np.array(selection, np.int32).reshape(Q, 3).copy()
+    best_out, exit_out, cmd = np.zeros(Q, np.int32), np.zeros(Q, np.int32), np.zeros((Q, 2))
+    for q in range(Q):
+        best_solution, best = 1e10, -1
+        for p in range(P):
+            b = q * P + p
+            if disabled[b]:
+                continue
+            objective = float(pobj[b]) * float(weight[b])
+            if int(exit_code[b]) == 1 and objective < best_solution:
+                best_solution, best = objective, p
+        best_out[q] = best
+        if best >= 0:
+            exit_out[q] = int(exit_code[q * P + best])
+        else:
+            exit_out[q] = -1 if disabled[q * P] else int(exit_code[q * P])
+        if best >= 0 and enable_output:
+            cmd[q] = (xtraj[q * P + best][1][3], utraj[q * P + best][0][1])
+        else:
+            w = float(state[q][3]) - float(deceleration) * float(control_dt)
+            cmd[q] = (0.0 if w < 0.0 else w, 0.0)
+        for p in range(P):
+            ids[q, p] = int(guidance_id[q * P + p])
+        if best >= 0:
+            sel[q, 0] = int(guidance_id[q * P + best])
+            sel[q, 1] = 1 if (use_tmpcpp and best == P - 1) else 0
+        sel[q, 2] = best
+    return dict(best=best_out, exit=exit_out, cmd=cmd, planner_ids=ids, selection=sel)
+
+
 # ---- obstacle preparation: host mirror of mpc_planner/src/data_preparation.cpp and of tmpc_prepare_obstacles_kernel, bit for bit -----------
 # An obstacle set is a dict of arrays over n obstacles: position [n][2] (the current position), pos [n][N][2], angle / major / minor [n][N]
 # (mode 0 of the prediction), radius [n], gaussian [n] (bool: PredictionType::GAUSSIAN, else DETERMINISTIC).

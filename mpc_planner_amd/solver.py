@@ -49,7 +49,8 @@ EXPORTS = ["tmpc_default_dims", "tmpc_default_dims_ex", "tmpc_create", "tmpc_des
            "tmpc_scenario_discard", "tmpc_scenario_discarded", "tmpc_linearize_topology_ex", "tmpc_clear_slot", "tmpc_gather_best",
            "tmpc_create_v2", "tmpc_set_param_sharing_ex", "tmpc_latency_mode_capacity", "tmpc_has_lane_kernels", "tmpc_debug_lds_passes", "tmpc_debug_poison_lds", "tmpc_has_lab_switches",
            "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters", "tmpc_track_path", "tmpc_set_path_parameters", "tmpc_fit_path",
-           "tmpc_costmap_points", "tmpc_decomp_halfspaces", "tmpc_set_halfspace_rows", "tmpc_path_velocity_window", "tmpc_scatter_parameters"]
+           "tmpc_costmap_points", "tmpc_decomp_halfspaces", "tmpc_set_halfspace_rows", "tmpc_path_velocity_window", "tmpc_scatter_parameters",
+           "tmpc_sample_guidance", "tmpc_guidance_plan", "tmpc_guidance_decide"]
 
 
 class TmpcObstacleOptions(C.Structure):
@@ -61,6 +62,19 @@ class TmpcObstacleOptions(C.Structure):
 class TmpcPathOptions(C.Structure):
     """tmpc_path_options (include/tmpc_hip.h)."""
     _fields_ = [("size", C.c_uint32), ("search_range", C.c_int32), ("window_segments", C.c_int32)]
+
+
+class TmpcGuidanceOptions(C.Structure):
+    """tmpc_guidance_options (include/tmpc_hip.h)."""
+    _fields_ = [("size", C.c_uint32), ("n_paths", C.c_int32), ("use_tmpcpp", C.c_int32), ("warmstart_with_mpc_solution", C.c_int32),
+                ("shift_previous_solution_forward", C.c_int32), ("reserved", C.c_int32), ("selection_weight_consistency", C.c_double)]
+
+
+def guidance_options(n_paths, use_tmpcpp=True, warmstart_with_mpc_solution=False, shift_previous_solution_forward=True,
+                     selection_weight_consistency=1.0):
+    """A filled tmpc_guidance_options for BatchedSolver.guidance_plan / guidance_decide."""
+    return TmpcGuidanceOptions(C.sizeof(TmpcGuidanceOptions), int(n_paths), int(bool(use_tmpcpp)), int(bool(warmstart_with_mpc_solution)),
+                               int(bool(shift_previous_solution_forward)), 0, float(selection_weight_consistency))
 
 
 class TmpcError(RuntimeError):
@@ -139,6 +153,10 @@ def load_library(path=None):
     if hasattr(lib, "tmpc_path_velocity_window"):
         lib.tmpc_path_velocity_window.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 7 + [C.c_double, vp, vp]
         lib.tmpc_scatter_parameters.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32, vp, C.c_int32]
+    if hasattr(lib, "tmpc_guidance_plan"):
+        lib.tmpc_sample_guidance.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 5
+        lib.tmpc_guidance_plan.argtypes = [vp, C.c_int32, C.POINTER(TmpcGuidanceOptions)] + [vp] * 12
+        lib.tmpc_guidance_decide.argtypes = [vp, C.c_int32, C.POINTER(TmpcGuidanceOptions)] + [vp] * 6 + [C.c_double, C.c_double, C.c_int32] + [vp] * 5
     if hasattr(lib, "tmpc_decomp_halfspaces"):
         lib.tmpc_costmap_points.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, vp, vp, vp]
         lib.tmpc_decomp_halfspaces.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 7 + [C.c_int32, C.c_double, C.c_int32, vp, vp, vp]
@@ -623,6 +641,45 @@ class BatchedSolver:
     def init_with_guidance(self, d_gpos, d_gvel, d_enabled=None):
         self._check(self.lib.tmpc_init_with_guidance(self._h, C.c_void_p(d_gpos), C.c_void_p(d_gvel),
                                                      C.c_void_p(d_enabled) if d_enabled else None), "tmpc_init_with_guidance")
+
+    def sample_guidance(self, n_traj, n_nodes_max, d_nodes, d_node_count, d_gpos, d_gvel, d_status):
+        """Guidance nodes to the samples init_with_guidance reads (tmpc_sample_guidance; raw device pointers): per trajectory
+        the natural cubic splines x(t), y(t) through d_nodes [n_traj][n_nodes_max][3] = (t, x, y) (d_node_count of them, at most 64), sampled
+        at t = k dt, k = 0 .. N, into d_gpos / d_gvel [n_traj][N + 1][2]; d_status 1 and zero rows for an invalid node list.  Equal bit for
+        bit to modules.sample_guidance.  Needs no batch.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_sample_guidance"):
+            raise TmpcError("this library has no tmpc_sample_guidance (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        self._check(self.lib.tmpc_sample_guidance(self._h, int(n_traj), int(n_nodes_max), vp(d_nodes), vp(d_node_count), vp(d_gpos), vp(d_gvel),
+                                                  vp(d_status)), "tmpc_sample_guidance")
+
+    def guidance_plan(self, n_scenes, options, d_traj_count, d_topology_class, d_planner_ids, d_selection, d_mode, d_src, d_init_enabled,
+                      d_rows_dummy, d_disabled, d_guidance_id, d_weight, d_previously_selected=None):
+        """What every planner of every scene does this tick (tmpc_guidance_plan; options from guidance_options(); raw device pointers): from
+        the trajectory counts, the classes and the cross-tick state d_planner_ids [n_scenes][P] / d_selection [n_scenes][3] to d_mode / d_src
+        (warmstart), d_init_enabled (init_with_guidance), d_rows_dummy (linearize_topology_ex's d_is_original), d_disabled, d_guidance_id and
+        d_weight (guidance_decide), entry b = scene P + planner.  Equal to modules.guidance_plan.  Needs no batch.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_guidance_plan"):
+            raise TmpcError("this library has no tmpc_guidance_plan (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        self._check(self.lib.tmpc_guidance_plan(self._h, int(n_scenes), C.byref(options) if options is not None else None, vp(d_traj_count),
+                                                vp(d_topology_class), vp(d_previously_selected), vp(d_planner_ids), vp(d_selection), vp(d_mode),
+                                                vp(d_src), vp(d_init_enabled), vp(d_rows_dummy), vp(d_disabled), vp(d_guidance_id), vp(d_weight)),
+                    "tmpc_guidance_plan")
+
+    def guidance_decide(self, n_scenes, options, d_pobj, d_exit_code, d_disabled, d_guidance_id, d_weight, d_state, d_best, d_exit, d_cmd,
+                        d_planner_ids, d_selection, deceleration=3.0, control_dt=0.05, enable_output=True):
+        """The decision after the solve (tmpc_guidance_decide; raw device pointers): per scene FindBestPlanner over the enabled planners into
+        d_best (as gather_best reads it), the exit code into d_exit, the command (v of node 1, w of node 0) of the winner or the braking
+        command into d_cmd [n_scenes][2], and the cross-tick state d_planner_ids / d_selection for the next guidance_plan.  d_pobj /
+        d_exit_code: result_device_ptrs(), or arrays of the caller's.  Equal bit for bit to modules.guidance_decide.  Stream-ordered."""
+        if not hasattr(self.lib, "tmpc_guidance_decide"):
+            raise TmpcError("this library has no tmpc_guidance_decide (a missing kernel is an error, there is no host fallback)")
+        vp = lambda p_: C.c_void_p(p_) if p_ else None
+        self._check(self.lib.tmpc_guidance_decide(self._h, int(n_scenes), C.byref(options) if options is not None else None, vp(d_pobj),
+                                                  vp(d_exit_code), vp(d_disabled), vp(d_guidance_id), vp(d_weight), vp(d_state), float(deceleration),
+                                                  float(control_dt), 1 if enable_output else 0, vp(d_best), vp(d_exit), vp(d_cmd), vp(d_planner_ids),
+                                                  vp(d_selection)), "tmpc_guidance_decide")
 
     def debug_get_x0(self):
         x0 = np.zeros((self.B, self.N + 1, self.dims.nvar)); xinit = np.zeros((self.B, self.dims.nx))

@@ -16,7 +16,11 @@ polyline along each scene's own warm start.  One JSON line per kernel with the e
 `--velocity [--segments n]`: the velocity-profile kernel and the column scatter alone (tmpc_path_velocity_window, tmpc_scatter_parameters) at
 512 scenes x 64 trajectories, S = 5, N = 20: 512 paths of n segments (default 64) fitted on device with a velocity at every waypoint, closest_s
 anywhere on the path, v_ref requested; the scatter writes the window's S x 4 = 20 values into 20 columns of every stage of every entry.  One
-JSON line per kernel: the mean of 50 launches between two HIP events."""
+JSON line per kernel: the mean of 50 launches between two HIP events.
+`--guidance`: the three guidance hand-off kernels alone (tmpc_sample_guidance, tmpc_guidance_plan, tmpc_guidance_decide) at 512 scenes x (4 + 1)
+planners = 2560 entries, 8 nodes per trajectory, N = 30 (cfg 2's rows): 16 generated scenes repeated, two to four trajectories found per scene,
+the state carried from launch to launch.  tmpc_guidance_decide needs a solved batch, so the run holds ONE tmpc_solve before the timed launches
+(its kernel is listed separately in a profile).  One JSON line per kernel: the mean of 50 launches between two HIP events."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -226,6 +230,66 @@ def velocity_kernels(n_seg, n_scenes=512, traj=64, N=20, S=5):
     so.close()
 
 
+def guidance_kernels(n_scenes=512, n_paths=4, n_nodes=8, N=30, M=8, S=5):
+    rng = np.random.default_rng(18)
+    P = n_paths + 1
+    B = n_scenes * P
+    so = solver.BatchedSolver(solver.default_dims(N=N, S=S, n_lin=M, M=M), B_max=B)
+    scs = [scenes.make_scene(500 + i, N=N, M=M, B=n_paths, tmpc_pp=True) for i in range(16)]
+    rep = n_scenes // len(scs)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    tile = lambda k: np.concatenate([np.concatenate([sc[k] for sc in scs])] * rep)
+    xinit = tile("xinit")
+    t_xinit, t_x0, t_params = up(xinit), up(tile("x0")), up(tile("params"))
+    so.set_batch_device(B, t_xinit.data_ptr(), t_x0.data_ptr(), t_params.data_ptr())
+    so.solve()
+    d_pobj, d_code = so.result_device_ptrs()
+    # nodes: every guided entry's guidance trajectory at n_nodes stages of the horizon; none for the non-guided planner
+    stages = np.linspace(0, N, n_nodes).round().astype(int)
+    nodes, node_count = np.zeros((B, n_nodes, 3)), np.zeros(B, np.int32)
+    for q in range(n_scenes):
+        sc = scs[q % len(scs)]
+        for p in range(n_paths):
+            nodes[q * P + p] = np.concatenate([stages[:, None] * so.dims.dt, sc["guidance_pos"][p][stages]], 1)
+            node_count[q * P + p] = n_nodes
+    t_nodes, t_ncnt = up(nodes), up(node_count)
+    t_cnt, t_cls = up(rng.integers(2, n_paths + 1, n_scenes).astype(np.int32)), up(rng.integers(0, 6, (n_scenes, n_paths)).astype(np.int32))
+    t_ids = torch.full((n_scenes, P), -1, dtype=torch.int32, device=dev); t_sel = up(np.tile(np.array([-1, 0, -1], np.int32), (n_scenes, 1)))
+    i32, u8, f64 = torch.int32, torch.uint8, torch.float64
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+    t_mode, t_src, t_gid, t_init, t_dummy, t_dis, t_w = z(B, i32), z(B, i32), z(B, i32), z(B, u8), z(B, u8), z(B, u8), z(B, f64)
+    t_gpos, t_gvel, t_status = z((B, N + 1, 2), f64), z((B, N + 1, 2), f64), z(B, i32)
+    t_best, t_exit, t_cmd, t_state = z(n_scenes, i32), z(n_scenes, i32), z((n_scenes, 2), f64), up(xinit[::P].copy())
+    opt = solver.guidance_options(n_paths, True, True, True, 0.8)
+    sample = lambda: so.sample_guidance(B, n_nodes, t_nodes.data_ptr(), t_ncnt.data_ptr(), t_gpos.data_ptr(), t_gvel.data_ptr(), t_status.data_ptr())
+    plan = lambda: so.guidance_plan(n_scenes, opt, t_cnt.data_ptr(), t_cls.data_ptr(), t_ids.data_ptr(), t_sel.data_ptr(), t_mode.data_ptr(), t_src.data_ptr(),
+                                    t_init.data_ptr(), t_dummy.data_ptr(), t_dis.data_ptr(), t_gid.data_ptr(), t_w.data_ptr())
+    decide = lambda: so.guidance_decide(n_scenes, opt, d_pobj, d_code, t_dis.data_ptr(), t_gid.data_ptr(), t_w.data_ptr(), t_state.data_ptr(), t_best.data_ptr(),
+                                        t_exit.data_ptr(), t_cmd.data_ptr(), t_ids.data_ptr(), t_sel.data_ptr())
+    hs = torch.cuda.ExternalStream(so.stream_ptr(), device=dev)
+    torch.cuda.synchronize()
+    for name, call in (("tmpc_guidance_plan_kernel", plan), ("tmpc_sample_guidance_kernel", sample), ("tmpc_guidance_decide_kernel", decide)):
+        for _ in range(10):
+            call()
+        so.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(hs):
+            e0.record()
+        for _ in range(50):
+            call()
+        with torch.cuda.stream(hs):
+            e1.record()
+        so.synchronize()
+        print(json.dumps(dict(kernel=name, n_scenes=n_scenes, planners=P, entries=B, nodes=n_nodes, N=N,
+                              us_per_launch_events=e0.elapsed_time(e1) * 1e3 / 50)), flush=True)
+    assert int(t_status.sum().item()) == n_scenes and int((t_best >= 0).sum().item()) > 0          # the non-guided entries have no nodes; some scene has a winner
+    so.close()
+
+
+if "--guidance" in sys.argv:
+    guidance_kernels()
+    print("done")
+    sys.exit(0)
 if "--velocity" in sys.argv:
     velocity_kernels(int(sys.argv[sys.argv.index("--segments") + 1]) if "--segments" in sys.argv else 64)
     print("done")
