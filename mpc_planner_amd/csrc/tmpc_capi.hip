@@ -6,7 +6,9 @@
 // instantiated here.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include "tmpc_kernels.hpp"
+#include "tmpc_handle_layout.hpp"
 #include "tmpc_instances.hpp"
 #if !defined(TMPC_GENERATED_STAGE) && !defined(TMPC_SINGLE_TU)
 TMPC_ALL_INSTANCES(EXT)
@@ -413,6 +415,35 @@ static void set_resident(KernelSlot &s, int per_cu, int cus)
     s.resident = per_cu * cus;
     s.prio = per_cu * (s.threads / 64) == 8;
 }
+static_assert(IO_NU == NU, "tmpc_handle_layout.hpp sizes utraj with the kernels' control count");
+// ---- the persistent per-slot solver state of a handle (tmpc_solve_iterations) -------------------------------------------------------------------
+// Five device arrays of B_max slots, allocated together on first use and zeroed: a slot holds what one Solver capsule of the reference keeps between solves.
+struct SolverState {
+    enum { Z, PI, LAMH, STOPPED, HAS, COUNT };
+    // Z [N + 1][NV] the iterate; PI [N + 1][NX] equality multipliers; LAMH [N][n_up + M] row multipliers; STOPPED (i32) the iteration loop of the current
+    // solve() has ended; HAS (i32) the slot holds state of an earlier tmpc_solve_iterations (set by the kernels' store)
+    void *a[COUNT] = {};
+    template <class T> T *get(int i) const { return static_cast<T *>(a[i]); }
+    bool allocated() const { return a[Z] != nullptr; }
+    // bytes of B slots of array i: what is copied, zeroed and -- for B_max slots -- allocated
+    static size_t bytes(const Dims &d, size_t B, int i) { return B * (i <= LAMH ? slot_doubles(d, i) * sizeof(double) : sizeof(int)); }
+    // doubles of one slot of Z, PI or LAMH (the kernels' strides)
+    static size_t slot_doubles(const Dims &d, int i) { return i == Z ? (d.N + 1) * NV : i == PI ? (d.N + 1) * NX : d.N * (d.n_up + d.M); }
+    void release() { for (void *&p : a) { if (p) (void)hipFree(p); p = nullptr; } }
+    // All or nothing (a later call must not find half of the arrays), zeroed on `stream`.  LAMH is allocated one double longer than bytes() says: a problem
+    // without inequality rows (n_up + M = 0) has no row multipliers, and a zero-size hipMalloc may hand back a null pointer -- the memset of it would then
+    // fail the whole allocation, and the kernels would be given a null lamh.  That double is never read, copied or reset.
+    bool allocate(const Dims &d, size_t B_max, hipStream_t stream)
+    {
+        bool ok = true;
+        for (int i = 0; i < COUNT && ok; i++) {
+            const size_t n = bytes(d, B_max, i) + (i == LAMH ? 8 : 0);
+            ok = hipMalloc(&a[i], n) == hipSuccess && hipMemsetAsync(a[i], 0, n, stream) == hipSuccess;
+        }
+        if (!ok) release();
+        return ok;
+    }
+};
 }  // namespace tmpc
 
 struct tmpc_handle {
@@ -425,12 +456,13 @@ struct tmpc_handle {
     double *xtraj = nullptr, *utraj = nullptr, *pobj = nullptr, *res_eq = nullptr, *d_weight = nullptr;
     int *exit_code = nullptr, *qp_status = nullptr, *sqp_iter = nullptr, *qp_iter = nullptr, *d_best = nullptr;
     uint8_t *d_disabled = nullptr;
-    // Control-tick handles (inputs and outputs of B_max trajectories <= TICK_SLAB_MAX bytes each): the owned input buffers (+ the slot map) are ONE device
-    // allocation, the outputs another, each mirrored in pinned host memory with the same layout -- tmpc_set_batch is one asynchronous H2D copy instead of
-    // three staged ones, tmpc_set_slots needs no stream synchronisation, tmpc_get is one D2H copy instead of eight (round 6: the C++ BatchContext's tick
-    // spent ~0.2 ms of 1.1 ms in those thirteen transfers).  Larger handles (the bench's 32768 trajectories) keep separate allocations and direct copies.
-    char *slab_in = nullptr, *slab_out = nullptr, *pin_in = nullptr, *pin_out = nullptr;
-    size_t slab_in_bytes = 0, slab_out_bytes = 0;
+    // The owned input buffers (+ the slot map) are ONE device allocation, the outputs another, laid out by `io` (tmpc_handle_layout.hpp); the typed pointers
+    // above and d_slot point into them.  Control-tick handles (io.tick) mirror both in pinned host memory with the same layout -- tmpc_set_batch is one
+    // asynchronous H2D copy instead of three staged ones, tmpc_set_slots needs no stream synchronisation, tmpc_get is one D2H copy instead of eight (round 6:
+    // the C++ BatchContext's tick spent ~0.2 ms of 1.1 ms in those thirteen transfers).  Larger handles (the bench's 32768 trajectories) have no mirrors:
+    // direct copies and a stream synchronisation.
+    tmpc::IoLayout io;
+    char *dev_in = nullptr, *dev_out = nullptr, *pin_in = nullptr, *pin_out = nullptr;
     hipEvent_t in_done = nullptr, slot_done = nullptr;    // the last H2D copies out of pin_in -- batch inputs / slot map: disjoint regions of the mirror, each rewritten only after ITS copy
     bool in_pending = false, slot_pending = false;
     tmpc::KernelSlot slot[tmpc::SLOT_COUNT];  // the solve kernels (tmpc::Slot)
@@ -439,11 +471,8 @@ struct tmpc_handle {
     int latency_mode = 0;                     // 0: throughput kernels, 1-3: the latency slots (tmpc_set_latency_mode)
     bool throughput_mode = false;             // lane-per-trajectory kernels (tmpc_lanes.hip) instead of one wave per trajectory
     tmpc::lanes::Context *lanes = nullptr;    // their HBM workspace, created when the mode is first enabled
-    // persistent per-slot solver state (tmpc_solve_iterations), allocated on first use
-    double *st_z = nullptr, *st_pi = nullptr, *st_lamh = nullptr;
-    int *st_stopped = nullptr;
-    int *st_has = nullptr;           // [B_max] the slot holds state of an earlier tmpc_solve_iterations (set by the kernels' store)
-    int *d_slot = nullptr;           // [B_max] state slot of every batch entry (tmpc_set_slots)
+    tmpc::SolverState st;            // persistent per-slot solver state (tmpc_solve_iterations), allocated on first use
+    int *d_slot = nullptr;           // [B_max] state slot of every batch entry (tmpc_set_slots): inside dev_in
     bool slots_set = false;
     int slots_B = 0;                 // batch size the slot map was given for: a map of another size is refused, never read past its end
     int *d_share = nullptr;          // [B_max] tmpc_set_param_sharing
@@ -463,6 +492,31 @@ struct tmpc_handle {
     int ev_used = 0;
     bool timing = false;
     std::string err;
+
+    tmpc_handle() = default;
+    tmpc_handle(const tmpc_handle &) = delete;
+    tmpc_handle &operator=(const tmpc_handle &) = delete;
+    // The handle owns everything above but the borrowed batch pointers; a handle that tmpc_create gave up half-way is released the same way.  (So the early
+    // failure paths of tmpc_create, hipSetDevice's own failure among them, now also set the calling thread's device -- to one the device count has confirmed
+    // -- where a bare delete did not.)
+    ~tmpc_handle()
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (void *p : {(void *)dev_in, (void *)dev_out, (void *)d_weight, (void *)d_best, (void *)d_disabled, (void *)d_share, (void *)scn_sample, (void *)scn_discard,
+                        (void *)ws, (void *)ticket})
+            if (p) (void)hipFree(p);
+        st.release();
+        if (pin_in) (void)hipHostFree(pin_in);
+        if (pin_out) (void)hipHostFree(pin_out);
+        if (in_done) (void)hipEventDestroy(in_done);
+        if (slot_done) (void)hipEventDestroy(slot_done);
+        for (auto &e : ev) (void)hipEventDestroy(e);
+        tmpc::lanes::destroy(lanes);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    // all B_max slots of state array i, zeroed on the handle's stream
+    hipError_t zero_state(int i) { return hipMemsetAsync(st.a[i], 0, tmpc::SolverState::bytes(d, B_max, i), stream); }
 };
 
 #define TMPC_HIP_CHECK(h, expr)                                                                     \
@@ -500,6 +554,17 @@ template <class Options> static bool read_options(tmpc_handle *h, const char *fn
         if (tail[i]) { h->err = std::string(fn) + ": options holds a non-zero field this library does not know"; return false; }
     o = *options;
     return true;
+}
+
+// Grow-on-demand scratch of a handle: afterwards *p holds at least `need` elements (the old contents are not kept).  The stream may still read the old buffer:
+// it is synchronised before the buffer is freed; a failed allocation leaves no buffer and a capacity of 0.
+template <class T> static int grow_scratch(tmpc_handle *h, T **p, size_t *cap, size_t need)
+{
+    if (need <= *cap) return TMPC_OK;
+    if (*p) { TMPC_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    TMPC_HIP_CHECK(h, hipMalloc(p, need * sizeof(T)));
+    *cap = need;
+    return TMPC_OK;
 }
 
 namespace {
@@ -581,7 +646,8 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return TMPC_ERR_NO_DEVICE;
-    tmpc_handle *h = new tmpc_handle();
+    std::unique_ptr<tmpc_handle> owner(new tmpc_handle());      // until *out takes it: every failure below is a plain return
+    tmpc_handle *h = owner.get();
     h->device = device; h->B_max = B_max;
     tmpc::Dims &d = h->d;
     d.N = dims->N; d.S = dims->S; d.n_lin = dims->n_lin; d.M = dims->M; d.npar = dims->npar;
@@ -601,7 +667,7 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
     KernelSlot *slot = h->slot, &def = h->slot[tmpc::SLOT_DEFAULT];
     const bool schur = d.riccati_form == TMPC_RICCATI_SCHUR;      // the square-root form has its fast kernels only: no latency / compact variants
     def.kernel = schur ? tmpc::pick_fast_kernel(d, &def) : tmpc::pick_sqrt_kernel(d, &def);
-    if (!schur && !def.kernel) { delete h; return TMPC_ERR_INVALID; }       // (no square-root instantiation for this shape: never a silent other form)
+    if (!schur && !def.kernel) return TMPC_ERR_INVALID;       // (no square-root instantiation for this shape: never a silent other form)
     if (const char *lm = lab_env("TMPC_LATENCY_MODE")) {      // experiments: latency variant regardless of the caller ("0" .. "3"; anything else is ignored)
         if (lm[0] >= '0' && lm[0] <= '3' && lm[1] == '\0') h->latency_mode = lm[0] - '0';
     }
@@ -613,9 +679,8 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
         def.name = generic_names[sm]; def.threads = tmpc::NT; def.kind = KernelSlot::GENERIC;
     }
     def.lds_bytes = tmpc::slot_lds(d, tmpc::SLOT_DEFAULT, def, 0);
-    auto fail = [&](int code) { delete h; return code; };
-    if (hipSetDevice(device) != hipSuccess) return fail(TMPC_ERR_HIP);
-    if (def.lds_bytes > tmpc::LDS_CAP) return fail(TMPC_ERR_INVALID);
+    if (hipSetDevice(device) != hipSuccess) return TMPC_ERR_HIP;
+    if (def.lds_bytes > tmpc::LDS_CAP) return TMPC_ERR_INVALID;
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 0;
     // the latency slots: beside a fast one-wave default; lat2 and lat3 also beside a two-wave one at N > 20, lat3 also beside the generic kernel of
@@ -648,10 +713,10 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
         tmpc::choose_compact_pad(d, tmpc::SLOT_DEFAULT, def);
     }
     if (hipFuncSetAttribute((const void *)def.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)def.lds_bytes) != hipSuccess)
-        return fail(TMPC_ERR_NO_DEVICE);
+        return TMPC_ERR_NO_DEVICE;
     if (def.kind == KernelSlot::COMPACT) {
         const int per_cu = tmpc::blocks_per_cu(def.kernel, def.threads, def.lds_bytes);
-        if (per_cu <= 0 || cus <= 0) return fail(TMPC_ERR_HIP);
+        if (per_cu <= 0 || cus <= 0) return TMPC_ERR_HIP;
         tmpc::set_resident(def, per_cu, cus);
     }
     KernelSlot &cp2 = slot[tmpc::SLOT_CP2];
@@ -667,44 +732,23 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
             tmpc::set_resident(cp2, per_cu, cus);
         }
     }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(TMPC_ERR_HIP);
-    const size_t N = d.N, B = B_max;
-    bool ok = true;
-    const size_t nxe = tmpc::ext_nx(d), nve = tmpc::ext_nv(d);
-    {
-        constexpr size_t TICK_SLAB_MAX = 2u << 20;
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t in_sz[4] = {B * nxe * 8, B * (N + 1) * nve * 8, B * N * d.npar * 8, B * 4};
-        const size_t out_sz[8] = {B * (N + 1) * nxe * 8, B * N * tmpc::NU * 8, B * 8, B * 8, B * 4, B * 4, B * 4, B * 4};
-        size_t in_off[5] = {0}, out_off[9] = {0};
-        for (int i = 0; i < 4; i++) in_off[i + 1] = in_off[i] + up(in_sz[i]);
-        for (int i = 0; i < 8; i++) out_off[i + 1] = out_off[i] + up(out_sz[i]);
-        if (in_off[4] <= TICK_SLAB_MAX && out_off[8] <= TICK_SLAB_MAX) {
-            h->slab_in_bytes = in_off[4]; h->slab_out_bytes = out_off[8];
-            ok &= hipMalloc(&h->slab_in, in_off[4]) == hipSuccess && hipMalloc(&h->slab_out, out_off[8]) == hipSuccess;
-            ok &= hipHostMalloc(&h->pin_in, in_off[4], hipHostMallocDefault) == hipSuccess && hipHostMalloc(&h->pin_out, out_off[8], hipHostMallocDefault) == hipSuccess;
-            ok &= hipEventCreateWithFlags(&h->in_done, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&h->slot_done, hipEventDisableTiming) == hipSuccess;
-            if (ok) {
-                h->o_xinit = (double *)(h->slab_in + in_off[0]); h->o_x0 = (double *)(h->slab_in + in_off[1]); h->o_params = (double *)(h->slab_in + in_off[2]);
-                h->d_slot = (int *)(h->slab_in + in_off[3]);
-                h->xtraj = (double *)(h->slab_out + out_off[0]); h->utraj = (double *)(h->slab_out + out_off[1]); h->pobj = (double *)(h->slab_out + out_off[2]);
-                h->res_eq = (double *)(h->slab_out + out_off[3]); h->exit_code = (int *)(h->slab_out + out_off[4]); h->qp_status = (int *)(h->slab_out + out_off[5]);
-                h->sqp_iter = (int *)(h->slab_out + out_off[6]); h->qp_iter = (int *)(h->slab_out + out_off[7]);
-            }
-        } else {
-            ok &= hipMalloc(&h->o_xinit, in_sz[0]) == hipSuccess;
-            ok &= hipMalloc(&h->o_x0, in_sz[1]) == hipSuccess;
-            ok &= hipMalloc(&h->o_params, in_sz[2]) == hipSuccess;
-            ok &= hipMalloc(&h->xtraj, out_sz[0]) == hipSuccess;
-            ok &= hipMalloc(&h->utraj, out_sz[1]) == hipSuccess;
-            ok &= hipMalloc(&h->pobj, out_sz[2]) == hipSuccess;
-            ok &= hipMalloc(&h->res_eq, out_sz[3]) == hipSuccess;
-            ok &= hipMalloc(&h->exit_code, out_sz[4]) == hipSuccess;
-            ok &= hipMalloc(&h->qp_status, out_sz[5]) == hipSuccess;
-            ok &= hipMalloc(&h->sqp_iter, out_sz[6]) == hipSuccess;
-            ok &= hipMalloc(&h->qp_iter, out_sz[7]) == hipSuccess;
-        }
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return TMPC_ERR_HIP;
+    const size_t B = B_max;
+    const tmpc::IoLayout &io = h->io = tmpc::io_layout(d.N, tmpc::ext_nx(d), tmpc::ext_nv(d), d.npar, B);
+    bool ok = hipMalloc(&h->dev_in, io.in_total) == hipSuccess && hipMalloc(&h->dev_out, io.out_total) == hipSuccess;
+    if (io.tick) {
+        ok &= hipHostMalloc(&h->pin_in, io.in_total, hipHostMallocDefault) == hipSuccess && hipHostMalloc(&h->pin_out, io.out_total, hipHostMallocDefault) == hipSuccess;
+        ok &= hipEventCreateWithFlags(&h->in_done, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&h->slot_done, hipEventDisableTiming) == hipSuccess;
     }
+    if (!ok) return TMPC_ERR_HIP;
+    auto in = [&](int i) { return (void *)(h->dev_in + io.in[i].offset); };
+    auto res = [&](int i) { return (void *)(h->dev_out + io.out[i].offset); };
+    h->o_xinit = (double *)in(tmpc::IN_XINIT); h->o_x0 = (double *)in(tmpc::IN_X0);
+    h->o_params = (double *)in(tmpc::IN_PARAMS); h->d_slot = (int *)in(tmpc::IN_SLOT);
+    h->xtraj = (double *)res(tmpc::OUT_XTRAJ); h->utraj = (double *)res(tmpc::OUT_UTRAJ);
+    h->pobj = (double *)res(tmpc::OUT_POBJ); h->res_eq = (double *)res(tmpc::OUT_RES_EQ);
+    h->exit_code = (int *)res(tmpc::OUT_EXIT_CODE); h->qp_status = (int *)res(tmpc::OUT_QP_STATUS);
+    h->sqp_iter = (int *)res(tmpc::OUT_SQP_ITER); h->qp_iter = (int *)res(tmpc::OUT_QP_ITER);
     ok &= hipMalloc(&h->d_weight, B * 8) == hipSuccess;
     ok &= hipMalloc(&h->d_best, 4) == hipSuccess;
     ok &= hipMalloc(&h->d_disabled, B) == hipSuccess;
@@ -712,35 +756,12 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
         ok &= hipMalloc(&h->ws, (size_t)p->resident * tmpc::ws_doubles(d.N, p->threads == 128) * 8) == hipSuccess;
         ok &= hipMalloc(&h->ticket, 8 * 4) == hipSuccess;         // one work counter per XCD (next_trajectory)
     }
-    if (!ok) { tmpc_destroy(h); return TMPC_ERR_HIP; }
-    *out = h;
+    if (!ok) return TMPC_ERR_HIP;
+    *out = owner.release();
     return TMPC_OK;
 }
 
-void tmpc_destroy(tmpc_handle *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void *ptrs[] = {h->o_xinit, h->o_x0, h->o_params, h->xtraj, h->utraj, h->pobj, h->res_eq, h->d_weight,
-                    h->exit_code, h->qp_status, h->sqp_iter, h->qp_iter, h->d_best, h->d_disabled,
-                    h->st_z, h->st_pi, h->st_lamh, h->st_stopped, h->st_has, h->d_slot, h->d_share, h->scn_sample, h->scn_discard, h->ws, h->ticket};
-    auto in_slab = [&](void *p) {
-        return (h->slab_in && (char *)p >= h->slab_in && (char *)p < h->slab_in + h->slab_in_bytes) ||
-               (h->slab_out && (char *)p >= h->slab_out && (char *)p < h->slab_out + h->slab_out_bytes);
-    };
-    for (void *p : ptrs) if (p && !in_slab(p)) (void)hipFree(p);
-    if (h->slab_in) (void)hipFree(h->slab_in);
-    if (h->slab_out) (void)hipFree(h->slab_out);
-    if (h->pin_in) (void)hipHostFree(h->pin_in);
-    if (h->pin_out) (void)hipHostFree(h->pin_out);
-    if (h->in_done) (void)hipEventDestroy(h->in_done);
-    if (h->slot_done) (void)hipEventDestroy(h->slot_done);
-    for (auto &e : h->ev) (void)hipEventDestroy(e);
-    tmpc::lanes::destroy(h->lanes);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+void tmpc_destroy(tmpc_handle *h) { delete h; }
 
 const char *tmpc_last_error(const tmpc_handle *h) { return h ? h->err.c_str() : "null handle"; }
 
@@ -748,28 +769,24 @@ int tmpc_set_batch(tmpc_handle *h, int32_t B, const double *xinit, const double 
 {
     if (!h || B <= 0 || B > h->B_max || !xinit || !x0 || !params) { if (h) h->err = "tmpc_set_batch: bad argument"; return TMPC_ERR_INVALID; }
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    const size_t N = h->d.N;
-    const size_t in_bytes_B = (size_t)B * (tmpc::ext_nx(h->d) + (N + 1) * tmpc::ext_nv(h->d) + N * h->d.npar) * 8;
-    if (h->slab_in && in_bytes_B <= (512u << 10)) {                // (measured: at 64 trajectories = 1.4 MB the runtime's own path for pageable memory is 12 us faster than a host copy into the mirror)
+    const tmpc::IoRegion *r = h->io.in;
+    const void *src[tmpc::IO_BATCH_ARRAYS] = {xinit, x0, params};
+    auto copy = [&](const char *from_base, size_t i) {           // the first B trajectories of batch array i: out of the mirror (from_base) or the caller's array
+        return hipMemcpyAsync(h->dev_in + r[i].offset, from_base ? from_base + r[i].offset : src[i], r[i].bytes(B), hipMemcpyHostToDevice, h->stream);
+    };
+    if (h->pin_in && h->io.batch_bytes(B) <= (512u << 10)) {       // (measured: at 64 trajectories = 1.4 MB the runtime's own path for pageable memory is 12 us faster than a host copy into the mirror)
         // through the pinned mirror: one asynchronous copy of [xinit | x0 | params of the first B trajectories] (the regions of B_max trajectories lie in this order)
         if (h->in_pending) { TMPC_HIP_CHECK(h, hipEventSynchronize(h->in_done)); h->in_pending = false; }
-        const size_t o0 = (char *)h->o_xinit - h->slab_in, o1 = (char *)h->o_x0 - h->slab_in, o2 = (char *)h->o_params - h->slab_in;
-        const size_t n_par = (size_t)B * N * h->d.npar * 8;
-        std::memcpy(h->pin_in + o0, xinit, (size_t)B * tmpc::ext_nx(h->d) * 8);
-        std::memcpy(h->pin_in + o1, x0, (size_t)B * (N + 1) * tmpc::ext_nv(h->d) * 8);
-        std::memcpy(h->pin_in + o2, params, n_par);
-        if (o2 <= (256u << 10)) {                                   // (B_max close to B, as for a control tick's handle: the gaps cost less than two more copies)
-            TMPC_HIP_CHECK(h, hipMemcpyAsync(h->slab_in, h->pin_in, o2 + n_par, hipMemcpyHostToDevice, h->stream));
+        for (size_t i = 0; i < tmpc::IO_BATCH_ARRAYS; i++) std::memcpy(h->pin_in + r[i].offset, src[i], r[i].bytes(B));
+        const tmpc::IoRegion &last = r[tmpc::IN_PARAMS];
+        if (last.offset <= (256u << 10)) {                          // (B_max close to B, as for a control tick's handle: the gaps cost less than two more copies)
+            TMPC_HIP_CHECK(h, hipMemcpyAsync(h->dev_in, h->pin_in, last.offset + last.bytes(B), hipMemcpyHostToDevice, h->stream));
         } else {
-            TMPC_HIP_CHECK(h, hipMemcpyAsync(h->o_xinit, h->pin_in + o0, (size_t)B * tmpc::ext_nx(h->d) * 8, hipMemcpyHostToDevice, h->stream));
-            TMPC_HIP_CHECK(h, hipMemcpyAsync(h->o_x0, h->pin_in + o1, (size_t)B * (N + 1) * tmpc::ext_nv(h->d) * 8, hipMemcpyHostToDevice, h->stream));
-            TMPC_HIP_CHECK(h, hipMemcpyAsync(h->o_params, h->pin_in + o2, n_par, hipMemcpyHostToDevice, h->stream));
+            for (size_t i = 0; i < tmpc::IO_BATCH_ARRAYS; i++) TMPC_HIP_CHECK(h, copy(h->pin_in, i));
         }
         TMPC_HIP_CHECK(h, hipEventRecord(h->in_done, h->stream)); h->in_pending = true;
     } else {
-    TMPC_HIP_CHECK(h, hipMemcpyAsync(h->o_xinit, xinit, (size_t)B * tmpc::ext_nx(h->d) * 8, hipMemcpyHostToDevice, h->stream));
-    TMPC_HIP_CHECK(h, hipMemcpyAsync(h->o_x0, x0, (size_t)B * (N + 1) * tmpc::ext_nv(h->d) * 8, hipMemcpyHostToDevice, h->stream));
-    TMPC_HIP_CHECK(h, hipMemcpyAsync(h->o_params, params, (size_t)B * N * h->d.npar * 8, hipMemcpyHostToDevice, h->stream));
+        for (size_t i = 0; i < tmpc::IO_BATCH_ARRAYS; i++) TMPC_HIP_CHECK(h, copy(nullptr, i));
     }
     h->xinit = h->o_xinit; h->x0 = h->o_x0; h->params = h->o_params; h->B = B;
     h->solved_B = 0;
@@ -819,7 +836,9 @@ static int launch_solve(tmpc_handle *h, int n_iter, int st_flags)
     } else {
         tmpc::Dims dd = h->d;
         dd.n_sqp = n_iter;
-        tmpc::StateIO io{h->st_z, h->st_pi, h->st_lamh, h->st_stopped, st_flags, h->ws, h->ticket, (h->slots_set && h->slots_B == h->B) ? h->d_slot : nullptr, h->st_has,
+        using St = tmpc::SolverState;
+        tmpc::StateIO io{h->st.get<double>(St::Z), h->st.get<double>(St::PI), h->st.get<double>(St::LAMH), h->st.get<int>(St::STOPPED), st_flags, h->ws, h->ticket,
+                         (h->slots_set && h->slots_B == h->B) ? h->d_slot : nullptr, h->st.get<int>(St::HAS),
                          (h->share_B == h->B) ? h->d_share : nullptr};      // (a map given for another batch size is not applied)
         const tmpc::KernelSlot &k = h->slot[launch_slot(h)];
         const bool persistent = k.kind == tmpc::KernelSlot::COMPACT;
@@ -833,8 +852,8 @@ static int launch_solve(tmpc_handle *h, int n_iter, int st_flags)
         TMPC_HIP_CHECK(h, hipGetLastError());
         if (st_flags & tmpc::ST_COMPLETE) {
             // a failed solve resets the reference's capsule (Solver_acados_reset, acados_solver_interface.cpp:187-191): zero multipliers
-            const int n_pi = (h->d.N + 1) * tmpc::NX, n_lam = h->d.N * (h->d.n_up + h->d.M);
-            hipLaunchKernelGGL(tmpc::tmpc_state_finalize_kernel, dim3(h->B), dim3(64), 0, h->stream, n_pi, n_lam, h->exit_code, h->st_pi, h->st_lamh,
+            const int n_pi = (int)St::slot_doubles(h->d, St::PI), n_lam = (int)St::slot_doubles(h->d, St::LAMH);
+            hipLaunchKernelGGL(tmpc::tmpc_state_finalize_kernel, dim3(h->B), dim3(64), 0, h->stream, n_pi, n_lam, h->exit_code, io.pi, io.lamh,
                                (h->slots_set && h->slots_B == h->B) ? h->d_slot : nullptr);
             TMPC_HIP_CHECK(h, hipGetLastError());
         }
@@ -859,7 +878,7 @@ static int share_check(tmpc_handle *h, const char *who)
 static int invalidate_state(tmpc_handle *h)
 {
     h->st_valid = false; h->st_B = 0;
-    if (h->st_has) TMPC_HIP_CHECK(h, hipMemsetAsync(h->st_has, 0, (size_t)h->B_max * 4, h->stream));
+    if (h->st.allocated()) TMPC_HIP_CHECK(h, h->zero_state(tmpc::SolverState::HAS));
     return TMPC_OK;
 }
 
@@ -884,16 +903,8 @@ int tmpc_solve_iterations(tmpc_handle *h, int32_t n_iter, int32_t flags)
                  std::to_string(h->B) + ": call tmpc_set_slots again after tmpc_set_batch (or clear it with a null map)";
         return TMPC_ERR_INVALID;
     }
-    if (!h->throughput_mode && !h->st_z) {
-        const size_t B = h->B_max, N = h->d.N, nh = h->d.n_up + h->d.M;
-        const size_t sz[5] = {B * (N + 1) * tmpc::NV * 8, B * (N + 1) * tmpc::NX * 8, (B * N * nh + 1) * 8, B * 4, B * 4};
-        void **dst[5] = {(void **)&h->st_z, (void **)&h->st_pi, (void **)&h->st_lamh, (void **)&h->st_stopped, (void **)&h->st_has};
-        bool ok = true;
-        for (int i = 0; i < 5 && ok; i++) ok = hipMalloc(dst[i], sz[i]) == hipSuccess && hipMemsetAsync(*dst[i], 0, sz[i], h->stream) == hipSuccess;
-        if (!ok) {                          // all or nothing: a later call must not find half of the arrays
-            for (int i = 0; i < 5; i++) { if (*dst[i]) (void)hipFree(*dst[i]); *dst[i] = nullptr; }
-            h->err = "tmpc_solve_iterations: state allocation failed"; return TMPC_ERR_HIP;
-        }
+    if (!h->throughput_mode && !h->st.allocated()) {
+        if (!h->st.allocate(h->d, h->B_max, h->stream)) { h->err = "tmpc_solve_iterations: state allocation failed"; return TMPC_ERR_HIP; }
         h->st_valid = false; h->st_B = 0;
     }
     int st = tmpc::ST_STORE;
@@ -913,7 +924,7 @@ int tmpc_solve_iterations(tmpc_handle *h, int32_t n_iter, int32_t flags)
     }
     if (flags & TMPC_ITER_COMPLETE) st |= tmpc::ST_COMPLETE;
     // a new solve() of the slots' Solvers: the "iteration loop has ended" marks belong to the previous solve (:105-106 is local to one solve())
-    if ((flags & TMPC_ITER_NEW_SOLVE) && !h->throughput_mode && h->st_stopped) TMPC_HIP_CHECK(h, hipMemsetAsync(h->st_stopped, 0, (size_t)h->B_max * 4, h->stream));
+    if ((flags & TMPC_ITER_NEW_SOLVE) && !h->throughput_mode && h->st.allocated()) TMPC_HIP_CHECK(h, h->zero_state(tmpc::SolverState::STOPPED));
     if ((flags & TMPC_ITER_NEW_SOLVE) && h->throughput_mode && h->lanes && tmpc::lanes::clear_stopped(h->lanes, h->stream, h->B_max, h->err)) return TMPC_ERR_HIP;
     const int rc = launch_solve(h, n_iter, st);
     if (rc == TMPC_OK && h->throughput_mode) { h->st_valid = true; if (h->B > h->st_B) h->st_B = h->B; }
@@ -926,10 +937,9 @@ int tmpc_reset_multipliers(tmpc_handle *h)
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
     if (h->throughput_mode) {
         if (h->lanes && tmpc::lanes::reset_multipliers(h->lanes, h->stream, h->B_max, h->err)) return TMPC_ERR_HIP;
-    } else if (h->st_pi) {
-        const size_t B = h->B_max, N = h->d.N, nh = h->d.n_up + h->d.M;
-        TMPC_HIP_CHECK(h, hipMemsetAsync(h->st_pi, 0, B * (N + 1) * tmpc::NX * 8, h->stream));
-        TMPC_HIP_CHECK(h, hipMemsetAsync(h->st_lamh, 0, B * N * nh * 8, h->stream));
+    } else if (h->st.allocated()) {
+        TMPC_HIP_CHECK(h, h->zero_state(tmpc::SolverState::PI));
+        TMPC_HIP_CHECK(h, h->zero_state(tmpc::SolverState::LAMH));
     }
     return TMPC_OK;
 }
@@ -973,16 +983,15 @@ int tmpc_set_slots(tmpc_handle *h, const int32_t *slots)
         seen[slots[b]] = 1;
     }
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    if (h->slab_in) {                                               // pinned mirror: asynchronous, nothing to wait for (the caller's array is copied here)
+    const tmpc::IoRegion &r = h->io.in[tmpc::IN_SLOT];
+    if (h->pin_in) {                                                // pinned mirror: asynchronous, nothing to wait for (the caller's array is copied here)
         if (h->slot_pending) { TMPC_HIP_CHECK(h, hipEventSynchronize(h->slot_done)); h->slot_pending = false; }      // (not the batch copy just enqueued: it reads other bytes)
-        const size_t o3 = (char *)h->d_slot - h->slab_in;
-        std::memcpy(h->pin_in + o3, slots, (size_t)h->B * 4);
-        TMPC_HIP_CHECK(h, hipMemcpyAsync(h->d_slot, h->pin_in + o3, (size_t)h->B * 4, hipMemcpyHostToDevice, h->stream));
+        std::memcpy(h->pin_in + r.offset, slots, r.bytes(h->B));
+        TMPC_HIP_CHECK(h, hipMemcpyAsync(h->d_slot, h->pin_in + r.offset, r.bytes(h->B), hipMemcpyHostToDevice, h->stream));
         TMPC_HIP_CHECK(h, hipEventRecord(h->slot_done, h->stream)); h->slot_pending = true;
     } else {
-    if (!h->d_slot) TMPC_HIP_CHECK(h, hipMalloc(&h->d_slot, (size_t)h->B_max * 4));
-    TMPC_HIP_CHECK(h, hipMemcpyAsync(h->d_slot, slots, (size_t)h->B * 4, hipMemcpyHostToDevice, h->stream));
-    TMPC_HIP_CHECK(h, hipStreamSynchronize(h->stream));            // (the caller's array may go away)
+        TMPC_HIP_CHECK(h, hipMemcpyAsync(h->d_slot, slots, r.bytes(h->B), hipMemcpyHostToDevice, h->stream));
+        TMPC_HIP_CHECK(h, hipStreamSynchronize(h->stream));        // (the caller's array may go away)
     }
     h->slots_set = true; h->slots_B = h->B;
     return TMPC_OK;
@@ -1023,23 +1032,13 @@ int tmpc_copy_state(tmpc_handle *dst, tmpc_handle *src)
         dst->device != src->device || dst->throughput_mode || src->throughput_mode) {
         dst->err = "tmpc_copy_state: handles of different shape / device / kernel family"; return TMPC_ERR_INVALID;
     }
-    if (!src->st_z) return TMPC_OK;                                 // nothing stored yet
+    if (!src->st.allocated()) return TMPC_OK;                                 // nothing stored yet
     TMPC_HIP_CHECK(dst, hipSetDevice(dst->device));
     TMPC_HIP_CHECK(dst, hipStreamSynchronize(src->stream));
-    if (!dst->st_z) {                                               // allocate through the regular path: an evaluation-only call on the (unset) batch is not possible, so inline it
-        const size_t B = dst->B_max, N = a.N, nh = a.n_up + a.M;
-        const size_t sz[5] = {B * (N + 1) * tmpc::NV * 8, B * (N + 1) * tmpc::NX * 8, (B * N * nh + 1) * 8, B * 4, B * 4};
-        void **p[5] = {(void **)&dst->st_z, (void **)&dst->st_pi, (void **)&dst->st_lamh, (void **)&dst->st_stopped, (void **)&dst->st_has};
-        bool ok = true;
-        for (int i = 0; i < 5 && ok; i++) ok = hipMalloc(p[i], sz[i]) == hipSuccess && hipMemsetAsync(*p[i], 0, sz[i], dst->stream) == hipSuccess;
-        if (!ok) { for (int i = 0; i < 5; i++) { if (*p[i]) (void)hipFree(*p[i]); *p[i] = nullptr; } dst->err = "tmpc_copy_state: allocation failed"; return TMPC_ERR_HIP; }
-    }
-    const size_t n = (size_t)(dst->B_max < src->B_max ? dst->B_max : src->B_max), N = a.N, nh = a.n_up + a.M;
-    TMPC_HIP_CHECK(dst, hipMemcpyAsync(dst->st_z, src->st_z, n * (N + 1) * tmpc::NV * 8, hipMemcpyDeviceToDevice, dst->stream));
-    TMPC_HIP_CHECK(dst, hipMemcpyAsync(dst->st_pi, src->st_pi, n * (N + 1) * tmpc::NX * 8, hipMemcpyDeviceToDevice, dst->stream));
-    TMPC_HIP_CHECK(dst, hipMemcpyAsync(dst->st_lamh, src->st_lamh, n * N * nh * 8, hipMemcpyDeviceToDevice, dst->stream));
-    TMPC_HIP_CHECK(dst, hipMemcpyAsync(dst->st_stopped, src->st_stopped, n * 4, hipMemcpyDeviceToDevice, dst->stream));
-    TMPC_HIP_CHECK(dst, hipMemcpyAsync(dst->st_has, src->st_has, n * 4, hipMemcpyDeviceToDevice, dst->stream));
+    if (!dst->st.allocated() && !dst->st.allocate(a, dst->B_max, dst->stream)) { dst->err = "tmpc_copy_state: allocation failed"; return TMPC_ERR_HIP; }
+    const size_t n = (size_t)(dst->B_max < src->B_max ? dst->B_max : src->B_max);
+    for (int i = 0; i < tmpc::SolverState::COUNT; i++)
+        TMPC_HIP_CHECK(dst, hipMemcpyAsync(dst->st.a[i], src->st.a[i], tmpc::SolverState::bytes(a, n, i), hipMemcpyDeviceToDevice, dst->stream));
     TMPC_HIP_CHECK(dst, hipStreamSynchronize(dst->stream));
     return TMPC_OK;
 }
@@ -1048,10 +1047,10 @@ int tmpc_clear_slot(tmpc_handle *h, int32_t slot)
 {
     if (!h || slot < 0 || slot >= h->B_max) { if (h) h->err = "tmpc_clear_slot: slot out of range"; return TMPC_ERR_INVALID; }
     if (h->throughput_mode) { h->err = "tmpc_clear_slot: the lane kernels keep their state per launch, not per slot"; return TMPC_ERR_INVALID; }
-    if (!h->st_has) return TMPC_OK;                                 // nothing stored yet: every slot is fresh
+    if (!h->st.allocated()) return TMPC_OK;                                 // nothing stored yet: every slot is fresh
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    TMPC_HIP_CHECK(h, hipMemsetAsync(h->st_has + slot, 0, 4, h->stream));
-    TMPC_HIP_CHECK(h, hipMemsetAsync(h->st_stopped + slot, 0, 4, h->stream));
+    TMPC_HIP_CHECK(h, hipMemsetAsync(h->st.get<int>(tmpc::SolverState::HAS) + slot, 0, 4, h->stream));
+    TMPC_HIP_CHECK(h, hipMemsetAsync(h->st.get<int>(tmpc::SolverState::STOPPED) + slot, 0, 4, h->stream));
     return TMPC_OK;
 }
 
@@ -1132,36 +1131,21 @@ int tmpc_get(tmpc_handle *h, double *xtraj, double *utraj, double *pobj, int32_t
 {
     if (!h || h->B <= 0) return TMPC_ERR_INVALID;
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    const size_t N = h->d.N, B = h->B;
-    if (h->slab_out) {                                              // one D2H copy of the output slab into its pinned mirror, then host copies of what was asked for
-        if (h->slab_out_bytes <= (256u << 10)) {
-            TMPC_HIP_CHECK(h, hipMemcpyAsync(h->pin_out, h->slab_out, h->slab_out_bytes, hipMemcpyDeviceToHost, h->stream));
-        } else {                                                    // B_max well above a tick's size: the first B entries of every array the caller asked for
-            auto dc = [&](const void *want, const void *dev, size_t n) {
-                return want ? hipMemcpyAsync(h->pin_out + ((const char *)dev - h->slab_out), dev, n, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-            };
-            TMPC_HIP_CHECK(h, dc(xtraj, h->xtraj, B * (N + 1) * tmpc::ext_nx(h->d) * 8)); TMPC_HIP_CHECK(h, dc(utraj, h->utraj, B * N * tmpc::NU * 8));
-            TMPC_HIP_CHECK(h, dc(pobj, h->pobj, B * 8)); TMPC_HIP_CHECK(h, dc(res_eq, h->res_eq, B * 8));
-            TMPC_HIP_CHECK(h, dc(exit_code, h->exit_code, B * 4)); TMPC_HIP_CHECK(h, dc(qp_status, h->qp_status, B * 4));
-            TMPC_HIP_CHECK(h, dc(sqp_iter, h->sqp_iter, B * 4)); TMPC_HIP_CHECK(h, dc(qp_iter_total, h->qp_iter, B * 4));
+    void *const dst[tmpc::OUT_COUNT] = {xtraj, utraj, pobj, res_eq, exit_code, qp_status, sqp_iter, qp_iter_total};      // in the table's order (tmpc::IoOut)
+    const tmpc::IoRegion *r = h->io.out;
+    const size_t B = h->B;
+    if (h->pin_out && h->io.out_total <= (256u << 10)) {            // one D2H copy of the whole output block into its pinned mirror
+        TMPC_HIP_CHECK(h, hipMemcpyAsync(h->pin_out, h->dev_out, h->io.out_total, hipMemcpyDeviceToHost, h->stream));
+    } else {                                                        // the first B entries of every array the caller asked for: into the mirror (B_max well above a
+        for (int i = 0; i < tmpc::OUT_COUNT; i++) {                 // tick's size), or -- a handle without mirrors -- into the caller's array
+            if (!dst[i]) continue;
+            void *to = h->pin_out ? (void *)(h->pin_out + r[i].offset) : dst[i];
+            TMPC_HIP_CHECK(h, hipMemcpyAsync(to, h->dev_out + r[i].offset, r[i].bytes(B), hipMemcpyDeviceToHost, h->stream));
         }
-        TMPC_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-        auto hc = [&](void *dst, const void *dev, size_t n) { if (dst) std::memcpy(dst, h->pin_out + ((const char *)dev - h->slab_out), n); };
-        hc(xtraj, h->xtraj, B * (N + 1) * tmpc::ext_nx(h->d) * 8); hc(utraj, h->utraj, B * N * tmpc::NU * 8);
-        hc(pobj, h->pobj, B * 8); hc(res_eq, h->res_eq, B * 8);
-        hc(exit_code, h->exit_code, B * 4); hc(qp_status, h->qp_status, B * 4); hc(sqp_iter, h->sqp_iter, B * 4); hc(qp_iter_total, h->qp_iter, B * 4);
-        return TMPC_OK;
     }
-    auto cp = [&](void *dst, const void *src, size_t n) { return dst ? hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, h->stream) : hipSuccess; };
-    TMPC_HIP_CHECK(h, cp(xtraj, h->xtraj, B * (N + 1) * tmpc::ext_nx(h->d) * 8));
-    TMPC_HIP_CHECK(h, cp(utraj, h->utraj, B * N * tmpc::NU * 8));
-    TMPC_HIP_CHECK(h, cp(pobj, h->pobj, B * 8));
-    TMPC_HIP_CHECK(h, cp(res_eq, h->res_eq, B * 8));
-    TMPC_HIP_CHECK(h, cp(exit_code, h->exit_code, B * 4));
-    TMPC_HIP_CHECK(h, cp(qp_status, h->qp_status, B * 4));
-    TMPC_HIP_CHECK(h, cp(sqp_iter, h->sqp_iter, B * 4));
-    TMPC_HIP_CHECK(h, cp(qp_iter_total, h->qp_iter, B * 4));
     TMPC_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    if (h->pin_out)                                                 // host copies of what was asked for
+        for (int i = 0; i < tmpc::OUT_COUNT; i++) if (dst[i]) std::memcpy(dst[i], h->pin_out + r[i].offset, r[i].bytes(B));
     return TMPC_OK;
 }
 
@@ -1246,7 +1230,7 @@ int tmpc_gather_best(tmpc_handle *h, const void *d_best, int32_t n_sets, int32_t
     }
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
     hipLaunchKernelGGL(tmpc::tmpc_gather_best_kernel, dim3(n_sets), dim3(64), 0, h->stream, (const int *)d_best, set_size, index_offset,
-                       (h->d.N + 1) * tmpc::ext_nx(h->d), h->d.N * tmpc::NU, h->xtraj, h->utraj, (double *)d_xtraj, (double *)d_utraj);
+                       (int)h->io.out[tmpc::OUT_XTRAJ].doubles(), (int)h->io.out[tmpc::OUT_UTRAJ].doubles(), h->xtraj, h->utraj, (double *)d_xtraj, (double *)d_utraj);
     TMPC_HIP_CHECK(h, hipGetLastError());
     return TMPC_OK;
 }
@@ -1548,11 +1532,7 @@ int tmpc_scenario_halfspaces(tmpc_handle *h, const void *d_samples, int32_t n_pt
     }
     const size_t units = (size_t)h->B * h->d.N;
     const size_t need = units * n_rows + 1 + units + (size_t)h->B;  // rows' samples, the first pass's overflow list (count, units), empty-polygon stages per trajectory
-    if (need > h->scn_cap) {
-        if (h->scn_sample) { TMPC_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->scn_sample); h->scn_sample = nullptr; h->scn_cap = 0; }
-        TMPC_HIP_CHECK(h, hipMalloc(&h->scn_sample, need * sizeof(int)));
-        h->scn_cap = need;
-    }
+    if (int rc = grow_scratch(h, &h->scn_sample, &h->scn_cap, need)) return rc;
     h->scn_rows = n_rows; h->scn_B = h->B;
     // scenarios discarded for this batch (tmpc_scenario_discard after the batch was set) are left out of the polygons
     const bool use_discard = h->scn_discard && h->scn_discard_B == h->B && h->scn_discard_S > 0 && n_pts % h->scn_discard_S == 0;
@@ -1604,11 +1584,7 @@ int tmpc_scenario_discard(tmpc_handle *h, const void *d_samples, int32_t n_pts, 
     }
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
     const size_t need = (size_t)h->B_max * n_scenarios;
-    if (need > h->scn_discard_cap) {
-        if (h->scn_discard) { TMPC_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->scn_discard); h->scn_discard = nullptr; h->scn_discard_cap = 0; }
-        TMPC_HIP_CHECK(h, hipMalloc(&h->scn_discard, need));
-        h->scn_discard_cap = need;
-    }
+    if (int rc = grow_scratch(h, &h->scn_discard, &h->scn_discard_cap, need)) return rc;
     const size_t lds = (size_t)n_scenarios * sizeof(double);
     if (lds > 48 * 1024)
         TMPC_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(tmpc::tmpc_scenario_discard_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1756,8 +1732,8 @@ int tmpc_debug_get_x0(tmpc_handle *h, double *x0, double *xinit)
     if (!h || h->B <= 0 || !h->x0) return TMPC_ERR_INVALID;
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
     TMPC_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-    if (x0) TMPC_HIP_CHECK(h, hipMemcpy(x0, h->x0, (size_t)h->B * (h->d.N + 1) * tmpc::ext_nv(h->d) * 8, hipMemcpyDeviceToHost));
-    if (xinit) TMPC_HIP_CHECK(h, hipMemcpy(xinit, h->xinit, (size_t)h->B * tmpc::ext_nx(h->d) * 8, hipMemcpyDeviceToHost));
+    if (x0) TMPC_HIP_CHECK(h, hipMemcpy(x0, h->x0, h->io.in[tmpc::IN_X0].bytes(h->B), hipMemcpyDeviceToHost));
+    if (xinit) TMPC_HIP_CHECK(h, hipMemcpy(xinit, h->xinit, h->io.in[tmpc::IN_XINIT].bytes(h->B), hipMemcpyDeviceToHost));
     return TMPC_OK;
 }
 
@@ -1805,7 +1781,7 @@ int tmpc_debug_get_params(tmpc_handle *h, double *params)
     if (!h || h->B <= 0 || !params || !h->params) return TMPC_ERR_INVALID;
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
     TMPC_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-    TMPC_HIP_CHECK(h, hipMemcpy(params, h->params, (size_t)h->B * h->d.N * h->d.npar * 8, hipMemcpyDeviceToHost));
+    TMPC_HIP_CHECK(h, hipMemcpy(params, h->params, h->io.in[tmpc::IN_PARAMS].bytes(h->B), hipMemcpyDeviceToHost));
     return TMPC_OK;
 }
 
