@@ -39,20 +39,6 @@ class TmpcDims(C.Structure):
         return self.n_lin + self.M + self.n_slk
 
 
-EXPORTS = ["tmpc_default_dims", "tmpc_default_dims_ex", "tmpc_create", "tmpc_destroy", "tmpc_last_error", "tmpc_set_batch",
-           "tmpc_set_batch_device", "tmpc_solve", "tmpc_set_latency_mode", "tmpc_synchronize", "tmpc_get", "tmpc_select_best",
-           "tmpc_result_device_ptrs", "tmpc_time_solve", "tmpc_debug_eval_stage", "tmpc_pack_records",
-           "tmpc_select_best_records", "tmpc_enable_timing", "tmpc_get_timings", "tmpc_debug_profile",
-           "tmpc_linearize_topology", "tmpc_scenario_halfspaces", "tmpc_scenario_support", "tmpc_warmstart", "tmpc_init_with_guidance",
-           "tmpc_debug_get_x0", "tmpc_debug_get_params", "tmpc_set_throughput_mode", "tmpc_solve_iterations",
-           "tmpc_reset_multipliers", "tmpc_get_stream", "tmpc_kernel_info", "tmpc_set_slots", "tmpc_set_param_sharing", "tmpc_copy_state", "tmpc_scenario_empty_stages", "tmpc_sample_scenarios",
-           "tmpc_scenario_discard", "tmpc_scenario_discarded", "tmpc_linearize_topology_ex", "tmpc_clear_slot", "tmpc_gather_best",
-           "tmpc_create_v2", "tmpc_set_param_sharing_ex", "tmpc_latency_mode_capacity", "tmpc_has_lane_kernels", "tmpc_debug_lds_passes", "tmpc_debug_poison_lds", "tmpc_has_lab_switches",
-           "tmpc_road_halfspaces", "tmpc_prepare_obstacles", "tmpc_set_obstacle_parameters", "tmpc_track_path", "tmpc_set_path_parameters", "tmpc_fit_path",
-           "tmpc_costmap_points", "tmpc_decomp_halfspaces", "tmpc_set_halfspace_rows", "tmpc_path_velocity_window", "tmpc_scatter_parameters",
-           "tmpc_sample_guidance", "tmpc_guidance_plan", "tmpc_guidance_decide"]
-
-
 class TmpcObstacleOptions(C.Structure):
     """tmpc_obstacle_options (include/tmpc_hip.h)."""
     _fields_ = [("size", C.c_uint32), ("probabilistic", C.c_int32), ("propagate_passes", C.c_int32), ("reserved", C.c_int32),
@@ -81,10 +67,96 @@ class TmpcError(RuntimeError):
     pass
 
 
+_int, _i32, _u32, _u64, _f64, _vp = C.c_int, C.c_int32, C.c_uint32, C.c_uint64, C.c_double, C.c_void_p
+_dims_p, _obstacle_p, _path_p, _guidance_p = C.POINTER(TmpcDims), C.POINTER(TmpcObstacleOptions), C.POINTER(TmpcPathOptions), C.POINTER(TmpcGuidanceOptions)
+
+# The Python side of include/tmpc_hip.h, in the header's order: name -> (restype, argtypes).  Everything else follows from this table: EXPORTS,
+# what load_library() sets on the library, how BatchedSolver._call() converts its arguments.  tests/test_binding_signatures.py holds it against
+# the header's prototypes.  _vp: the handle and every data pointer (an integer address, a ctypes object or None = NULL).
+_SIGNATURES = {
+    "tmpc_default_dims": (None, [_dims_p, _i32, _i32, _i32, _i32]),
+    "tmpc_default_dims_ex": (None, [_dims_p] + [_i32] * 6),
+    "tmpc_create": (_int, [C.POINTER(_vp), _dims_p, _i32, _i32]),
+    "tmpc_create_v2": (_int, [C.POINTER(_vp), _dims_p, _u32, _i32, _i32]),
+    "tmpc_destroy": (None, [_vp]),
+    "tmpc_last_error": (C.c_char_p, [_vp]),
+    "tmpc_set_batch": (_int, [_vp, _i32, _vp, _vp, _vp]),
+    "tmpc_set_batch_device": (_int, [_vp, _i32, _vp, _vp, _vp]),
+    "tmpc_solve": (_int, [_vp]),
+    "tmpc_synchronize": (_int, [_vp]),
+    "tmpc_solve_iterations": (_int, [_vp, _i32, _i32]),
+    "tmpc_set_slots": (_int, [_vp, _vp]),
+    "tmpc_set_param_sharing": (_int, [_vp, _vp]),
+    "tmpc_set_param_sharing_ex": (_int, [_vp, _vp, _i32]),
+    "tmpc_copy_state": (_int, [_vp, _vp]),
+    "tmpc_clear_slot": (_int, [_vp, _i32]),
+    "tmpc_reset_multipliers": (_int, [_vp]),
+    "tmpc_set_latency_mode": (_int, [_vp, _i32]),
+    "tmpc_latency_mode_capacity": (_int, [_vp, _i32]),
+    "tmpc_set_throughput_mode": (_int, [_vp, _i32]),
+    "tmpc_has_lane_kernels": (_int, []),
+    "tmpc_get": (_int, [_vp] + [_vp] * 8),
+    "tmpc_select_best": (_int, [_vp, _i32, _i32, _vp, _vp, C.POINTER(_i32)]),
+    "tmpc_result_device_ptrs": (_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "tmpc_get_stream": (_int, [_vp, C.POINTER(_vp)]),
+    "tmpc_kernel_info": (_int, [_vp, C.c_char_p, _i32]),
+    "tmpc_pack_records": (_int, [_vp, _vp, _vp, _vp]),
+    "tmpc_select_best_records": (_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "tmpc_gather_best": (_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "tmpc_enable_timing": (_int, [_vp, _i32]),
+    "tmpc_get_timings": (_int, [_vp, _vp, _i32, C.POINTER(_i32)]),
+    "tmpc_time_solve": (_int, [_vp, _i32, _vp]),
+    "tmpc_linearize_topology": (_int, [_vp, _vp, _vp, _vp, _f64, _vp]),
+    "tmpc_linearize_topology_ex": (_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _f64, _vp]),
+    "tmpc_road_halfspaces": (_int, [_vp, _vp, _i32, _vp, _f64, _f64, _vp, _i32, _i32]),
+    "tmpc_prepare_obstacles": (_int, [_vp, _i32, _i32, _i32] + [_vp] * 6 + [_obstacle_p] + [_vp] * 5),
+    "tmpc_set_obstacle_parameters": (_int, [_vp] + [_vp] * 6 + [_f64] * 5),
+    "tmpc_track_path": (_int, [_vp, _i32, _i32] + [_vp] * 5 + [_i32, _path_p] + [_vp] * 5),
+    "tmpc_set_path_parameters": (_int, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    "tmpc_path_velocity_window": (_int, [_vp, _i32, _i32, _i32] + [_vp] * 7 + [_f64, _vp, _vp]),
+    "tmpc_scatter_parameters": (_int, [_vp, C.POINTER(_i32), _i32, _vp, _i32, _vp, _i32]),
+    "tmpc_fit_path": (_int, [_vp, _i32, _i32, _i32] + [_vp] * 13),
+    "tmpc_costmap_points": (_int, [_vp, _i32, _i32, _i32, _vp, _vp, _f64, _i32, _vp, _vp, _vp]),
+    "tmpc_decomp_halfspaces": (_int, [_vp, _vp, _i32, _i32] + [_vp] * 7 + [_i32, _f64, _i32, _vp, _vp, _vp]),
+    "tmpc_set_halfspace_rows": (_int, [_vp, _vp, _i32, _i32, _vp, _i32, _f64]),
+    "tmpc_scenario_halfspaces": (_int, [_vp, _vp, _i32, _i32, _vp, _vp, _f64, _f64]),
+    "tmpc_scenario_support": (_int, [_vp, _i32, _f64, _vp, _vp]),
+    "tmpc_sample_scenarios": (_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _vp]),
+    "tmpc_scenario_discard": (_int, [_vp, _vp, _i32, _i32, _i32, _vp, _f64]),
+    "tmpc_scenario_discarded": (_int, [_vp, _vp]),
+    "tmpc_scenario_empty_stages": (_int, [_vp, _vp]),
+    "tmpc_warmstart": (_int, [_vp, _vp, _vp, _vp, _f64]),
+    "tmpc_init_with_guidance": (_int, [_vp, _vp, _vp, _vp]),
+    "tmpc_sample_guidance": (_int, [_vp, _i32, _i32] + [_vp] * 5),
+    "tmpc_guidance_plan": (_int, [_vp, _i32, _guidance_p] + [_vp] * 12),
+    "tmpc_guidance_decide": (_int, [_vp, _i32, _guidance_p] + [_vp] * 6 + [_f64, _f64, _i32] + [_vp] * 5),
+    "tmpc_debug_get_x0": (_int, [_vp, _vp, _vp]),
+    "tmpc_debug_get_params": (_int, [_vp, _vp]),
+    "tmpc_debug_profile": (_int, [_vp, _vp, _i32]),
+    "tmpc_debug_lds_passes": (_int, [_i32] * 5),
+    "tmpc_debug_poison_lds": (_int, [_vp]),
+    "tmpc_has_lab_switches": (_int, []),
+    "tmpc_debug_eval_stage": (_int, [_vp, _i32] + [_vp] * 13),
+}
+EXPORTS = list(_SIGNATURES)
+
+_CTYPES = (C._SimpleCData, C.Array, C.Structure, C._Pointer, type(C.byref(_int())))
+
+
+def _pointer(v):
+    """None or 0: NULL; an integer address as it is; a ctypes object (c_void_p, byref(..), an array) untouched."""
+    return v if v is None or isinstance(v, _CTYPES) else int(v) or None
+
+
+# per function, how BatchedSolver._call() converts each argument behind the handle: counts through int() and reals through float() (a numpy
+# scalar is a TypeError to ctypes otherwise), everything else is a pointer
+_CONVERT = {name: tuple(int if t in (_int, _i32, _u32, _u64) else float if t is _f64 else _pointer for t in argtypes[1:])
+            for name, (_, argtypes) in _SIGNATURES.items()}
+
+
 def has_lane_kernels(lib_path=None):
     """Does this build of the library carry the optional lane-per-trajectory kernels (tmpc_set_throughput_mode)?"""
-    lib = load_library(lib_path)
-    return hasattr(lib, "tmpc_has_lane_kernels") and lib.tmpc_has_lane_kernels() == 1
+    return load_library(lib_path).tmpc_has_lane_kernels() == 1
 
 
 _libs = {}
@@ -107,86 +179,10 @@ def load_library(path=None):
         raise TmpcError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(path)
-    lib.tmpc_last_error.restype = C.c_char_p
-    lib.tmpc_last_error.argtypes = [C.c_void_p]
-    lib.tmpc_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(TmpcDims), C.c_int32, C.c_int32]
-    lib.tmpc_destroy.argtypes = [C.c_void_p]
-    lib.tmpc_default_dims.argtypes = [C.POINTER(TmpcDims), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    lib.tmpc_default_dims_ex.argtypes = [C.POINTER(TmpcDims)] + [C.c_int32] * 6
-    vp = C.c_void_p
-    lib.tmpc_set_batch.argtypes = [vp, C.c_int32, vp, vp, vp]
-    lib.tmpc_set_batch_device.argtypes = [vp, C.c_int32, vp, vp, vp]
-    lib.tmpc_solve.argtypes = [vp]
-    lib.tmpc_set_latency_mode.argtypes = [vp, C.c_int32]
-    lib.tmpc_set_throughput_mode.argtypes = [vp, C.c_int32]
-    lib.tmpc_solve_iterations.argtypes = [vp, C.c_int32, C.c_int32]
-    lib.tmpc_reset_multipliers.argtypes = [vp]
-    lib.tmpc_get_stream.argtypes = [vp, C.POINTER(vp)]
-    if hasattr(lib, "tmpc_kernel_info"):        # (absent from reference builds of earlier rounds used in A/B runs)
-        lib.tmpc_kernel_info.argtypes = [vp, C.c_char_p, C.c_int32]
-    if hasattr(lib, "tmpc_set_slots"):        # (absent from reference builds of earlier rounds used in A/B runs)
-        lib.tmpc_set_slots.argtypes = [vp, vp]
-    if hasattr(lib, "tmpc_set_param_sharing"):
-        lib.tmpc_set_param_sharing.argtypes = [vp, vp]
-    if hasattr(lib, "tmpc_set_param_sharing_ex"):
-        lib.tmpc_set_param_sharing_ex.argtypes = [vp, vp, C.c_int32]
-        lib.tmpc_latency_mode_capacity.argtypes = [vp, C.c_int32]
-        lib.tmpc_create_v2.argtypes = [C.POINTER(C.c_void_p), C.POINTER(TmpcDims), C.c_uint32, C.c_int32, C.c_int32]
-    if hasattr(lib, "tmpc_scenario_empty_stages"):        # (absent from reference builds of earlier rounds used in A/B runs)
-        lib.tmpc_scenario_empty_stages.argtypes = [vp, vp]
-    if hasattr(lib, "tmpc_sample_scenarios"):        # (absent from reference builds of earlier rounds used in A/B runs)
-        lib.tmpc_sample_scenarios.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp]
-    if hasattr(lib, "tmpc_scenario_discard"):        # (absent from reference builds of earlier rounds used in A/B runs)
-        lib.tmpc_scenario_discard.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_double]
-    if hasattr(lib, "tmpc_linearize_topology_ex"):
-        lib.tmpc_linearize_topology_ex.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_double, vp]
-    if hasattr(lib, "tmpc_road_halfspaces"):
-        lib.tmpc_road_halfspaces.argtypes = [vp, vp, C.c_int32, vp, C.c_double, C.c_double, vp, C.c_int32, C.c_int32]
-    if hasattr(lib, "tmpc_prepare_obstacles"):
-        lib.tmpc_prepare_obstacles.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 6 + [C.POINTER(TmpcObstacleOptions)] + [vp] * 5
-        lib.tmpc_set_obstacle_parameters.argtypes = [vp] + [vp] * 6 + [C.c_double] * 5
-    if hasattr(lib, "tmpc_track_path"):
-        lib.tmpc_track_path.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 5 + [C.c_int32, C.POINTER(TmpcPathOptions)] + [vp] * 5
-        lib.tmpc_set_path_parameters.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
-    if hasattr(lib, "tmpc_fit_path"):
-        lib.tmpc_fit_path.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 13
-    if hasattr(lib, "tmpc_path_velocity_window"):
-        lib.tmpc_path_velocity_window.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 7 + [C.c_double, vp, vp]
-        lib.tmpc_scatter_parameters.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32, vp, C.c_int32]
-    if hasattr(lib, "tmpc_guidance_plan"):
-        lib.tmpc_sample_guidance.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 5
-        lib.tmpc_guidance_plan.argtypes = [vp, C.c_int32, C.POINTER(TmpcGuidanceOptions)] + [vp] * 12
-        lib.tmpc_guidance_decide.argtypes = [vp, C.c_int32, C.POINTER(TmpcGuidanceOptions)] + [vp] * 6 + [C.c_double, C.c_double, C.c_int32] + [vp] * 5
-    if hasattr(lib, "tmpc_decomp_halfspaces"):
-        lib.tmpc_costmap_points.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, vp, vp, vp]
-        lib.tmpc_decomp_halfspaces.argtypes = [vp, vp, C.c_int32, C.c_int32] + [vp] * 7 + [C.c_int32, C.c_double, C.c_int32, vp, vp, vp]
-        lib.tmpc_set_halfspace_rows.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_double]
-    if hasattr(lib, "tmpc_scenario_discarded"):        # (absent from reference builds of earlier rounds used in A/B runs)
-        lib.tmpc_scenario_discarded.argtypes = [vp, vp]
-    if hasattr(lib, "tmpc_copy_state"):        # (absent from reference builds of earlier rounds used in A/B runs)
-        lib.tmpc_copy_state.argtypes = [vp, vp]
-    if hasattr(lib, "tmpc_gather_best"):
-        lib.tmpc_gather_best.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
-    if hasattr(lib, "tmpc_clear_slot"):
-        lib.tmpc_clear_slot.argtypes = [vp, C.c_int32]
-    lib.tmpc_synchronize.argtypes = [vp]
-    lib.tmpc_get.argtypes = [vp] + [vp] * 8
-    lib.tmpc_select_best.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(C.c_int32)]
-    lib.tmpc_result_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-    lib.tmpc_time_solve.argtypes = [vp, C.c_int32, vp]
-    lib.tmpc_debug_eval_stage.argtypes = [vp, C.c_int32] + [vp] * 13
-    lib.tmpc_pack_records.argtypes = [vp, vp, vp, vp]
-    lib.tmpc_select_best_records.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp]
-    lib.tmpc_enable_timing.argtypes = [vp, C.c_int32]
-    lib.tmpc_get_timings.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32)]
-    lib.tmpc_debug_profile.argtypes = [vp, vp, C.c_int32]
-    lib.tmpc_linearize_topology.argtypes = [vp, vp, vp, vp, C.c_double, vp]
-    lib.tmpc_warmstart.argtypes = [vp, vp, vp, vp, C.c_double]
-    lib.tmpc_init_with_guidance.argtypes = [vp, vp, vp, vp]
-    lib.tmpc_debug_get_x0.argtypes = [vp, vp, vp]
-    lib.tmpc_scenario_halfspaces.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_double]
-    lib.tmpc_scenario_support.argtypes = [vp, C.c_int32, C.c_double, vp, vp]
-    lib.tmpc_debug_get_params.argtypes = [vp, vp]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name, None)           # an older build of the same C-ABI (A/B runs) may lack an entry: skipped here, refused when called
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     _libs[path] = lib
     return lib
 
@@ -260,6 +256,18 @@ class BatchedSolver:
         if rc != 0:
             raise TmpcError(f"{what} failed ({rc}): {self.lib.tmpc_last_error(self._h).decode()}")
 
+    def _invoke(self, name, *args):
+        """The one path into the library: entry `name` of _SIGNATURES on this handle, every argument converted as its type in the table
+        says; returns the entry's code as it is (for the entries whose non-negative return is a value)."""
+        fn = getattr(self.lib, name, None)
+        if fn is None:
+            raise TmpcError(f"this library has no {name} (a missing kernel is an error, there is no host fallback)")
+        return fn(self._h, *[convert(a) for convert, a in zip(_CONVERT[name], args)])
+
+    def _call(self, name, *args):
+        """_invoke, and a non-zero code raises with the library's message."""
+        self._check(self._invoke(name, *args), name)
+
     # --- inputs -----------------------------------------------------------------------------------
     def set_batch(self, xinit, x0, params):
         """Host arrays: xinit [B][nx], x0 [B][N+1][nvar], params [B][N][npar] (reference layouts; nx, nvar = 5, 7 or,
@@ -272,26 +280,25 @@ class BatchedSolver:
             raise ValueError(f"set_batch: expected xinit [{B}][{self.dims.nx}], x0 [{B}][{self.N + 1}][{self.dims.nvar}], "
                              f"params [{B}][{self.N}][{self.npar}]; got {xinit.shape}, {x0.shape}, {params.shape}")
         self._keep = (xinit, x0, params)
-        self._check(self.lib.tmpc_set_batch(self._h, B, _p(xinit), _p(x0), _p(params)), "tmpc_set_batch")
+        self._call("tmpc_set_batch", B, _p(xinit), _p(x0), _p(params))
         self.B = B
 
     def set_batch_device(self, B, d_xinit, d_x0, d_params):
         """Raw device pointers (ints), inputs already resident in HBM."""
-        self._check(self.lib.tmpc_set_batch_device(self._h, int(B), C.c_void_p(d_xinit), C.c_void_p(d_x0),
-                                                   C.c_void_p(d_params)), "tmpc_set_batch_device")
+        self._call("tmpc_set_batch_device", B, d_xinit, d_x0, d_params)
         self.B = int(B)
 
     # --- solve ------------------------------------------------------------------------------------
     def solve(self, sync=True):
-        self._check(self.lib.tmpc_solve(self._h), "tmpc_solve")
+        self._call("tmpc_solve")
         if sync:
-            self._check(self.lib.tmpc_synchronize(self._h), "tmpc_synchronize")
+            self._call("tmpc_synchronize")
 
     def set_latency_mode(self, on=True):
         """Kernel variant for small control ticks: True / 1 = two waves per trajectory, 2 = the Newton systems solved parallel in time
         (csrc/tmpc_scan.hpp), 3 = four waves per trajectory (round 6: the parallel-in-time solve with its wide phases, the stage evaluation and the
         row passes on 256 lanes; N <= 20), False / 0 = the throughput kernels; returns False if the shape has no such variant."""
-        rc = self.lib.tmpc_set_latency_mode(self._h, int(on))
+        rc = self._invoke("tmpc_set_latency_mode", on)
         if rc < 0:
             self._check(rc, "tmpc_set_latency_mode")
         return rc == 0
@@ -303,18 +310,18 @@ class BatchedSolver:
         initializeOneIteration / solveOneIteration / completeOneIteration protocol and multipliers carried across ticks."""
         flags = (self.KEEP_ITERATE if keep_iterate else 0) | (self.KEEP_MULTIPLIERS if keep_multipliers else 0) | (self.COMPLETE if complete else 0) \
             | (self.NEW_SOLVE if new_solve else 0)      # new_solve: first call of a new Solver::solve(): loop exits of the previous solve do not carry over
-        self._check(self.lib.tmpc_solve_iterations(self._h, int(n_iter), flags), "tmpc_solve_iterations")
+        self._call("tmpc_solve_iterations", n_iter, flags)
         if sync:
             self.synchronize()
 
     def set_slots(self, slots):
         """State slot of every entry of the current batch (tmpc_set_slots); None: entry b uses slot b."""
         if slots is None:
-            self._check(self.lib.tmpc_set_slots(self._h, None), "tmpc_set_slots")
+            self._call("tmpc_set_slots", None)
             return
         a = np.ascontiguousarray(slots, np.int32)
         assert a.size == self.B
-        self._check(self.lib.tmpc_set_slots(self._h, a.ctypes.data_as(C.c_void_p)), "tmpc_set_slots")
+        self._call("tmpc_set_slots", _p(a))
 
     def set_param_sharing(self, base_of, copies_not_maintained=False):
         """Hint (tmpc_set_param_sharing): entry b's parameter rows equal entry base_of[b]'s except for its own topology / scenario
@@ -322,55 +329,55 @@ class BatchedSolver:
         copies_not_maintained (tmpc_set_param_sharing_ex, TMPC_SHARE_COPIES_NOT_MAINTAINED): the caller writes a set's shared rows into the base
         entry only; every path that would read the other entries' copies then fails instead of falling back."""
         if base_of is None:
-            self._check(self.lib.tmpc_set_param_sharing(self._h, None), "tmpc_set_param_sharing")
+            self._call("tmpc_set_param_sharing", None)
             return
         a = np.ascontiguousarray(base_of, np.int32)
         assert a.size == self.B
-        self._check(self.lib.tmpc_set_param_sharing_ex(self._h, a.ctypes.data_as(C.c_void_p), 1 if copies_not_maintained else 0), "tmpc_set_param_sharing_ex")
+        self._call("tmpc_set_param_sharing_ex", _p(a), 1 if copies_not_maintained else 0)
 
     def latency_mode_capacity(self, mode):
         """Trajectories one launch of kernel variant `mode` holds resident on this device (tmpc_latency_mode_capacity); 0: no such variant."""
-        rc = self.lib.tmpc_latency_mode_capacity(self._h, int(mode))
+        rc = self._invoke("tmpc_latency_mode_capacity", mode)
         if rc < 0:
             self._check(rc, "tmpc_latency_mode_capacity")
         return rc
 
     def clear_slot(self, slot):
         """Forget one slot's persistent state (tmpc_clear_slot): the slot's next solve_iterations starts like a fresh capsule."""
-        self._check(self.lib.tmpc_clear_slot(self._h, int(slot)), "tmpc_clear_slot")
+        self._call("tmpc_clear_slot", slot)
 
     def copy_state_from(self, other):
-        self._check(self.lib.tmpc_copy_state(self._h, other._h), "tmpc_copy_state")
+        self._call("tmpc_copy_state", other._h)
 
     def debug_poison_lds(self):
         """Test aid: fill every CU's LDS with NaN bit patterns (tmpc_debug_poison_lds): a kernel that reads a word it never wrote shows."""
-        self._check(self.lib.tmpc_debug_poison_lds(self._h), "tmpc_debug_poison_lds")
+        self._call("tmpc_debug_poison_lds")
 
     def kernel_info(self):
         """Which solve kernel the handle dispatches and how it is launched (text)."""
         buf = C.create_string_buffer(2048)
-        n = self.lib.tmpc_kernel_info(self._h, buf, 2048)
+        n = self._invoke("tmpc_kernel_info", buf, 2048)
         return buf.value.decode() if n >= 0 else ""
 
     def stream_ptr(self):
         """hipStream_t of the handle (as an integer), e.g. for torch.cuda.ExternalStream."""
         st = C.c_void_p()
-        self._check(self.lib.tmpc_get_stream(self._h, C.byref(st)), "tmpc_get_stream")
+        self._call("tmpc_get_stream", C.byref(st))
         return st.value or 0
 
     def reset_multipliers(self):
-        self._check(self.lib.tmpc_reset_multipliers(self._h), "tmpc_reset_multipliers")
+        self._call("tmpc_reset_multipliers")
 
     def set_throughput_mode(self, on=True):
         """Lane-per-trajectory kernels for large batches (allocates the HBM workspace for B_max trajectories on first use)."""
-        self._check(self.lib.tmpc_set_throughput_mode(self._h, int(bool(on))), "tmpc_set_throughput_mode")
+        self._call("tmpc_set_throughput_mode", bool(on))
 
     def synchronize(self):
-        self._check(self.lib.tmpc_synchronize(self._h), "tmpc_synchronize")
+        self._call("tmpc_synchronize")
 
     def time_solve(self, reps):
         ms = np.zeros(reps, np.float32)
-        self._check(self.lib.tmpc_time_solve(self._h, int(reps), _p(ms)), "tmpc_time_solve")
+        self._call("tmpc_time_solve", reps, _p(ms))
         return ms
 
     # --- outputs ----------------------------------------------------------------------------------
@@ -379,9 +386,7 @@ class BatchedSolver:
         out = dict(xtraj=np.zeros((B, N + 1, self.dims.nx)), utraj=np.zeros((B, N, NU)), pobj=np.zeros(B),
                    exit_code=np.zeros(B, np.int32), qp_status=np.zeros(B, np.int32), sqp_iter=np.zeros(B, np.int32),
                    res_eq=np.zeros(B), qp_iter_total=np.zeros(B, np.int32))
-        self._check(self.lib.tmpc_get(self._h, _p(out["xtraj"]), _p(out["utraj"]), _p(out["pobj"]), _p(out["exit_code"]),
-                                      _p(out["qp_status"]), _p(out["sqp_iter"]), _p(out["res_eq"]),
-                                      _p(out["qp_iter_total"])), "tmpc_get")
+        self._call("tmpc_get", *[_p(out[k]) for k in ("xtraj", "utraj", "pobj", "exit_code", "qp_status", "sqp_iter", "res_eq", "qp_iter_total")])
         return out
 
     def select_best(self, first=0, count=None, weight=None, disabled=None):
@@ -389,48 +394,38 @@ class BatchedSolver:
         w = None if weight is None else np.ascontiguousarray(weight, np.float64)
         dis = None if disabled is None else np.ascontiguousarray(disabled, np.uint8)
         best = C.c_int32(-2)
-        self._check(self.lib.tmpc_select_best(self._h, int(first), int(count), _p(w), _p(dis), C.byref(best)),
-                    "tmpc_select_best")
+        self._call("tmpc_select_best", first, count, _p(w), _p(dis), C.byref(best))
         return best.value
 
     def enable_timing(self, max_records):
-        self._check(self.lib.tmpc_enable_timing(self._h, int(max_records)), "tmpc_enable_timing")
+        self._call("tmpc_enable_timing", max_records)
 
     def get_timings(self, capacity=4096):
         ms = np.zeros(capacity, np.float32); n = C.c_int32(0)
-        self._check(self.lib.tmpc_get_timings(self._h, _p(ms), capacity, C.byref(n)), "tmpc_get_timings")
+        self._call("tmpc_get_timings", _p(ms), capacity, C.byref(n))
         return ms[:n.value].copy()
 
     def pack_records(self, d_records, d_guidance_id=None, d_weight=None):
         """d_*: raw device pointers (ints). Packs {f64 objective, i32 exit_code, i32 guidance_id} per trajectory."""
-        self._check(self.lib.tmpc_pack_records(self._h, C.c_void_p(d_records),
-                                               C.c_void_p(d_guidance_id) if d_guidance_id else None,
-                                               C.c_void_p(d_weight) if d_weight else None), "tmpc_pack_records")
+        self._call("tmpc_pack_records", d_records, d_guidance_id, d_weight)
 
     def select_best_records(self, d_records, n_ranks, n_scenes, per_rank, d_best):
-        self._check(self.lib.tmpc_select_best_records(self._h, C.c_void_p(d_records), int(n_ranks), int(n_scenes),
-                                                      int(per_rank), C.c_void_p(d_best)), "tmpc_select_best_records")
+        self._call("tmpc_select_best_records", d_records, n_ranks, n_scenes, per_rank, d_best)
 
     def gather_best(self, d_best, n_sets, set_size, d_xtraj, d_utraj, index_offset=0):
         """The winners' trajectories of every set in one compact device buffer (tmpc_gather_best; raw device pointers)."""
-        self._check(self.lib.tmpc_gather_best(self._h, C.c_void_p(d_best), int(n_sets), int(set_size), int(index_offset),
-                                              C.c_void_p(d_xtraj), C.c_void_p(d_utraj)), "tmpc_gather_best")
+        self._call("tmpc_gather_best", d_best, n_sets, set_size, index_offset, d_xtraj, d_utraj)
 
     def linearize_topology(self, d_obstacle_pos, d_scene_of, d_state_x, robot_radius, d_is_original=None):
         """Device LinearizedConstraints::update + setParameters (raw device pointers); modifies the batch params in place."""
-        self._check(self.lib.tmpc_linearize_topology(self._h, C.c_void_p(d_obstacle_pos), C.c_void_p(d_scene_of),
-                                                     C.c_void_p(d_state_x), float(robot_radius),
-                                                     C.c_void_p(d_is_original) if d_is_original else None),
-                    "tmpc_linearize_topology")
+        self._call("tmpc_linearize_topology", d_obstacle_pos, d_scene_of, d_state_x, robot_radius, d_is_original)
 
     def linearize_topology_ex(self, d_obstacle_pos, n_obstacles, d_scene_of, d_state_x, robot_radius, d_obstacle_radius=None,
                               d_static_halfspaces=None, n_static=0, d_is_original=None):
         """The whole of LinearizedConstraints::update / setParameters on device (tmpc_linearize_topology_ex): fewer obstacles than rows,
         static halfspace rows (`add_halfspaces`), per-obstacle radii (the `_use_guidance == false` branch)."""
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_linearize_topology_ex(self._h, vp(d_obstacle_pos), int(n_obstacles), vp(d_obstacle_radius),
-                                                        vp(d_static_halfspaces), int(n_static), C.c_void_p(d_scene_of), C.c_void_p(d_state_x),
-                                                        float(robot_radius), vp(d_is_original)), "tmpc_linearize_topology_ex")
+        self._call("tmpc_linearize_topology_ex", d_obstacle_pos, n_obstacles, d_obstacle_radius, d_static_halfspaces, n_static, d_scene_of, d_state_x,
+                   robot_radius, d_is_original)
 
     def road_halfspaces(self, d_main_of, n_scenes, offset_first, offset_second, d_static_halfspaces, n_static, first_row=0,
                         d_bound_segments=None):
@@ -438,12 +433,7 @@ class BatchedSolver:
         d_static_halfspaces [n_scenes][N][n_static][3] -- the buffer linearize_topology_ex reads -- from the warm start and path window of batch
         entry d_main_of[scene].  d_bound_segments None: centreline mode, offsets = modules.road_offsets(width, radius, two_way); else
         [n_scenes][2][S][8] left / right bound cubics and offsets = (radius, radius).  Stream-ordered, no synchronisation."""
-        if not hasattr(self.lib, "tmpc_road_halfspaces"):
-            raise TmpcError("this library has no tmpc_road_halfspaces (a missing kernel is an error, there is no host fallback)")
-        self._check(self.lib.tmpc_road_halfspaces(self._h, C.c_void_p(d_main_of) if d_main_of else None, int(n_scenes),
-                                                  C.c_void_p(d_bound_segments) if d_bound_segments else None, float(offset_first),
-                                                  float(offset_second), C.c_void_p(d_static_halfspaces) if d_static_halfspaces else None,
-                                                  int(n_static), int(first_row)), "tmpc_road_halfspaces")
+        self._call("tmpc_road_halfspaces", d_main_of, n_scenes, d_bound_segments, offset_first, offset_second, d_static_halfspaces, n_static, first_row)
 
     def prepare_obstacles(self, n_scenes, n_slots, max_obstacles, d_count, d_state, d_raw_pos, d_raw_radius, d_obstacle_pos, d_obstacle_shape,
                           d_obstacle_radius, d_obstacle_gaussian, d_selected, d_raw_vel=None, d_raw_pred=None, probabilistic=False, noise=0.3,
@@ -453,29 +443,19 @@ class BatchedSolver:
         obstacles -- distance filter, closest-M selection or dummies, uncertainty passes -- in d_obstacle_pos [n_scenes][M][N][2] (what
         linearize_topology_ex reads), d_obstacle_shape [..][N][3], d_obstacle_radius, d_obstacle_gaussian (u8), d_selected (i32) [n_scenes][M].
         Equal bit for bit to modules.prepare_obstacles.  Needs no batch.  Stream-ordered, no synchronisation."""
-        if not hasattr(self.lib, "tmpc_prepare_obstacles"):
-            raise TmpcError("this library has no tmpc_prepare_obstacles (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
         opt = TmpcObstacleOptions(C.sizeof(TmpcObstacleOptions), int(probabilistic), int(propagate_passes), 0, float(noise),
                                   float(max_obstacle_distance))
-        self._check(self.lib.tmpc_prepare_obstacles(self._h, int(n_scenes), int(n_slots), int(max_obstacles), vp(d_count), vp(d_state), vp(d_raw_pos),
-                                                    vp(d_raw_radius), vp(d_raw_vel), vp(d_raw_pred), C.byref(opt), vp(d_obstacle_pos),
-                                                    vp(d_obstacle_shape), vp(d_obstacle_radius), vp(d_obstacle_gaussian), vp(d_selected)),
-                    "tmpc_prepare_obstacles")
+        self._call("tmpc_prepare_obstacles", n_scenes, n_slots, max_obstacles, d_count, d_state, d_raw_pos, d_raw_radius, d_raw_vel, d_raw_pred,
+                   C.byref(opt), d_obstacle_pos, d_obstacle_shape, d_obstacle_radius, d_obstacle_gaussian, d_selected)
 
     def set_obstacle_parameters(self, d_obstacle_pos, d_obstacle_shape, d_obstacle_radius, d_obstacle_gaussian, d_scene_of, d_state, robot_radius,
                                 disc_offset=0.0, risk=0.05, obstacle_radius=0.0):
         """The collision columns of the current batch's parameter rows, in place, from prepare_obstacles' buffers (tmpc_set_obstacle_parameters;
         raw device pointers): EllipsoidConstraints (row_model 0) or GaussianConstraints (row_model 1; obstacle_radius = the configured radius of
         its r column), ego_disc_radius and ego_disc_0_offset.  chi = -log(risk) / 0.5 is evaluated here, on the host.  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_set_obstacle_parameters"):
-            raise TmpcError("this library has no tmpc_set_obstacle_parameters (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
         chi = float(-np.log(risk) / 0.5)                              # ExponentialQuantile(0.5, 1 - risk), ellipsoid_constraints.cpp:80
-        self._check(self.lib.tmpc_set_obstacle_parameters(self._h, vp(d_obstacle_pos), vp(d_obstacle_shape), vp(d_obstacle_radius),
-                                                          vp(d_obstacle_gaussian), vp(d_scene_of), vp(d_state), float(robot_radius),
-                                                          float(disc_offset), float(risk), chi, float(obstacle_radius)),
-                    "tmpc_set_obstacle_parameters")
+        self._call("tmpc_set_obstacle_parameters", d_obstacle_pos, d_obstacle_shape, d_obstacle_radius, d_obstacle_gaussian, d_scene_of, d_state,
+                   robot_radius, disc_offset, risk, chi, obstacle_radius)
 
     def track_path(self, n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_pos, pos_stride, d_segment, d_closest_s, d_window,
                    d_bounds=None, d_bound_window=None, d_reached=None, search_range=2, window_segments=0):
@@ -486,24 +466,16 @@ class BatchedSolver:
         [n_scenes][2][n_seg_max][8] the bound cubics of the window into d_bound_window [n_scenes][2][S][8] (what road_halfspaces takes), and
         the objective-reached flag into d_reached (u8).  Equal bit for bit to modules.track_path.  Needs no batch.  Stream-ordered.
         window_segments: 0 = the handle's S; a generated solver has none and needs the stack's contouring/num_segments here (1 .. 64)."""
-        if not hasattr(self.lib, "tmpc_track_path"):
-            raise TmpcError("this library has no tmpc_track_path (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
         opt = TmpcPathOptions(C.sizeof(TmpcPathOptions), int(search_range), int(window_segments))
-        self._check(self.lib.tmpc_track_path(self._h, int(n_scenes), int(n_seg_max), vp(d_path), vp(d_path_count), vp(d_path_length), vp(d_bounds),
-                                             vp(d_pos), int(pos_stride), C.byref(opt), vp(d_segment), vp(d_closest_s), vp(d_window),
-                                             vp(d_bound_window), vp(d_reached)), "tmpc_track_path")
+        self._call("tmpc_track_path", n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_bounds, d_pos, pos_stride, C.byref(opt), d_segment,
+                   d_closest_s, d_window, d_bound_window, d_reached)
 
     def set_path_parameters(self, d_window, d_scene_of, n_scenes, d_closest_s=None, d_state=None):
         """The spline columns of the current batch's parameter rows, in place, from track_path's d_window (tmpc_set_path_parameters; raw
         device pointers); entries whose d_scene_of is outside [0, n_scenes) are left untouched.  With d_closest_s and d_state [B][nx]: the
         spline entry of each named entry's state becomes its scene's closest_s -- before warmstart(d_state) the solve starts from the fresh
         value, after it from the previous tick's, as in the reference (planner.cpp:81-96).  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_set_path_parameters"):
-            raise TmpcError("this library has no tmpc_set_path_parameters (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_set_path_parameters(self._h, vp(d_window), vp(d_scene_of), int(n_scenes), vp(d_closest_s), vp(d_state)),
-                    "tmpc_set_path_parameters")
+        self._call("tmpc_set_path_parameters", d_window, d_scene_of, n_scenes, d_closest_s, d_state)
 
     def path_velocity_window(self, n_scenes, n_seg_max, S, d_path, d_path_count, d_path_length, d_segment, d_closest_s, d_window, d_velocity=None,
                              d_has_velocity=None, reference_velocity=0.0, d_v_ref=None):
@@ -513,12 +485,8 @@ class BatchedSolver:
         without a profile (d_velocity None, d_has_velocity[scene] == 0 or count <= 0); with d_v_ref the profile's value at closest_s (or
         reference_velocity) into d_v_ref [n_scenes], what the guidance planner is given.  Equal bit for bit to modules.path_velocity_window
         and modules.path_velocity_at.  Needs no batch; also in a generated solver.  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_path_velocity_window"):
-            raise TmpcError("this library has no tmpc_path_velocity_window (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_path_velocity_window(self._h, int(n_scenes), int(n_seg_max), int(S), vp(d_velocity), vp(d_path), vp(d_path_count),
-                                                       vp(d_path_length), vp(d_segment), vp(d_closest_s), vp(d_has_velocity),
-                                                       float(reference_velocity), vp(d_window), vp(d_v_ref)), "tmpc_path_velocity_window")
+        self._call("tmpc_path_velocity_window", n_scenes, n_seg_max, S, d_velocity, d_path, d_path_count, d_path_length, d_segment, d_closest_s,
+                   d_has_velocity, reference_velocity, d_window, d_v_ref)
 
     def scatter_parameters(self, cols, d_values, d_scene_of, n_scenes, per_stage=False):
         """Caller-chosen columns of the current batch's parameter rows, in place (tmpc_scatter_parameters; cols a host sequence of at most 128
@@ -526,12 +494,8 @@ class BatchedSolver:
         [n_scenes][len(cols)] into every stage of every entry whose d_scene_of is inside [0, n_scenes), or with per_stage d_values
         [n_scenes][N][len(cols)], stage k from row k; nothing else.  The parameter writer of generated solvers.  Equal bit for bit to
         modules.scatter_parameters.  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_scatter_parameters"):
-            raise TmpcError("this library has no tmpc_scatter_parameters (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
         arr = None if cols is None else (C.c_int32 * max(len(cols), 1))(*[int(c) for c in cols])
-        self._check(self.lib.tmpc_scatter_parameters(self._h, arr, 0 if cols is None else len(cols), vp(d_values), 1 if per_stage else 0,
-                                                     vp(d_scene_of), int(n_scenes)), "tmpc_scatter_parameters")
+        self._call("tmpc_scatter_parameters", arr, 0 if cols is None else len(cols), d_values, bool(per_stage), d_scene_of, n_scenes)
 
     def fit_path(self, n_scenes, n_pts_max, n_seg_max, d_xy, d_count, d_path, d_path_count, d_path_length, d_s=None, d_left_xy=None,
                  d_right_xy=None, d_v=None, d_bounds=None, d_velocity=None, d_road_width=None, d_status=None):
@@ -541,23 +505,15 @@ class BatchedSolver:
         curves on the centreline's knots into d_bounds [n_scenes][2][n_seg_max][8] and the road width into d_road_width; with d_v the
         velocity profile into d_velocity [n_scenes][n_seg_max][4]; d_status (u8): 0 fitted, 1 invalid (count 0, nothing else written).
         Equal bit for bit to modules.fit_path.  Needs no batch.  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_fit_path"):
-            raise TmpcError("this library has no tmpc_fit_path (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_fit_path(self._h, int(n_scenes), int(n_pts_max), int(n_seg_max), vp(d_xy), vp(d_count), vp(d_s), vp(d_left_xy),
-                                           vp(d_right_xy), vp(d_v), vp(d_path), vp(d_path_count), vp(d_path_length), vp(d_bounds), vp(d_velocity),
-                                           vp(d_road_width), vp(d_status)), "tmpc_fit_path")
+        self._call("tmpc_fit_path", n_scenes, n_pts_max, n_seg_max, d_xy, d_count, d_s, d_left_xy, d_right_xy, d_v, d_path, d_path_count, d_path_length,
+                   d_bounds, d_velocity, d_road_width, d_status)
 
     def costmap_points(self, n_scenes, size_x, size_y, d_cost, d_origin, resolution, n_pts_max, d_points, d_count, d_overflow=None):
         """Occupied costmap cells to points on device (tmpc_costmap_points; raw device pointers; getOccupiedGridCells,
         decomp_constraints.cpp:122-148): d_cost u8 [n_scenes][size_y][size_x], d_origin [n_scenes][2] -> the centres of the cells whose cost is
         not 0, mx outer and my inner, the first n_pts_max of them into d_points [n_scenes][n_pts_max][2], their number into d_count (i32),
         d_overflow (u8) 1 iff there were more.  Equal bit for bit to modules.costmap_points.  Needs no batch.  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_costmap_points"):
-            raise TmpcError("this library has no tmpc_costmap_points (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_costmap_points(self._h, int(n_scenes), int(size_x), int(size_y), vp(d_cost), vp(d_origin), float(resolution),
-                                                 int(n_pts_max), vp(d_points), vp(d_count), vp(d_overflow)), "tmpc_costmap_points")
+        self._call("tmpc_costmap_points", n_scenes, size_x, size_y, d_cost, d_origin, resolution, n_pts_max, d_points, d_count, d_overflow)
 
     def decomp_halfspaces(self, d_main_of, n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_s0, d_state_x, d_points, d_count, n_pts_max,
                           decomp_range, n_rows, d_rows, d_row_count, d_status):
@@ -566,61 +522,46 @@ class BatchedSolver:
         d_main_of[scene], one convex polygon per segment among the scene's d_count points of d_points [n_scenes][n_pts_max][2], its rows into
         d_rows [n_scenes][N][n_rows][3] (dummies (1, 0, d_state_x + 100) included), d_row_count (i32) and d_status (u8: 0 complete, 1
         truncated, 2 degenerate) [n_scenes][N].  Equal bit for bit to modules.decomp_halfspaces.  Stream-ordered, no synchronisation."""
-        if not hasattr(self.lib, "tmpc_decomp_halfspaces"):
-            raise TmpcError("this library has no tmpc_decomp_halfspaces (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_decomp_halfspaces(self._h, vp(d_main_of), int(n_scenes), int(n_seg_max), vp(d_path), vp(d_path_count),
-                                                    vp(d_path_length), vp(d_s0), vp(d_state_x), vp(d_points), vp(d_count), int(n_pts_max),
-                                                    float(decomp_range), int(n_rows), vp(d_rows), vp(d_row_count), vp(d_status)),
-                    "tmpc_decomp_halfspaces")
+        self._call("tmpc_decomp_halfspaces", d_main_of, n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_s0, d_state_x, d_points, d_count,
+                   n_pts_max, decomp_range, n_rows, d_rows, d_row_count, d_status)
 
     def set_halfspace_rows(self, d_rows, n_rows, d_scene_of, n_scenes, first_row=0, disc_offset=0.0):
         """DecompConstraints::setParameters on device (tmpc_set_halfspace_rows; raw device pointers): d_rows [n_scenes][N][n_rows][3] of every
         stage into the slack rows first_row .. first_row + n_rows - 1 of every entry of the current batch whose d_scene_of is inside
         [0, n_scenes), and ego_disc_0_offset; nothing else.  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_set_halfspace_rows"):
-            raise TmpcError("this library has no tmpc_set_halfspace_rows (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_set_halfspace_rows(self._h, vp(d_rows), int(n_rows), int(first_row), vp(d_scene_of), int(n_scenes),
-                                                     float(disc_offset)), "tmpc_set_halfspace_rows")
+        self._call("tmpc_set_halfspace_rows", d_rows, n_rows, first_row, d_scene_of, n_scenes, disc_offset)
 
     def scenario_halfspaces(self, d_samples, n_pts, n_rows, d_scene_of, d_state_x, radius, disc_offset=0.0):
         """Device scenario -> halfspace reduction of SH-MPC (raw device pointers; samples [n_scenes][N][n_pts][2]);
         modifies the batch params in place."""
-        self._check(self.lib.tmpc_scenario_halfspaces(self._h, C.c_void_p(d_samples), int(n_pts), int(n_rows),
-                                                      C.c_void_p(d_scene_of), C.c_void_p(d_state_x), float(radius),
-                                                      float(disc_offset)), "tmpc_scenario_halfspaces")
+        self._call("tmpc_scenario_halfspaces", d_samples, n_pts, n_rows, d_scene_of, d_state_x, radius, disc_offset)
 
     def scenario_support(self, n_scenarios, tol=1e-6):
         """Support of every trajectory's solution (distinct scenarios with an active row; tmpc_scenario_support) after a solve on
         rows built by scenario_halfspaces.  Returns (support [B], active_rows [B]) as numpy int32."""
         import torch
         out = torch.empty((2, self.B), dtype=torch.int32, device=f"cuda:{self.device}")
-        self._check(self.lib.tmpc_scenario_support(self._h, int(n_scenarios), float(tol), C.c_void_p(out[0].data_ptr()),
-                                                   C.c_void_p(out[1].data_ptr())), "tmpc_scenario_support")
+        self._call("tmpc_scenario_support", n_scenarios, tol, out[0].data_ptr(), out[1].data_ptr())
         self.synchronize()
         o = out.cpu().numpy()
         return o[0], o[1]
 
     def scenario_support_async(self, n_scenarios, tol, d_support, d_active_rows):
         """tmpc_scenario_support on raw device pointers (int32 [B] each), stream-ordered on the handle's stream, no synchronisation."""
-        self._check(self.lib.tmpc_scenario_support(self._h, int(n_scenarios), float(tol), C.c_void_p(d_support), C.c_void_p(d_active_rows)),
-                    "tmpc_scenario_support")
+        self._call("tmpc_scenario_support", n_scenarios, tol, d_support, d_active_rows)
 
     def sample_scenarios(self, d_pred, d_prob, n_solvers, n_obstacles, n_modes, n_scenarios, seed, d_samples):
         """Device scenario sampler (tmpc_sample_scenarios): raw device pointers; d_samples [n_solvers][N][n_obstacles * n_scenarios][2]."""
-        self._check(self.lib.tmpc_sample_scenarios(self._h, C.c_void_p(d_pred), C.c_void_p(d_prob), int(n_solvers), int(n_obstacles), int(n_modes),
-                                                   int(n_scenarios), C.c_uint64(int(seed)), C.c_void_p(d_samples)), "tmpc_sample_scenarios")
+        self._call("tmpc_sample_scenarios", d_pred, d_prob, n_solvers, n_obstacles, n_modes, n_scenarios, seed, d_samples)
 
     def scenario_discard(self, d_samples, n_pts, n_scenarios, n_discard, d_scene_of, radius):
         """Scenario removal for the current batch (tmpc_scenario_discard); the next scenario_halfspaces leaves the discarded scenarios out."""
-        self._check(self.lib.tmpc_scenario_discard(self._h, C.c_void_p(d_samples), int(n_pts), int(n_scenarios), int(n_discard),
-                                                   C.c_void_p(d_scene_of), float(radius)), "tmpc_scenario_discard")
+        self._call("tmpc_scenario_discard", d_samples, n_pts, n_scenarios, n_discard, d_scene_of, radius)
 
     def scenario_discarded(self, n_scenarios):
         import torch
         out = torch.zeros((self.B, n_scenarios), dtype=torch.uint8, device=f"cuda:{self.device}")
-        self._check(self.lib.tmpc_scenario_discarded(self._h, C.c_void_p(out.data_ptr())), "tmpc_scenario_discarded")
+        self._call("tmpc_scenario_discarded", out.data_ptr())
         self.synchronize()
         return out.cpu().numpy().astype(bool)
 
@@ -629,29 +570,23 @@ class BatchedSolver:
         such a stage keeps the closest halfspaces and the trajectory is not eligible)."""
         import torch
         out = torch.zeros(self.B, dtype=torch.int32, device=f"cuda:{self.device}")
-        self._check(self.lib.tmpc_scenario_empty_stages(self._h, C.c_void_p(out.data_ptr())), "tmpc_scenario_empty_stages")
+        self._call("tmpc_scenario_empty_stages", out.data_ptr())
         self.synchronize()
         return out.cpu().numpy()
 
     def warmstart(self, d_state, d_mode=None, d_src=None, deceleration=3.0):
         """Device warm start of the next tick from the solution held by the handle (raw device pointers)."""
-        self._check(self.lib.tmpc_warmstart(self._h, C.c_void_p(d_state), C.c_void_p(d_mode) if d_mode else None,
-                                            C.c_void_p(d_src) if d_src else None, float(deceleration)), "tmpc_warmstart")
+        self._call("tmpc_warmstart", d_state, d_mode, d_src, deceleration)
 
     def init_with_guidance(self, d_gpos, d_gvel, d_enabled=None):
-        self._check(self.lib.tmpc_init_with_guidance(self._h, C.c_void_p(d_gpos), C.c_void_p(d_gvel),
-                                                     C.c_void_p(d_enabled) if d_enabled else None), "tmpc_init_with_guidance")
+        self._call("tmpc_init_with_guidance", d_gpos, d_gvel, d_enabled)
 
     def sample_guidance(self, n_traj, n_nodes_max, d_nodes, d_node_count, d_gpos, d_gvel, d_status):
         """Guidance nodes to the samples init_with_guidance reads (tmpc_sample_guidance; raw device pointers): per trajectory
         the natural cubic splines x(t), y(t) through d_nodes [n_traj][n_nodes_max][3] = (t, x, y) (d_node_count of them, at most 64), sampled
         at t = k dt, k = 0 .. N, into d_gpos / d_gvel [n_traj][N + 1][2]; d_status 1 and zero rows for an invalid node list.  Equal bit for
         bit to modules.sample_guidance.  Needs no batch.  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_sample_guidance"):
-            raise TmpcError("this library has no tmpc_sample_guidance (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_sample_guidance(self._h, int(n_traj), int(n_nodes_max), vp(d_nodes), vp(d_node_count), vp(d_gpos), vp(d_gvel),
-                                                  vp(d_status)), "tmpc_sample_guidance")
+        self._call("tmpc_sample_guidance", n_traj, n_nodes_max, d_nodes, d_node_count, d_gpos, d_gvel, d_status)
 
     def guidance_plan(self, n_scenes, options, d_traj_count, d_topology_class, d_planner_ids, d_selection, d_mode, d_src, d_init_enabled,
                       d_rows_dummy, d_disabled, d_guidance_id, d_weight, d_previously_selected=None):
@@ -659,13 +594,8 @@ class BatchedSolver:
         the trajectory counts, the classes and the cross-tick state d_planner_ids [n_scenes][P] / d_selection [n_scenes][3] to d_mode / d_src
         (warmstart), d_init_enabled (init_with_guidance), d_rows_dummy (linearize_topology_ex's d_is_original), d_disabled, d_guidance_id and
         d_weight (guidance_decide), entry b = scene P + planner.  Equal to modules.guidance_plan.  Needs no batch.  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_guidance_plan"):
-            raise TmpcError("this library has no tmpc_guidance_plan (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_guidance_plan(self._h, int(n_scenes), C.byref(options) if options is not None else None, vp(d_traj_count),
-                                                vp(d_topology_class), vp(d_previously_selected), vp(d_planner_ids), vp(d_selection), vp(d_mode),
-                                                vp(d_src), vp(d_init_enabled), vp(d_rows_dummy), vp(d_disabled), vp(d_guidance_id), vp(d_weight)),
-                    "tmpc_guidance_plan")
+        self._call("tmpc_guidance_plan", n_scenes, None if options is None else C.byref(options), d_traj_count, d_topology_class,
+                   d_previously_selected, d_planner_ids, d_selection, d_mode, d_src, d_init_enabled, d_rows_dummy, d_disabled, d_guidance_id, d_weight)
 
     def guidance_decide(self, n_scenes, options, d_pobj, d_exit_code, d_disabled, d_guidance_id, d_weight, d_state, d_best, d_exit, d_cmd,
                         d_planner_ids, d_selection, deceleration=3.0, control_dt=0.05, enable_output=True):
@@ -673,27 +603,22 @@ class BatchedSolver:
         d_best (as gather_best reads it), the exit code into d_exit, the command (v of node 1, w of node 0) of the winner or the braking
         command into d_cmd [n_scenes][2], and the cross-tick state d_planner_ids / d_selection for the next guidance_plan.  d_pobj /
         d_exit_code: result_device_ptrs(), or arrays of the caller's.  Equal bit for bit to modules.guidance_decide.  Stream-ordered."""
-        if not hasattr(self.lib, "tmpc_guidance_decide"):
-            raise TmpcError("this library has no tmpc_guidance_decide (a missing kernel is an error, there is no host fallback)")
-        vp = lambda p_: C.c_void_p(p_) if p_ else None
-        self._check(self.lib.tmpc_guidance_decide(self._h, int(n_scenes), C.byref(options) if options is not None else None, vp(d_pobj),
-                                                  vp(d_exit_code), vp(d_disabled), vp(d_guidance_id), vp(d_weight), vp(d_state), float(deceleration),
-                                                  float(control_dt), 1 if enable_output else 0, vp(d_best), vp(d_exit), vp(d_cmd), vp(d_planner_ids),
-                                                  vp(d_selection)), "tmpc_guidance_decide")
+        self._call("tmpc_guidance_decide", n_scenes, None if options is None else C.byref(options), d_pobj, d_exit_code, d_disabled, d_guidance_id,
+                   d_weight, d_state, deceleration, control_dt, bool(enable_output), d_best, d_exit, d_cmd, d_planner_ids, d_selection)
 
     def debug_get_x0(self):
         x0 = np.zeros((self.B, self.N + 1, self.dims.nvar)); xinit = np.zeros((self.B, self.dims.nx))
-        self._check(self.lib.tmpc_debug_get_x0(self._h, _p(x0), _p(xinit)), "tmpc_debug_get_x0")
+        self._call("tmpc_debug_get_x0", _p(x0), _p(xinit))
         return x0, xinit
 
     def debug_get_params(self):
         out = np.zeros((self.B, self.N, self.npar))
-        self._check(self.lib.tmpc_debug_get_params(self._h, _p(out)), "tmpc_debug_get_params")
+        self._call("tmpc_debug_get_params", _p(out))
         return out
 
     def result_device_ptrs(self):
         a, b = C.c_void_p(), C.c_void_p()
-        self._check(self.lib.tmpc_result_device_ptrs(self._h, C.byref(a), C.byref(b)), "tmpc_result_device_ptrs")
+        self._call("tmpc_result_device_ptrs", C.byref(a), C.byref(b))
         return a.value, b.value
 
     # --- debug ------------------------------------------------------------------------------------
@@ -702,7 +627,7 @@ class BatchedSolver:
 
     def debug_profile(self):
         cyc = np.zeros(10, np.int64)
-        self._check(self.lib.tmpc_debug_profile(self._h, _p(cyc), 10), "tmpc_debug_profile")
+        self._call("tmpc_debug_profile", _p(cyc), 10)
         return dict(zip(self.PHASES, cyc.tolist()))
 
     def debug_eval_stage(self, z, p, pi=None, lamh=None):
@@ -714,10 +639,7 @@ class BatchedSolver:
         o = dict(cost=np.zeros(n), cost_grad=np.zeros((n, NV)), cost_hess=np.zeros((n, NV, NV)), h=np.zeros((n, nh)),
                  h_jac=np.zeros((n, nh, NV)), x_next=np.zeros((n, NX)), x_jac=np.zeros((n, NX, NV)),
                  lag_hess=np.zeros((n, NV, NV)), mirror=np.zeros((n, NV, NV)))
-        self._check(self.lib.tmpc_debug_eval_stage(self._h, n, _p(z), _p(p), _p(pi), _p(lamh), _p(o["cost"]),
-                                                   _p(o["cost_grad"]), _p(o["cost_hess"]), _p(o["h"]), _p(o["h_jac"]),
-                                                   _p(o["x_next"]), _p(o["x_jac"]), _p(o["lag_hess"]), _p(o["mirror"])),
-                    "tmpc_debug_eval_stage")
+        self._call("tmpc_debug_eval_stage", n, _p(z), _p(p), _p(pi), _p(lamh), *[_p(a) for a in o.values()])
         return o
 
 

@@ -140,9 +140,7 @@ def test_lds_bank_conflict_model_of_the_layout_padding():
     import __graft_entry__ as g
     g.build()
     from mpc_planner_amd import solver
-    lib = C.CDLL(solver.LIB_PATH)
-    lib.tmpc_debug_lds_passes.argtypes = [C.c_int32] * 5
-    lib.tmpc_debug_lds_passes.restype = C.c_int
+    lib = solver.load_library()
 
     def model(N, n_pair, nh, threads, dstride):
         lps = (3 if 3 * N <= 64 else 2) if threads == 64 else (6 if N <= 21 else 4)
