@@ -81,7 +81,7 @@ __host__ __device__ inline int lds_doubles_compact(int N, int n_pair, int nh, in
 {
     const int dstride = 2 * n_pair + 3 * (nh - n_pair) + dpad;
     const int persistent = N * 8 + BA_NCONST + N * dstride + 3;
-    const int work = (N + 1) * NV + (N + 1) * NX + (N + 1) * compact_hstride(layout) + 2 * (N + 1) * NV + N * NX + (N + 1) * NV + (N + 1) * NX + (layout == 3 ? 0 : N * NU) + (nth > 64 ? 64 : 8);
+    const int work = (N + 1) * NV + (N + 1) * NX + (N + 1) * compact_hstride(layout) + 2 * (N + 1) * NV + N * NX + (N + 1) * NV + (N + 1) * NX + (layout == 3 ? 0 : N * NU) + (nth > 64 ? SCR_FULL : SCR_COMPACT);
     const int staging = 2 * N * nh;
     return persistent + (work > staging ? work : staging);
 }
@@ -104,7 +104,7 @@ __device__ __forceinline__ Lds carve_compact(double *s, double *ws, const Dims &
     double *w = s;
     L.v = take((N + 1) * NV); L.pq = take((N + 1) * NX); L.Hh = take((N + 1) * compact_hstride(layout));      // (hoff<CP>: tmpc_riccati.hpp)
     L.rg = take((N + 1) * NV); L.gh = take((N + 1) * NV); L.rb = take(N * NX); L.dv = take((N + 1) * NV);
-    L.dpi = take((N + 1) * NX); L.pr = L.dpi; L.y = layout == 3 ? nullptr : take(N * NU); L.scr = take(nth > 64 ? 64 : 8);
+    L.dpi = take((N + 1) * NX); L.pr = L.dpi; L.y = layout == 3 ? nullptr : take(N * NU); L.scr = take(nth > 64 ? SCR_FULL : SCR_COMPACT);
     s = w;
     L.beta = take(N * L.nh); L.lamh = take(N * L.nh);
     L.t = L.lam = L.invt = L.qt = L.rdiag = nullptr;

@@ -55,6 +55,16 @@ __device__ unsigned long long g_sweep_prof[SP_COUNT];
 //  ONE two-double load with a per-lane base where every lane loaded all three, two instructions; the arithmetic is the same)
 constexpr int FB_LXU = 0, FB_R0 = 10, FB_L10 = 11, FB_R1 = 12, FB_P = 13;
 
+// L.scr: SCR_COMPACT doubles in the compact one-wave carve, SCR_FULL in every other one (tmpc_fast.hpp, tmpc_kernels.hpp).  The factorisation's stores of lanes
+// outside a store group go to a dummy region of it that nobody reads: RDUM_EXTENT doubles from RDUM_BASE_COMPACT / RDUM_BASE_FULL -- the P row's five at
+// RDUM_P, the pair's two at RDUM_PAIR, the three pivots on top of the P row's at RDUM_PIV -- below the two-wave kernels' flag L.scr[SCR_FULL - 1] and above
+// what the other users of L.scr take (the block reductions' slots, the parallel-in-time factorisation's four doubles at 48).
+constexpr int SCR_COMPACT = 8, SCR_FULL = 64;
+constexpr int RDUM_P = 0, RDUM_PIV = 0, RDUM_PAIR = 5, RDUM_EXTENT = 7, RDUM_BASE_COMPACT = 0, RDUM_BASE_FULL = 56;
+static_assert(RDUM_P + NX <= RDUM_PAIR && RDUM_PIV + 3 <= RDUM_PAIR && RDUM_PAIR + NU <= RDUM_EXTENT, "dummy slots of the factorisation's store groups");
+static_assert(RDUM_BASE_COMPACT + RDUM_EXTENT <= SCR_COMPACT, "the dummy region must fit the compact carve's L.scr");
+static_assert(RDUM_BASE_FULL >= 52 && RDUM_BASE_FULL + RDUM_EXTENT <= SCR_FULL - 1, "the dummy region must stay between scr + 48..51 and the flag scr[63]");
+
 // Offset of stage k's block in Hh.  A stride of 28 doubles (56 dwords) puts the stages k, k + 8, k + 16 on the same LDS banks: the stage-parallel loops
 // (one lane per stage: the node's 28 stores of Hh <- W, the 15 + 15 loads of P in the vector solves' prologue / epilogue, the row passes' ds_add_f64)
 // ran every access in three passes; 29 is conflict-free and costs (N + 1) doubles of LDS.  The stride is a COMPILE-TIME fact of the instantiation --
@@ -237,13 +247,20 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
     // (backward), so the sweeps store separately.  profiles/round6_saturated_levers_ab.jsonl; results are bitwise the same either way.
     // End of stage k: the Lxu pairs of lanes 2..6 and the extra row's [y0 y1] are the registers f[0], f[1] of their lanes: ONE store for both (per-lane
     // address); lane 1 adds L10 and the two reciprocal pivots.  (p_k follows at the top of stage k - 1; p_0 is never read.)
+    // One straight-line store region per stage: the three store groups (the P row, the Lxu / y pair, lane 1's pivots) are stores of EVERY lane through a
+    // per-lane (offset, stride) pair -- evaluated once, here -- and the lanes outside a group write to a dummy slot of L.scr (stride 0) that nobody reads.
+    // Predicated, each group was a divergent side block of the stage loop (saveexec / branch pairs, a lane compare re-evaluated per stage).
+    const bool prl = rowl && li >= NU, vl = vec && wr;
+    const int dum = (int)(L.scr - L.Hh) + (CP ? RDUM_BASE_COMPACT : RDUM_BASE_FULL);
+    const int po = vl ? (int)(L.pr - L.Hh) : prl ? FB_P + i5 * (i5 + 1) / 2 : dum + RDUM_P, pst = vl ? NX : prl ? hstride<CP>() : 0;
+    const int qo = vl ? (CP == 3 ? NP28 : (int)(L.y - L.Hh)) : prl ? FB_LXU + 2 * i5 : dum + RDUM_PAIR;
+    const int qst = vl ? (CP == 3 ? hstride<CP>() : NU) : prl ? hstride<CP>() : 0;
+    const int vo = (rowl && li == 1) ? 0 : dum + RDUM_PIV - FB_R0, vst = (rowl && li == 1) ? hstride<CP>() : 0;
     auto store_pairs = [&](int k, double r0, double r1) {
-        double *Fb = L.Hh + hoff<CP>(k);
-        if ((rowl && li >= NU) || (vec && wr)) {
-            double *pp = vec ? ysl<CP>(L, k) : Fb + FB_LXU + 2 * i5;
-            pp[0] = f[0]; pp[1] = f[1];
-        }
-        if (rowl && li == 1) { Fb[FB_L10] = f[0]; Fb[FB_R0] = r0; Fb[FB_R1] = r1; }
+        double *pp = L.Hh + qo + mul24(k, qst);
+        pp[0] = f[0]; pp[1] = f[1];
+        double *Fv = L.Hh + vo + mul24(k, vst);
+        Fv[FB_L10] = f[0]; Fv[FB_R0] = r0; Fv[FB_R1] = r1;
     };
     auto stage = [&](const Opnd &o, Opnd &nx, int k) {
         // broadcast P (lower triangle of the 5x5 cost-to-go Hessian of stage k+1: rows 2..6 after the elimination) to every lane of the row
@@ -256,11 +273,21 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
         // P_{k+1} (own row of lanes 2..6) is kept for the vector solves -- and the extra row's p_{k+1} (square-root form: lx) leaves in the SAME five store
         // instructions (round 6: the LDS unit is the busy one at eight trajectories per CU, and an LDS instruction costs the same with one lane as with six):
         // lane 7 holds it in the same registers f[2..6] at the same point of the loop; only the address differs per lane
-        if ((rowl && li >= NU) || (vec && wr)) {
-            double *Ln = vec ? L.pr + (k + 1) * NX : L.Hh + hoff<CP>(k + 1) + FB_P + i5 * (i5 + 1) / 2;
-            const int lim = vec ? NX : i5;
-#pragma unroll
-            for (int l = 0; l < NX; l++) *(l <= lim ? Ln + l : L.scr + (CP ? 0 : 56) + l) = f[NU + l];   // (entries above the diagonal go to a dummy slot: a select on the address instead of five masked stores)
+        // The row is stored WITHOUT a select for the entries above the diagonal: every lane stores all five entries to Ln + l, in DESCENDING order of l.
+        // Entry l > i5 of lane i5 lands on packed offset i5 (i5 + 1) / 2 + l, which is entry e < l of a later row j > i5: its owner writes it in a LATER
+        // instruction of the same wave (LDS operations of a wave execute in order), so the junk is gone before anything reads the block.  The compiler
+        // sees one thread: it may not re-order these stores or merge two of them into one instruction (a two-address store would put lane 0's junk and
+        // lane 1's value on one address at once for the pairs (2, 1) and (1, 0)) -- hence the compiler barriers between them; only the pair (4, 3), whose
+        // junk lands on junk or on entries <= 2, may share an instruction.
+        {
+            double *Ln = L.Hh + po + mul24(k + 1, pst);
+            Ln[4] = f[NU + 4]; Ln[3] = f[NU + 3];
+            asm volatile("" ::: "memory");
+            Ln[2] = f[NU + 2];
+            asm volatile("" ::: "memory");
+            Ln[1] = f[NU + 1];
+            asm volatile("" ::: "memory");
+            Ln[0] = f[NU + 0];
         }
         if constexpr (SQ) {
             // G = Lp^T [B A] (5 x 7), Lp = Pm (the lower triangle holds Lxx of stage k + 1).  Own column densely from ba[]; all columns (row-uniform)
@@ -500,7 +527,7 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         // lane as with 64, and at eight trajectories per CU the launch follows the LDS instruction count of these loops).  The pivot data is used by
         // lanes 0, 1 only and the Lxu pair by lanes 2..6 only, both sit in the stage's factor block: one pair (a0, a1) = lane 0 (1/L00, L10), lane 1
         // (L10, 1/L11), lane 2 + i (Lxu_i0, Lxu_i1).  The arithmetic on every lane that counts is what it was (profiles/sweep_operand_merge_ab.jsonl).
-        struct Ops { double ghj, ba[NX], a0, a1, q; };
+        struct Ops { double ghj, ba[NX], a0, a1; };                        // (ghj: gh_j on lanes 0..6, q_i on lanes 8..12)
         const int fbo = li < NU ? FB_R0 + li : FB_LXU + 2 * i5;            // (lanes >= 7 follow lane 2: their values are not used)
         const BaLane bc = ba_column(N, ls);
         double bac[NX];
@@ -508,9 +535,14 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
 #pragma unroll
             for (int m = 2; m < NX; m++) bac[m] = L.tab[ba_off(N, 0, m, ls)];
         }
+        // q rides in the gh load: lanes 8..12 of the row, idle in the sweeps, read q_i = dpi[(k + 1) NX + i] where they used to re-read gh[k NV] --
+        // a per-lane (pointer, stride) pair --, and one row shift by six lanes hands it to lane 2 + i: the same value, one LDS load per stage fewer
+        const bool ql = li >= 8 && li < 8 + NX;
+        const double *ghq = ql ? L.dpi + NX + (li - 8) : L.gh + ls;
+        const int ghs = ql ? NX : NV;
         auto load_stage = [&](Ops &o, int k) {
             const double *Fb = L.Hh + hoff<CP>(k);
-            o.ghj = L.gh[uni(k * NV) + ls];
+            o.ghj = ghq[mul24(k, ghs)];
             if constexpr (CP) {
                 { const double *Tc = L.tab + bc.o0 + mul24(k, bc.st); o.ba[0] = Tc[0]; o.ba[1] = Tc[1]; }       // rows x, y of the own column: one load
 #pragma unroll
@@ -521,10 +553,9 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
                 for (int l = 0; l < NX; l++) o.ba[l] = BA[l * NV + ls];
             }
             o.a0 = Fb[fbo]; o.a1 = Fb[fbo + 1];
-            o.q = L.dpi[uni((k + 1) * NX) + i5];
         };
         auto stage = [&](const Ops &o, int k) {
-            const double Pb = p + o.q;                                     // (P_{k+1} rb_k + p_{k+1}), lane 2+i
+            const double Pb = p + dpp_shift_zero<0x106>(o.ghj);           // row_shl:6: lane 2 + i takes lane 8 + i's q_i
             double fj = o.ghj;
             static_for<0, NX>([&](auto l_) { constexpr int l = decltype(l_)::value; fj += o.ba[l] * bcast16<NU + l>(Pb); });
             const double y0 = bcast16<0>(fj * o.a0);                       // lane 0: fj 1/L00

@@ -1,4 +1,7 @@
 """Static view of a kernel's ISA (hipcc -S): innermost loops (backward branches) with their instruction mix.
+A loop's SIDE BLOCKS -- code placed outside the loop's line range that the loop branches out to and that branches (or falls) back into it, as the
+compiler lays out divergent regions (s_cbranch_exec* to a block behind the loop, s_branch back) -- are found and added: every loop is printed with the
+mix of its line range and -- innermost loops only --, where it has side blocks, with the mix including them (every side block counted once: an upper bound of one trip).
 Usage: python tools/isa_loops.py file.s kernel-name-prefix"""
 import re
 import sys
@@ -44,9 +47,58 @@ def mix(a, b):
         elif op.startswith("ds_"): c["lds"] += 1
         elif op.startswith(("global_", "scratch_", "buffer_", "flat_")): c["vmem"] += 1
     return c
+BRANCH = re.compile(r"^\s*(s_cbranch_\w+|s_branch)\s+(\.LBB\d+_\d+)")
+def side_blocks(a, b, limit=400):
+    """[(first, last)] line ranges outside [a, b] that the loop a..b branches to and that return into it."""
+    inside = lambda i: a <= i <= b
+    todo = [label_at[m.group(2)] for l in body[a:b + 1] for m in [BRANCH.match(l)] if m and m.group(2) in label_at and not inside(label_at[m.group(2)])]
+    seen, blocks = set(), []
+    while todo:
+        t = todo.pop()
+        if t in seen or any(x <= t <= y for x, y in blocks):
+            continue
+        seen.add(t)
+        pending, end = [], None
+        for j in range(t, min(t + limit, len(body))):
+            l = body[j]
+            if "s_endpgm" in l:
+                break
+            if j > t and j == a:                      # fell through into the loop's header
+                end = j - 1
+                break
+            m = BRANCH.match(l)
+            if not m or m.group(2) not in label_at:
+                continue
+            tgt = label_at[m.group(2)]
+            if m.group(1) == "s_branch":
+                if inside(tgt) or any(x <= tgt <= y for x, y in blocks) or tgt in seen:
+                    end = j
+                break
+            if inside(tgt):
+                end = j                                 # a conditional return; the block may go on
+            else:
+                pending.append(tgt)
+        if end is not None:
+            blocks.append((t, end))
+            todo += pending
+    merged = []                                        # (a block reached twice at different entry points is counted once)
+    for x, y in sorted(blocks):
+        if merged and x <= merged[-1][1]:
+            merged[-1] = (merged[-1][0], max(merged[-1][1], y))
+        else:
+            merged.append((x, y))
+    return merged
+def add(c, d):
+    return {k: c[k] + d[k] for k in c}
 # innermost: loops that contain no other loop
 inner = [lp for lp in loops if not any(o != lp and lp[0] <= o[0] and o[1] <= lp[1] for o in loops)]
 print(f"kernel lines {len(body)}, total {mix(0, len(body) - 1)}")
 for a, b in sorted(set(loops)):
     tag = "inner" if (a, b) in inner else "outer"
     print(f"{tag} loop lines {a}-{b} ({b - a}): {mix(a, b)}")
+    sb = side_blocks(a, b) if (a, b) in inner else []   # (an outer loop's "blocks" would be the enclosing loop's fall-through code, not divergent regions)
+    if sb:
+        tot = mix(a, b)
+        for x, y in sb:
+            tot = add(tot, mix(x, y))
+        print(f"    with side blocks {', '.join(f'{x}-{y}' for x, y in sb)}: {tot}")
