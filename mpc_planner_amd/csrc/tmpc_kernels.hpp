@@ -100,16 +100,18 @@ struct Lds {
 // runs over a row or column of [B A] keeps its operation order: results are bitwise those of the dense layout.
 // The 20 constants are ORDERED so that the sequential loops reach what a lane needs of a stage with the fewest LDS instructions
 // (each is one instruction whatever the lane count): dyn8 holds a column's (X, Y) entries next to each other, and the constants hold
-//   * rows psi, v, s of [B A] in dyn8 column order (a, w, psi, v) at stride 2 like rows x, y in dyn8 (forward sweep: BAR_*),
+//   * rows psi, v, s of [B E], E = A - I, in dyn8 column order (a, w, psi, v) at stride 2 like rows x, y in dyn8 (forward sweep: BAR_*; the sweep
+//     needs E, not A: the rows' 1 on the diagonal is stored as the 0.0 that A - I gave, so nothing is subtracted per stage -- 1 - 1 and x - 0 are exact),
 //   * a column's entries of rows x, y next to each other (columns x, y, s: BAP_*), like the (X, Y) pair of the other columns in dyn8,
 //   * a column's entries of rows psi, v, s next to each other (BAT_*),
 // all overlapping in 20 slots (no LDS was free for a longer table):
-//   index    0  1    2   3  4   5   6   7  8  9  10  11   12  13  14  15  16  17  18  19
-//   value    1  sdt  sh  0  dt  sh  dt  0  0  0  1   sdt  0   dt  dt  0   1   0   0   1
-constexpr int BAC_1 = 8, BAC_SDT = 9, BAC_SH = 10, BAC_0 = 11, BAC_DT = 12, BA_NCONST = 20;
-constexpr int BAR_S = 5, BAR_PSI = 12, BAR_V = 13;                                      // rows s, psi, v: (a, w, psi, v) at +0, +2, +4, +6
-constexpr int BAP_X = 16, BAP_Y = 15, BAP_S = 7;                                        // columns x, y, s: rows (x, y) at +0, +1
-constexpr int BAT_A = 3, BAT_W = 6, BAT_XY = 7, BAT_PSI = 16, BAT_V = 9, BAT_S = 17;    // columns: rows (psi, v, s) at +0, +1, +2
+//   index    0   1   2  3  4  5  6    7  8  9  10  11  12  13  14  15  16  17  18  19
+//   value    sh  dt  0  0  0  1  sdt  1  0  0  dt  dt  0   0   0   0   0   0   dt  sh
+// (the five values ba_off's codes name -- BAC_* -- sit in the first eight slots)
+constexpr int BAC_SH = 8, BAC_DT = 9, BAC_0 = 10, BAC_1 = 13, BAC_SDT = 14, BA_NCONST = 20;                 // (codes 8..15 reach indices 0..7)
+constexpr int BAR_S = 0, BAR_PSI = 8, BAR_V = 11;                                       // rows s, psi, v of [B E]: (a, w, psi, v) at +0, +2, +4, +6
+constexpr int BAP_X = 7, BAP_Y = 4, BAP_S = 2;                                          // columns x, y, s: rows (x, y) at +0, +1
+constexpr int BAT_A = 17, BAT_W = 1, BAT_XY = 2, BAT_PSI = 7, BAT_V = 4, BAT_S = 3;     // columns: rows (psi, v, s) at +0, +1, +2
 constexpr unsigned ba_pack(int a, int w, int x, int y, int p, int v, int s_)
 {
     return (unsigned)a | (unsigned)w << 4 | (unsigned)x << 8 | (unsigned)y << 12 | (unsigned)p << 16 | (unsigned)v << 20 | (unsigned)s_ << 24;
@@ -134,7 +136,7 @@ __device__ __forceinline__ void ba_tab_init(double *tab, const Dims &d, int tid)
 {
     if (tid < BA_NCONST) {
         const double dt = d.dt, sdt = d.sdt, sh = d.shdt2;
-        const double c[BA_NCONST] = {1.0, sdt, sh, 0.0, dt,   sh, dt, 0.0, 0.0, 0.0, 1.0, sdt,   0.0, dt, dt, 0.0, 1.0, 0.0, 0.0, 1.0};
+        const double c[BA_NCONST] = {sh, dt, 0.0, 0.0, 0.0, 1.0, sdt,   1.0, 0.0, 0.0, dt, dt, 0.0, 0.0, 0.0, 0.0, 0.0,   0.0, dt, sh};
         double val = 0.0;
 #pragma unroll
         for (int i = 0; i < BA_NCONST; i++) if (i == tid) val = c[i];

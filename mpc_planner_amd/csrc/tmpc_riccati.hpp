@@ -124,7 +124,7 @@ __device__ __forceinline__ BaLane ba_column(int N, int j)
     c.st = c.o0 < 8 ? 8 : 0;
     return c;
 }
-__device__ __forceinline__ BaLane ba_row4(int N, int i5)          // o0: base of (b_a, b_w, a_psi, a_v) of row i5, at stride 2
+__device__ __forceinline__ BaLane ba_row4(int N, int i5)          // o0: base of (b_a, b_w, e_psi, e_v) of row i5 of [B E], E = A - I, at stride 2
 {
     BaLane c;
     c.o0 = i5 < 2 ? i5 : N * 8 + (i5 == 2 ? BAR_PSI : i5 == 3 ? BAR_V : BAR_S); c.o1 = 0;
@@ -585,28 +585,36 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
     if (sweeper) {
         double dx = 0.0;
         // Operand merging as in the backward sweep, two loads per stage fewer:
-        //   yr        lane 0: y0, lane 1: y1 (s0 counts on lane 0 only, s1 on lane 1 only), lanes 2..6: rb_i -- a per-lane (pointer, stride) pair, like
-        //             the factorisation's hrow / bo[] / bst[]; layout 3 keeps y inside the stage's block: another base and stride, the same load
-        //   (a0, a1)  lane 0: (1/L00, L10), lane 1: (L10, 1/L11), lanes 2..6: the lane's own pair of Lxu.  (Before, the Lxu pair had ONE register set of its
-        //             own, re-loaded right after its last use early in the stage, because two sets pushed the compact kernels into scratch; with y0, y1,
-        //             rb_i in one register the merged pair fits the double-buffered set: 14 doubles where 9 + 9 + 2 were live.)
+        //   yr        lane 0: y0, lane 8: y1, lanes 2..6 and 10..14: rb_i -- a per-lane (pointer, stride) pair, like the factorisation's hrow / bo[] / bst[];
+        //             layout 3 keeps y inside the stage's block: another base and stride, the same load
+        //   (a0, a1)  lane 0: (1/L00, L10), lane 8: (1/L11, -), lanes 2 + i: (Lxu_i0, -), lanes 10 + i: (Lxu_i1, -); a1 counts on lane 0 only.  (Before, the
+        //             Lxu pair had ONE register set of its own, re-loaded right after its last use early in the stage, because two sets pushed the compact
+        //             kernels into scratch; with y0, y1, rb_i in one register the merged pair fits the double-buffered set: 14 doubles where 9 + 9 + 2 were live.)
+        // Two lane groups: the second column of Lxu has a SHADOW group on the row's upper half, which the forward sweep left idle.  Group A (lanes 0..6) is the
+        // stage vector as everywhere; in group B lane 8 plays the second input (y1, 1/L11) and lanes 10..14 run a copy of dx: the same rb_i, the same row of
+        // [B E], the same broadcast u0, u1, dpsi, dv -- taken from group A --, so their dx is bit for bit group A's.  With a0 = column 0 of Lxu on group A and
+        // column 1 on group B, ONE product a0 dx and ONE chain of five shifted adds reduce both columns at once (lane 0 sums lanes 2..6, lane 8 lanes 10..14,
+        // each in the order m = 0..4 the two chains of row broadcasts had): per stage 1 multiply + 5 adds where 2 + 10 were, the same bits
+        // (profiles/forward_sweep_half_row_ab.jsonl).  Only group A stores.
         struct Ops { double yr, a0, a1, a_psi, a_v, b_a, b_w; };
-        const double *yrb = li < NU ? ysl<CP>(L, 0) + li : L.rb + i5;
-        const int yrs = li < NU ? (CP == 3 ? hstride<CP>() : NU) : NX;
-        const int fbo = li < NU ? FB_R0 + li : FB_LXU + 2 * i5;
-        const double i_psi = li == ZPSI ? 1.0 : 0.0, i_v = li == ZV ? 1.0 : 0.0;
+        const bool shb = li >= 8 && li < 8 + NV;                           // group B: lane 8 + j shadows lane j
+        const int lj = shb ? li - 8 : ls, j5 = lj >= NU ? lj - NU : 0;     // (lj: the lane's role; lanes 1 and 9 load like lanes 0 and 8 and are not read)
+        const double *yrb = lj < NU ? ysl<CP>(L, 0) + (shb ? 1 : 0) : L.rb + j5;
+        const int yrs = lj < NU ? (CP == 3 ? hstride<CP>() : NU) : NX;
+        const int fbo = lj < NU ? (shb ? FB_R1 : FB_R0) : FB_LXU + 2 * j5 + (shb ? 1 : 0);
+        const double i_psi = lj == ZPSI ? 1.0 : 0.0, i_v = lj == ZV ? 1.0 : 0.0;
         double *dv_own = L.dv + ls;
-        const BaLane br = ba_row4(N, i5);
+        const BaLane br = ba_row4(N, j5);
         auto load_stage = [&](Ops &o, int k) {
             const double *Fb = L.Hh + hoff<CP>(k);
             o.yr = yrb[mul24(k, yrs)];
             o.a0 = Fb[fbo]; o.a1 = Fb[fbo + 1];
             if constexpr (CP) {
-                const double *Tr = L.tab + br.o0 + mul24(k, br.st);              // own row of [B A] as (b_a, b_w, a_psi, a_v), at stride 2
+                const double *Tr = L.tab + br.o0 + mul24(k, br.st);              // own row of [B E] as (b_a, b_w, e_psi, e_v), at stride 2
                 o.a_psi = Tr[4]; o.a_v = Tr[6];
                 o.b_a = Tr[0]; o.b_w = Tr[2];
             } else {
-                const double *BAr = L.BA + k * NX * NV + i5 * NV;          // own row of [B A]
+                const double *BAr = L.BA + k * NX * NV + j5 * NV;          // own row of [B A]
                 o.a_psi = BAr[ZPSI]; o.a_v = BAr[ZV];                      // loads only: arithmetic here would wait for them
                 o.b_a = BAr[ZA]; o.b_w = BAr[ZW];
             }
@@ -618,18 +626,19 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
             // product form (round 4) has 13, four LDS instructions fewer.  At eight trajectories per CU the LDS unit is the busier one (65 % of the kernel
             // time, most of it these sweeps): cfg 2 1.288 -> 1.343 M solves/s (+4.3 %, profiles/round6_saturated_levers_ab.jsonl).
             // Every kernel family takes it (the fast and the compact kernel of a shape stay bitwise equal); the sums associate differently: rounding level.
-            // (p0, p1 are read from lanes 2..6 only -- bcast16<NU + m> --, where a 0 / 1 lane mask that used to multiply them was 1.0: gone, same bits)
-            const double p0 = o.a0 * dx, p1 = o.a1 * dx;
-            double s0 = o.yr, s1 = o.yr;
-            static_for<0, NX>([&](auto m_) { constexpr int m = decltype(m_)::value; s0 += bcast16<NU + m>(p0); s1 += bcast16<NU + m>(p1); });
+            // (the products are read from lanes 2..6 and 10..14 only, where a 0 / 1 lane mask that used to multiply them was 1.0: gone, same bits)
+            const double pa = o.a0 * dx;                                   // lanes 2..6: Lxu_i0 dx_i, lanes 10..14: Lxu_i1 dx_i
+            double s = o.yr;
+            static_for<0, NX>([&](auto m_) { constexpr int m = decltype(m_)::value; s += dpp_shift_zero<0x100 + NU + m>(pa); });      // row_shl:(2 + m)
             double dxs[NX];
             dxs[ZPSI - NU] = bcast16<ZPSI>(dx); dxs[ZV - NU] = bcast16<ZV>(dx);
-            const double u1 = bcast16<1>(-s1 * o.a1);                      // lane 1: -s1 1/L11
-            const double u0 = bcast16<0>((-s0 - o.a1 * u1) * o.a0);        // lane 0: (-s0 - L10 u1) 1/L00   (its a1 is L10)
+            const double u1 = bcast16<8>(-s * o.a0);                       // lane 8: -s1 1/L11
+            const double u0 = bcast16<0>((-s - o.a1 * u1) * o.a0);         // lane 0: (-s0 - L10 u1) 1/L00   (its a1 is L10)
             if (rowl && li == 0) { L.dv[k * NV] = u0; L.dv[k * NV + 1] = u1; }
             if (xl) dv_own[k * NV] = dx;
             const double dpsi = dxs[ZPSI - NU], dvv = dxs[ZV - NU];
-            const double e_psi = o.a_psi - i_psi, e_v = o.a_v - i_v;
+            // compact layouts: the table rows hold E = A - I itself (ba_tab_init); the dense [B A] of the other layouts holds A
+            const double e_psi = CP ? o.a_psi : o.a_psi - i_psi, e_v = CP ? o.a_v : o.a_v - i_v;
             dx = dx + e_psi * dpsi + e_v * dvv + o.b_a * u0 + o.b_w * u1 + o.yr;   // lanes 2..6 meaningful (their yr is rb_i)
         };
         Ops oa, ob;
