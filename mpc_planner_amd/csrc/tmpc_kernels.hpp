@@ -371,6 +371,19 @@ __device__ __forceinline__ void static_for(F &&f)
 // added on the vector side.
 __device__ __forceinline__ int mul24(int a, int b) { return (int)__umul24((unsigned)a, (unsigned)b); }
 __device__ __forceinline__ int uni(int x) { asm volatile("" : "+s"(x)); return x; }
+// at8: the address of stage k's part of an operand stream with base and stride kept in BYTES.  On a `double *`, base + mul24(k, stride in elements)
+// compiles to the 24-bit multiply AND a shift-and-add that scales the product by eight (v_mul_u32_u24 + v_lshl_add_u32), per stream and stage; with
+// the stride in bytes (B8 * elements, folded where the lane roles are set up, before the loop) the whole address is ONE v_mad_u32_u24 -- base and
+// stride are the two values that were live anyway.  A stride that is a compile-time fact of the instantiation with a wave-uniform k stays on the
+// scalar side (s_mul, one v_add).  The char * arithmetic keeps the pointer's provenance: the accesses stay ds_* (checked in the assembly).
+// 24 bits hold every product: the horizon is at most STAGE_MAX stages (tmpc_create refuses more) and the largest stride is a dense [B A] block.
+constexpr int B8 = (int)sizeof(double), STAGE_MAX = 62;
+static_assert((long long)(STAGE_MAX + 1) * (NX * NV > NP28 + 2 ? NX * NV : NP28 + 2) * B8 < (1ll << 24), "stage index x byte stride must fit mul24");
+template <typename T> __device__ __forceinline__ T *at8(T *base, int k, int stride_bytes) { return (T *)((char *)base + mul24(k, stride_bytes)); }
+// (at8u: k wave-uniform -- the stage loops' counter -- and the stride a compile-time constant: a plain product, which the compiler keeps on the scalar
+//  side or turns into a running offset.  mul24 here made it fold `uniform * constant + per-lane base` into a v_mad_u64_u32: quarter rate again.)
+template <typename T> __device__ __forceinline__ T *at8o(T *base, int off_bytes) { return (T *)((char *)base + off_bytes); }
+template <typename T> __device__ __forceinline__ T *at8u(T *base, int k, int stride_bytes) { return at8o(base, k * stride_bytes); }
 // 1/sqrt(d) for d > 0: v_rsq_f64 seed (5e-8 relative, measured) + one third-order (Halley) step: with e = 1 - d y^2,
 // y (1 + e/2 + 3 e^2/8) leaves an error of order e^3 -- full double precision in five dependent operations, where two Newton steps
 // take eight (this sits on the critical chain of the Cholesky: seven pivots per stage)

@@ -55,13 +55,13 @@ __device__ unsigned long long g_sweep_prof[SP_COUNT];
 //  ONE two-double load with a per-lane base where every lane loaded all three, two instructions; the arithmetic is the same)
 constexpr int FB_LXU = 0, FB_R0 = 10, FB_L10 = 11, FB_R1 = 12, FB_P = 13;
 
-// L.scr: SCR_COMPACT doubles in the compact one-wave carve, SCR_FULL in every other one (tmpc_fast.hpp, tmpc_kernels.hpp).  The factorisation's stores of lanes
-// outside a store group go to a dummy region of it that nobody reads: RDUM_EXTENT doubles from RDUM_BASE_COMPACT / RDUM_BASE_FULL -- the P row's five at
+// L.scr: SCR_COMPACT doubles in the compact one-wave carve, SCR_FULL in every other one (tmpc_fast.hpp, tmpc_kernels.hpp).  The stage loops' stores of lanes
+// outside a store group (factorisation and both vector sweeps) go to a dummy region of it that nobody reads: RDUM_EXTENT doubles from RDUM_BASE_COMPACT / RDUM_BASE_FULL -- the P row's five at
 // RDUM_P, the pair's two at RDUM_PAIR, the three pivots on top of the P row's at RDUM_PIV -- below the two-wave kernels' flag L.scr[SCR_FULL - 1] and above
 // what the other users of L.scr take (the block reductions' slots, the parallel-in-time factorisation's four doubles at 48).
 constexpr int SCR_COMPACT = 8, SCR_FULL = 64;
 constexpr int RDUM_P = 0, RDUM_PIV = 0, RDUM_PAIR = 5, RDUM_EXTENT = 7, RDUM_BASE_COMPACT = 0, RDUM_BASE_FULL = 56;
-static_assert(RDUM_P + NX <= RDUM_PAIR && RDUM_PIV + 3 <= RDUM_PAIR && RDUM_PAIR + NU <= RDUM_EXTENT, "dummy slots of the factorisation's store groups");
+static_assert(RDUM_P + NX <= RDUM_PAIR && RDUM_PIV + 3 <= RDUM_PAIR && RDUM_PAIR + NU <= RDUM_EXTENT, "dummy slots of the stage loops' store groups");
 static_assert(RDUM_BASE_COMPACT + RDUM_EXTENT <= SCR_COMPACT, "the dummy region must fit the compact carve's L.scr");
 static_assert(RDUM_BASE_FULL >= 52 && RDUM_BASE_FULL + RDUM_EXTENT <= SCR_FULL - 1, "the dummy region must stay between scr + 48..51 and the flag scr[63]");
 
@@ -189,46 +189,53 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
     // arithmetic were ~17 of the stage loop's ~250 instructions): a lane reads hk[j] = row[j] at IMMEDIATE offsets from the start of its row of
     // the packed Hh block -- the entries j > own row index belong to the next row and are never used (chol_rows reads the lower triangle only).
     // (the same for ba[] -- running offsets or pointers, five more values live across the stage loop -- pushed the compact kernels into scratch
-    // twice: ba[] keeps its (base + k * stride) form, which the compiler rematerialises; mul24: tmpc_kernels.hpp)
+    // twice: ba[] keeps its (base + k * stride) form, which the compiler rematerialises)
+    // Every stream of the stage loop -- loads and stores -- is a (base pointer, stride in BYTES) pair per lane, set up here, and its stage address is
+    // at8(base, k, stride): one v_mad_u32_u24 (tmpc_kernels.hpp).  The hk[] stream used to be `hrow + (vec ? k * NV : hoff<CP>(k))`, k times a per-lane
+    // select of two constants: a full 32-bit (quarter-rate) multiply per stage; it is the same pair form now.
     const double *hrow = nullptr;
-    const double *bbase = CP ? L.tab : L.BA;
-    int bo[NX], bst[NX];
+    int hst = 0;
+    const double *bo[NX] = {};
+    int bst[NX] = {};
     if constexpr (VEC) {
-        hrow = vec ? L.gh : L.Hh + pidx(ls, 0);       // (row start inside a stage's block; the block's offset is added per stage: hoff<CP>)
+        hrow = vec ? L.gh : L.Hh + pidx(ls, 0);       // (row start inside a stage's block)
+        hst = (vec ? NV : hstride<CP>()) * B8;
         if constexpr (CP) {
             // the table keeps a column's entries of rows x, y and of rows psi, v, s next to each other, as rb is: two bases per lane, three loads
             // (2 + 2 + 1 doubles) where five bases took five
-            bo[0] = vec ? (int)(L.rb - L.tab) : bc.o0; bst[0] = vec ? NX : bc.st;
-            bo[2] = vec ? (int)(L.rb - L.tab) + 2 : bc.o1; bst[2] = vec ? NX : 0;
+            bo[0] = vec ? L.rb : L.tab + bc.o0; bst[0] = (vec ? NX : bc.st) * B8;
+            bo[2] = vec ? L.rb + 2 : L.tab + bc.o1; bst[2] = (vec ? NX : 0) * B8;
         } else {
 #pragma unroll
-            for (int m = 0; m < NX; m++) { bo[m] = vec ? (int)(L.rb - L.BA) + m : m * NV + ls; bst[m] = vec ? NX : NX * NV; }
+            for (int m = 0; m < NX; m++) { bo[m] = vec ? L.rb + m : L.BA + m * NV + ls; bst[m] = (vec ? NX : NX * NV) * B8; }
         }
     }
+    const double *tcb = CP ? L.tab + bc.o0 : nullptr;             // (non-VEC compact: rows x, y of the own column of [B A] in the table)
+    const int tcs = bc.st * B8;
     // (load_stage reads stage k, then k - 1, ...; the last call re-loads stage 0)
     auto load_stage = [&](Opnd &o, int k) {
         // unconditional loads (clamped indices): entries above the diagonal / of idle lanes are never used
         if constexpr (VEC) {
-            const double *hr = hrow + (vec ? k * NV : hoff<CP>(k));          // (two wave-uniform offsets, one select per stage)
+            const double *hr = at8(hrow, k, hst);
 #pragma unroll
             for (int j = 0; j < NV; j++) o.hk[j] = hr[j];
             if constexpr (CP) {
-                const double *T0 = bbase + bo[0] + mul24(k, bst[0]), *T2 = bbase + bo[2] + mul24(k, bst[2]);
+                const double *T0 = at8(bo[0], k, bst[0]), *T2 = at8(bo[2], k, bst[2]);
                 o.ba[0] = T0[0]; o.ba[1] = T0[1]; o.ba[2] = T2[0]; o.ba[3] = T2[1]; o.ba[4] = T2[2];
             } else {
 #pragma unroll
-                for (int m = 0; m < NX; m++) o.ba[m] = bbase[bo[m] + mul24(k, bst[m])];
+                for (int m = 0; m < NX; m++) o.ba[m] = *at8(bo[m], k, bst[m]);
             }
         } else {
-            const double *Hk = L.Hh + hoff<CP>(k);
+            const double *Hk = at8u(L.Hh, k, hstride<CP>() * B8);
 #pragma unroll
             for (int j = 0; j < NV; j++) o.hk[j] = Hk[pidx(ls, j <= ls ? j : ls)];
             if constexpr (CP) {
-                { const double *Tc = L.tab + bc.o0 + mul24(k, bc.st); o.ba[0] = Tc[0]; o.ba[1] = Tc[1]; }       // rows x, y of the own column: one load
+                { const double *Tc = at8(tcb, k, tcs); o.ba[0] = Tc[0]; o.ba[1] = Tc[1]; }       // rows x, y of the own column: one load
 #pragma unroll
                 for (int m = 2; m < NX; m++) o.ba[m] = bac[m];
             } else {
-                const double *BA = L.BA + k * NX * NV;
+                const double *BA = at8u(L.BA, k, NX * NV * B8);
 #pragma unroll
                 for (int m = 0; m < NX; m++) o.ba[m] = BA[m * NV + ls];
             }
@@ -251,15 +258,20 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
     // per-lane (offset, stride) pair -- evaluated once, here -- and the lanes outside a group write to a dummy slot of L.scr (stride 0) that nobody reads.
     // Predicated, each group was a divergent side block of the stage loop (saveexec / branch pairs, a lane compare re-evaluated per stage).
     const bool prl = rowl && li >= NU, vl = vec && wr;
-    const int dum = (int)(L.scr - L.Hh) + (CP ? RDUM_BASE_COMPACT : RDUM_BASE_FULL);
-    const int po = vl ? (int)(L.pr - L.Hh) : prl ? FB_P + i5 * (i5 + 1) / 2 : dum + RDUM_P, pst = vl ? NX : prl ? hstride<CP>() : 0;
-    const int qo = vl ? (CP == 3 ? NP28 : (int)(L.y - L.Hh)) : prl ? FB_LXU + 2 * i5 : dum + RDUM_PAIR;
-    const int qst = vl ? (CP == 3 ? hstride<CP>() : NU) : prl ? hstride<CP>() : 0;
-    const int vo = (rowl && li == 1) ? 0 : dum + RDUM_PIV - FB_R0, vst = (rowl && li == 1) ? hstride<CP>() : 0;
+    // (The pair store and the pivot store cannot share an address register: lane 1 is a real lane of the pivots -- block stride -- and a dummy lane of the
+    //  pairs -- stride 0, it has to stay inside the RDUM_EXTENT doubles --, and lanes 2..6 the other way round: no choice of dummy slots makes the
+    //  difference of the two addresses the same at every stage.)
+    double *const dum = L.scr + (CP ? RDUM_BASE_COMPACT : RDUM_BASE_FULL);
+    double *const po = vl ? L.pr : prl ? L.Hh + FB_P + i5 * (i5 + 1) / 2 : dum + RDUM_P;
+    const int pst = (vl ? NX : prl ? hstride<CP>() : 0) * B8;
+    double *const qo = vl ? (CP == 3 ? L.Hh + NP28 : L.y) : prl ? L.Hh + FB_LXU + 2 * i5 : dum + RDUM_PAIR;
+    const int qst = (vl ? (CP == 3 ? hstride<CP>() : NU) : prl ? hstride<CP>() : 0) * B8;
+    double *const vo = (rowl && li == 1) ? L.Hh : dum + RDUM_PIV - FB_R0;
+    const int vst = ((rowl && li == 1) ? hstride<CP>() : 0) * B8;
     auto store_pairs = [&](int k, double r0, double r1) {
-        double *pp = L.Hh + qo + mul24(k, qst);
+        double *pp = at8(qo, k, qst);
         pp[0] = f[0]; pp[1] = f[1];
-        double *Fv = L.Hh + vo + mul24(k, vst);
+        double *Fv = at8(vo, k, vst);
         Fv[FB_L10] = f[0]; Fv[FB_R0] = r0; Fv[FB_R1] = r1;
     };
     auto stage = [&](const Opnd &o, Opnd &nx, int k) {
@@ -280,7 +292,7 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
         // lane 1's value on one address at once for the pairs (2, 1) and (1, 0)) -- hence the compiler barriers between them; only the pair (4, 3), whose
         // junk lands on junk or on entries <= 2, may share an instruction.
         {
-            double *Ln = L.Hh + po + mul24(k + 1, pst);
+            double *Ln = at8(po, k + 1, pst);
             Ln[4] = f[NU + 4]; Ln[3] = f[NU + 3];
             asm volatile("" ::: "memory");
             Ln[2] = f[NU + 2];
@@ -527,8 +539,11 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         // lane as with 64, and at eight trajectories per CU the launch follows the LDS instruction count of these loops).  The pivot data is used by
         // lanes 0, 1 only and the Lxu pair by lanes 2..6 only, both sit in the stage's factor block: one pair (a0, a1) = lane 0 (1/L00, L10), lane 1
         // (L10, 1/L11), lane 2 + i (Lxu_i0, Lxu_i1).  The arithmetic on every lane that counts is what it was (profiles/sweep_operand_merge_ab.jsonl).
+        // Addresses: every stream of the loop is at8(base, k, stride in bytes), base and stride set up here (tmpc_kernels.hpp): the per-lane strides
+        // (gh / q, the table column) one v_mad_u32_u24 per stage, the block stride -- a compile-time fact -- a scalar product added to the lane's base.
         struct Ops { double ghj, ba[NX], a0, a1; };                        // (ghj: gh_j on lanes 0..6, q_i on lanes 8..12)
-        const int fbo = li < NU ? FB_R0 + li : FB_LXU + 2 * i5;            // (lanes >= 7 follow lane 2: their values are not used)
+        const double *const fb = L.Hh + (li < NU ? FB_R0 + li : FB_LXU + 2 * i5);      // own pair in a factor block (lanes >= 7 follow lane 2: their values are not used)
+        constexpr int HS8 = hstride<CP>() * B8, YS8 = (CP == 3 ? hstride<CP>() : NU) * B8;
         const BaLane bc = ba_column(N, ls);
         double bac[NX];
         if constexpr (CP) {
@@ -539,20 +554,32 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         // a per-lane (pointer, stride) pair --, and one row shift by six lanes hands it to lane 2 + i: the same value, one LDS load per stage fewer
         const bool ql = li >= 8 && li < 8 + NX;
         const double *ghq = ql ? L.dpi + NX + (li - 8) : L.gh + ls;
-        const int ghs = ql ? NX : NV;
+        const int ghs = (ql ? NX : NV) * B8;
+        const double *const tcb = CP ? L.tab + bc.o0 : L.BA + ls;          // own column of [B A]: rows x, y in the table / the dense block
+        const int tcs = bc.st * B8;
+        // The two stores of a stage (y: lane 0, p: lanes 2..6) are stores of EVERY lane through a per-lane (base, stride) pair, as in the factorisation:
+        // the lanes outside a store's group write to its dummy slot of L.scr (stride 0), which nobody reads -- the sweeping wave is the only one at
+        // work between the barriers around the sweeps.  Predicated, each store was an s_and_saveexec / s_or pair around a block of the stage loop:
+        // 18 -> 8 SALU instructions per trip of two stages for one VALU more; the same stores in the same order on the lanes that count.  (Measured
+        // alone before the byte addresses: +0.2 ... 0.3 %, inside the spread, left out; on top of them +0.8 % / +1.1 % in two passes at a base
+        // spread of 0.12 %: profiles/riccati_stage_addresses_ab.jsonl.)
+        double *const dumb = L.scr + (CP ? RDUM_BASE_COMPACT : RDUM_BASE_FULL);
+        const bool l0 = rowl && li == 0;
+        double *const ydb = l0 ? ysl<CP>(L, 0) : dumb + RDUM_PAIR, *const pdb = xl ? L.pr + i5 : dumb + RDUM_P;
+        const int yds = l0 ? YS8 : 0, pds = xl ? NX * B8 : 0;
         auto load_stage = [&](Ops &o, int k) {
-            const double *Fb = L.Hh + hoff<CP>(k);
-            o.ghj = ghq[mul24(k, ghs)];
+            const double *Fb = at8u(fb, k, HS8);
+            o.ghj = *at8(ghq, k, ghs);
             if constexpr (CP) {
-                { const double *Tc = L.tab + bc.o0 + mul24(k, bc.st); o.ba[0] = Tc[0]; o.ba[1] = Tc[1]; }       // rows x, y of the own column: one load
+                { const double *Tc = at8(tcb, k, tcs); o.ba[0] = Tc[0]; o.ba[1] = Tc[1]; }       // rows x, y of the own column: one load
 #pragma unroll
                 for (int l = 2; l < NX; l++) o.ba[l] = bac[l];
             } else {
-                const double *BA = L.BA + k * NX * NV;
+                const double *BA = at8u(tcb, k, NX * NV * B8);
 #pragma unroll
-                for (int l = 0; l < NX; l++) o.ba[l] = BA[l * NV + ls];
+                for (int l = 0; l < NX; l++) o.ba[l] = BA[l * NV];
             }
-            o.a0 = Fb[fbo]; o.a1 = Fb[fbo + 1];
+            o.a0 = Fb[0]; o.a1 = Fb[1];
         };
         auto stage = [&](const Ops &o, int k) {
             const double Pb = p + dpp_shift_zero<0x106>(o.ghj);           // row_shl:6: lane 2 + i takes lane 8 + i's q_i
@@ -561,8 +588,9 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
             const double y0 = bcast16<0>(fj * o.a0);                       // lane 0: fj 1/L00
             const double y1 = bcast16<1>((fj - o.a0 * y0) * o.a1);         // lane 1: (fj - L10 y0) 1/L11   (its a0 is L10)
             p = fj - o.a0 * y0 - o.a1 * y1;                                // lanes 2..6: fj - Lxu_i0 y0 - Lxu_i1 y1
-            if (rowl && li == 0) { ysl<CP>(L, k)[0] = y0; ysl<CP>(L, k)[1] = y1; }
-            if (xl) L.pr[k * NX + i5] = p;
+            double *const yk = at8(ydb, k, yds);
+            yk[0] = y0; yk[1] = y1;
+            *at8(pdb, k, pds) = p;
         };
         Ops oa, ob;
         load_stage(oa, N - 1);
@@ -600,21 +628,30 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         const bool shb = li >= 8 && li < 8 + NV;                           // group B: lane 8 + j shadows lane j
         const int lj = shb ? li - 8 : ls, j5 = lj >= NU ? lj - NU : 0;     // (lj: the lane's role; lanes 1 and 9 load like lanes 0 and 8 and are not read)
         const double *yrb = lj < NU ? ysl<CP>(L, 0) + (shb ? 1 : 0) : L.rb + j5;
-        const int yrs = lj < NU ? (CP == 3 ? hstride<CP>() : NU) : NX;
-        const int fbo = lj < NU ? (shb ? FB_R1 : FB_R0) : FB_LXU + 2 * j5 + (shb ? 1 : 0);
+        const int yrs = (lj < NU ? (CP == 3 ? hstride<CP>() : NU) : NX) * B8;
+        const double *const fb = L.Hh + (lj < NU ? (shb ? FB_R1 : FB_R0) : FB_LXU + 2 * j5 + (shb ? 1 : 0));
+        constexpr int HS8 = hstride<CP>() * B8;
         const double i_psi = lj == ZPSI ? 1.0 : 0.0, i_v = lj == ZV ? 1.0 : 0.0;
-        double *dv_own = L.dv + ls;
         const BaLane br = ba_row4(N, j5);
+        const double *const trb = CP ? L.tab + br.o0 : L.BA + j5 * NV;     // own row of [B E] in the table / of [B A] in the dense block
+        const int trs = br.st * B8;
+        // stores of every lane with dummy slots outside the group, as in the backward sweep: du on lane 0, dx on lanes 2..6.  (One address register for
+        // both -- they share the stride, and lane 0's dx base is L.dv itself -- takes two VALU instructions per trip off the PREDICATED form, 65 -> 63;
+        // it does not combine with the dummy slots, where a lane is inside one group and outside the other, and measured less: +1.7 % against +2.7 %.)
+        double *const dumb = L.scr + (CP ? RDUM_BASE_COMPACT : RDUM_BASE_FULL);
+        const bool l0 = rowl && li == 0;
+        double *const udb = l0 ? L.dv : dumb + RDUM_PAIR, *const xdb = xl ? L.dv + ls : dumb + RDUM_P;
+        const int uds = l0 ? NV * B8 : 0, xds = xl ? NV * B8 : 0;
         auto load_stage = [&](Ops &o, int k) {
-            const double *Fb = L.Hh + hoff<CP>(k);
-            o.yr = yrb[mul24(k, yrs)];
-            o.a0 = Fb[fbo]; o.a1 = Fb[fbo + 1];
+            const double *Fb = at8u(fb, k, HS8);
+            o.yr = *at8(yrb, k, yrs);
+            o.a0 = Fb[0]; o.a1 = Fb[1];
             if constexpr (CP) {
-                const double *Tr = L.tab + br.o0 + mul24(k, br.st);              // own row of [B E] as (b_a, b_w, e_psi, e_v), at stride 2
+                const double *Tr = at8(trb, k, trs);                       // own row of [B E] as (b_a, b_w, e_psi, e_v), at stride 2
                 o.a_psi = Tr[4]; o.a_v = Tr[6];
                 o.b_a = Tr[0]; o.b_w = Tr[2];
             } else {
-                const double *BAr = L.BA + k * NX * NV + j5 * NV;          // own row of [B A]
+                const double *BAr = at8u(trb, k, NX * NV * B8);             // own row of [B A]
                 o.a_psi = BAr[ZPSI]; o.a_v = BAr[ZV];                      // loads only: arithmetic here would wait for them
                 o.b_a = BAr[ZA]; o.b_w = BAr[ZW];
             }
@@ -634,8 +671,9 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
             dxs[ZPSI - NU] = bcast16<ZPSI>(dx); dxs[ZV - NU] = bcast16<ZV>(dx);
             const double u1 = bcast16<8>(-s * o.a0);                       // lane 8: -s1 1/L11
             const double u0 = bcast16<0>((-s - o.a1 * u1) * o.a0);         // lane 0: (-s0 - L10 u1) 1/L00   (its a1 is L10)
-            if (rowl && li == 0) { L.dv[k * NV] = u0; L.dv[k * NV + 1] = u1; }
-            if (xl) dv_own[k * NV] = dx;
+            double *const uk = at8(udb, k, uds);
+            uk[0] = u0; uk[1] = u1;
+            *at8(xdb, k, xds) = dx;
             const double dpsi = dxs[ZPSI - NU], dvv = dxs[ZV - NU];
             // compact layouts: the table rows hold E = A - I itself (ba_tab_init); the dense [B A] of the other layouts holds A
             const double e_psi = CP ? o.a_psi : o.a_psi - i_psi, e_v = CP ? o.a_v : o.a_v - i_v;

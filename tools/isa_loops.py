@@ -2,6 +2,10 @@
 A loop's SIDE BLOCKS -- code placed outside the loop's line range that the loop branches out to and that branches (or falls) back into it, as the
 compiler lays out divergent regions (s_cbranch_exec* to a block behind the loop, s_branch back) -- are found and added: every loop is printed with the
 mix of its line range and -- innermost loops only --, where it has side blocks, with the mix including them (every side block counted once: an upper bound of one trip).
+Two fields follow the address arithmetic of the sequential stage loops: `int` counts the VALU integer and move instructions (everything on the vector
+side that is neither floating point nor a cross-lane move: the index / address arithmetic, selects and register copies) and `quarter` the quarter-rate
+integer forms among them (the 32-bit multiplies v_mul_lo / v_mul_hi and the 64-bit multiply-adds v_mad_u64_u32 / v_mad_i64_i32: 16 issue cycles where
+v_mul_u32_u24 / v_mad_u32_u24 take 4; csrc/tmpc_kernels.hpp, mul24).
 Usage: python tools/isa_loops.py file.s kernel-name-prefix"""
 import re
 import sys
@@ -28,8 +32,10 @@ for i, l in enumerate(body):
 def is_instr(l):
     s = l.strip()
     return bool(s) and not s.startswith((";", ".")) and not s.endswith(":")
+FLOAT = re.compile(r"_(f|bf)(16|32|64)|_pk_f")
+QUARTER = ("v_mul_lo_u32", "v_mul_lo_i32", "v_mul_hi_u32", "v_mul_hi_i32", "v_mad_u64_u32", "v_mad_i64_i32")
 def mix(a, b):
-    c = dict(valu=0, f64=0, salu=0, lds=0, vmem=0, readlane=0, dpp=0, nop=0, wait=0, trans=0, total=0)
+    c = dict(valu=0, f64=0, salu=0, lds=0, vmem=0, readlane=0, dpp=0, nop=0, wait=0, trans=0, int=0, quarter=0, total=0)
     for l in body[a:b + 1]:
         if not is_instr(l):
             continue
@@ -41,6 +47,8 @@ def mix(a, b):
             if "readlane" in op or "readfirstlane" in op: c["readlane"] += 1
             if "dpp" in l: c["dpp"] += 1
             if op.startswith(("v_rsq", "v_rcp", "v_sqrt", "v_sin", "v_cos", "v_exp", "v_log")): c["trans"] += 1
+            if not FLOAT.search(op) and "lane" not in op and "dpp" not in l: c["int"] += 1
+            if op.startswith(QUARTER): c["quarter"] += 1
         elif op.startswith("s_nop"): c["nop"] += 1
         elif op.startswith("s_waitcnt"): c["wait"] += 1
         elif op.startswith("s_"): c["salu"] += 1
