@@ -358,6 +358,21 @@ __device__ __forceinline__ double bcast16(double x)
     const long long r = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(long long, x), 0x150 + LANE, 0xf, 0xf, false);   // (no `old` value to materialise)
     return __builtin_bit_cast(double, r);
 }
+// The broadcast folded into its multiply-add: acc + bcast16<LANE>(src) * y as ONE v_fmac_f64_dpp row_newbcast where the compiler emits v_mov_b64_dpp +
+// v_fma_f64 (it never selects the fused form, hence inline assembly); a `-` in front of the broadcast operand gives acc - bcast16<LANE>(src) * y.
+// Rounding: one fused multiply-add with the broadcast value as one multiplicand -- bit for bit fma(bcast16<LANE>(src), y, acc).
+// TMPC_FMAC_BCAST16 is one such instruction as text, for asm statements whose operands are named; the lane is an "n" operand or a literal.
+// Hazard: a DPP operand must not be read within two wait states of a VALU write of that register, and the compiler's hazard recogniser does not look
+// into an asm statement: the wait states are part of the statement, `s_nop 1` in front of its first fused instruction.  What that costs was measured
+// (tools/fused_bcast_cost.hip, profiles/riccati_fused_broadcast_ab.jsonl; 64 lanes, cycles of the SIMD per multiply-add with one / two waves on it):
+// mov + fma 8.3 ... 9.0 / 8.1 ... 8.5, s_nop 1 + fused 12.2 / 6.1, fused alone 4.3 ... 5.0 / 4.1 -- the pad takes a wave eight cycles, which only a second
+// wave on the SIMD can use.  So the stage loops (tmpc_riccati.hpp) fuse in GROUPS: one statement holds the pad and then every fused instruction of a
+// group whose sources NO instruction of the group writes (its accumulators are early-clobber operands, so none shares a register with a source): from
+// the second instruction on, the two preceding VALU slots are the statement's own and provably leave the source alone.  Not volatile: a group is
+// scheduled like any instruction and deleted when unused.  Operands that come from an LDS load need nothing special -- the compiler's s_waitcnt
+// bookkeeping follows the registers of asm operands.
+#define TMPC_FMAC_BCAST16(acc, src, y, lane) "v_fmac_f64_dpp " acc ", " src ", " y " row_newbcast:" lane " row_mask:0xf bank_mask:0xf\n\t"
+// (A helper per instruction, fmac_bcast16<LANE>(acc, src, y) with a pad of its own, was built first and measured: +0.5 % where the groups give +5.2 %.)
 // compile-time loop: f(std::integral_constant<int, I>) for I = A .. B-1 (lane numbers of DPP controls must be immediates)
 template <int A, int B, typename F>
 __device__ __forceinline__ void static_for(F &&f)

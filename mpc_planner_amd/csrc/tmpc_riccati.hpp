@@ -83,6 +83,69 @@ template <int CP> __device__ __forceinline__ double *ysl(const Lds &L, int k) { 
 // busy 70 % of the kernel time at eight trajectories per CU and the sweeps issue two thirds of its instructions -- was measured in round 5: 1.3 %
 // SLOWER, profiles/round5_o_sweep_rows_ab.jsonl; an LDS instruction costs the same with 16 lanes as with 64 and the EXEC changes are not free.)
 
+// ---- row broadcasts folded into the multiply-adds of the stage loops ---------------------------------------------------------------------
+// Groups of v_fmac_f64_dpp behind ONE hazard pad (TMPC_FMAC_BCAST16, tmpc_kernels.hpp: why groups, the rounding, what the pad costs).  In every group
+// the sources of the broadcasts are inputs that no instruction of the group writes, the accumulators are early-clobber, and the unfused expression
+// was the same chain of FMAs -- explicit fma() or the contracted a += b * c, checked in the parent's assembly -- with the same operand roles in the
+// same order: same bits.  Per stage of the factorisation 39 multiply-adds are fused and 29 of the 36 v_mov_b64_dpp are gone (left: column 0 of P, whose
+// products open the w chains -- an fmac onto 0.0 would differ in the sign of a zero --, and the two pivots, which feed rsqrt_nr), 119 -> 90 VALU
+// instructions and 4 pads; per stage of the backward sweep 5 of 9, 24 -> 19 and one pad: +5.2 % on the bench launch, lever by lever in
+// profiles/riccati_fused_broadcast_ab.jsonl (tools/isa_loops.py counts `fused`, `nop`).  Not taken: the forward sweep's dx update, whose sources are
+// written just before (a pad each) and whose accumulator is one of them (a register copy): -0.4 %.
+// column c of chol_rows<0, NU>: f[j] -= bcast16<j>(f[c]) * f[c] for the rows j = c + 1 .. NV - 1 (f[c] was written just before: the pad is needed)
+#define CH_T(i) TMPC_FMAC_BCAST16("%[a" #i "]", "-%[s]", "%[s]", "%[l" #i "]")
+#define CH_A(i) [a##i] "+&v"(f[c + 1 + i])
+#define CH_L(i) [l##i] "n"(c + 1 + i)
+template <int c>
+__device__ __forceinline__ void chol_column_update(double (&f)[NV])
+{
+    static_assert(NV == 7 && NU == 2 && c >= 0 && c < NU, "the two input columns: six and five rows below the pivot");
+    if constexpr (c == 0)
+        asm("s_nop 1\n\t" CH_T(0) CH_T(1) CH_T(2) CH_T(3) CH_T(4) CH_T(5)
+            : CH_A(0), CH_A(1), CH_A(2), CH_A(3), CH_A(4), CH_A(5) : [s] "v"(f[c]), CH_L(0), CH_L(1), CH_L(2), CH_L(3), CH_L(4), CH_L(5));
+    else
+        asm("s_nop 1\n\t" CH_T(0) CH_T(1) CH_T(2) CH_T(3) CH_T(4)
+            : CH_A(0), CH_A(1), CH_A(2), CH_A(3), CH_A(4) : [s] "v"(f[c]), CH_L(0), CH_L(1), CH_L(2), CH_L(3), CH_L(4));
+}
+#undef CH_T
+#undef CH_A
+#undef CH_L
+// the terms m = 1 .. 4 of the five chains w_n = sum_m P_nm ba_m, P_nm = bcast16<NU + max(n, m)>(f[NU + min(n, m)]); w[n] comes in as the product
+// P_n0 ba_0.  m outer, n inner: a chain's terms stay in the order m = 1, 2, 3, 4 and two instructions of one chain are five apart
+#define W_T(n, m, lo, lane) TMPC_FMAC_BCAST16("%[w" #n "]", "%[p" #lo "]", "%[b" #m "]", #lane)
+__device__ __forceinline__ void w_chains_update(double (&w)[NX], const double (&f)[NV], const double (&ba)[NX])
+{
+    static_assert(NU == 2 && NX == 5, "the literal lane numbers NU + max(n, m) below");
+    asm("s_nop 1\n\t"
+        W_T(0, 1, 0, 3) W_T(1, 1, 1, 3) W_T(2, 1, 1, 4) W_T(3, 1, 1, 5) W_T(4, 1, 1, 6)
+        W_T(0, 2, 0, 4) W_T(1, 2, 1, 4) W_T(2, 2, 2, 4) W_T(3, 2, 2, 5) W_T(4, 2, 2, 6)
+        W_T(0, 3, 0, 5) W_T(1, 3, 1, 5) W_T(2, 3, 2, 5) W_T(3, 3, 3, 5) W_T(4, 3, 3, 6)
+        W_T(0, 4, 0, 6) W_T(1, 4, 1, 6) W_T(2, 4, 2, 6) W_T(3, 4, 3, 6) W_T(4, 4, 4, 6)
+        : [w0] "+&v"(w[0]), [w1] "+&v"(w[1]), [w2] "+&v"(w[2]), [w3] "+&v"(w[3]), [w4] "+&v"(w[4])
+        : [p0] "v"(f[NU + 0]), [p1] "v"(f[NU + 1]), [p2] "v"(f[NU + 2]), [p3] "v"(f[NU + 3]), [p4] "v"(f[NU + 4]),
+          [b1] "v"(ba[1]), [b2] "v"(ba[2]), [b3] "v"(ba[3]), [b4] "v"(ba[4]));
+}
+#undef W_T
+// the stage-dependent entries of [B A] in the F row: h_c += bcast16<c>(ba0) * w0, then h_c += bcast16<c>(ba1) * w1, for the columns c = a, w, psi, v
+// (ba0, ba1: rows x, y of the lane's own column of [B A]; h_c comes in as Hh's entry)
+#define F_T(c, s, y) TMPC_FMAC_BCAST16("%[h" #c "]", "%[" #s "]", "%[" #y "]", "%[l" #c "]")
+__device__ __forceinline__ void f_row_update(double &ha, double &hw, double &hp, double &hv, double ba0, double ba1, double w0, double w1)
+{
+    asm("s_nop 1\n\t" F_T(a, s0, y0) F_T(w, s0, y0) F_T(p, s0, y0) F_T(v, s0, y0) F_T(a, s1, y1) F_T(w, s1, y1) F_T(p, s1, y1) F_T(v, s1, y1)
+        : [ha] "+&v"(ha), [hw] "+&v"(hw), [hp] "+&v"(hp), [hv] "+&v"(hv)
+        : [s0] "v"(ba0), [s1] "v"(ba1), [y0] "v"(w0), [y1] "v"(w1), [la] "n"(ZA), [lw] "n"(ZW), [lp] "n"(ZPSI), [lv] "n"(ZV));
+}
+#undef F_T
+// backward sweep: fj += bcast16<NU + l>(Pb) * ba[l], l = 0 .. 4 in this order
+#define B_T(l, lane) TMPC_FMAC_BCAST16("%[fj]", "%[pb]", "%[b" #l "]", #lane)
+__device__ __forceinline__ void bwd_chain_update(double &fj, double Pb, const double (&ba)[NX])
+{
+    static_assert(NU == 2 && NX == 5, "the literal lane numbers NU + l below");
+    asm("s_nop 1\n\t" B_T(0, 2) B_T(1, 3) B_T(2, 4) B_T(3, 5) B_T(4, 6)
+        : [fj] "+&v"(fj) : [pb] "v"(Pb), [b0] "v"(ba[0]), [b1] "v"(ba[1]), [b2] "v"(ba[2]), [b3] "v"(ba[3]), [b4] "v"(ba[4]));
+}
+#undef B_T
+
 // right-looking elimination of columns C0 .. C1-1 of the row-per-lane matrix
 template <int C0, int C1 = NV>
 __device__ __forceinline__ bool chol_rows(double (&f)[NV], int lane, double *r0, double *r1)
@@ -96,10 +159,13 @@ __device__ __forceinline__ bool chol_rows(double (&f)[NV], int lane, double *r0,
         f[c] *= y;                                  // lane i >= c: L_ic (i == c: sqrt(d))
         if (c == 0 && r0) *r0 = y;
         if (c == 1 && r1) *r1 = y;
-        static_for<c + 1, NV>([&](auto j_) {
+        // L_jc to the row's lanes and the update of column j.  The Schur-complement form's two input columns (every kernel's default path) fold the
+        // broadcasts into the multiply-adds, one group per column; the square-root form's seven columns keep the pair (not measured there).
+        if constexpr (C0 == 0 && C1 == NU) chol_column_update<c>(f);
+        else static_for<c + 1, NV>([&](auto j_) {
             constexpr int j = decltype(j_)::value;
-            const double ljc = bcast16<j>(f[c]);    // L_jc to the row's lanes (one v_mov_b64_dpp; folding it into the fmac as
-            f[j] -= f[c] * ljc;                     //  v_fmac_f64_dpp by hand measured no gain: profiles/round3_e_fused_fmac_dpp_rejected.json)
+            const double ljc = bcast16<j>(f[c]);
+            f[j] -= f[c] * ljc;
         });
     });
     (void)lane;                                       // entries above the diagonal are never read
@@ -353,27 +419,29 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
         // Schur-complement form (default): P_{k+1} enters the next stage's F unfactorised (its diagonal is tested after the loop, riccati_factor)
         // w = P [B A]_.,own (the lane's own column of [B A], densely from ba[]); the extra row: P rb + p_{k+1} -- as fma(1.0 or 0.0, f, acc):
         // exactly acc + f on the extra row and acc on the others (f is finite there), without the v_cndmask a select costs
+        // (the first term of a chain is a plain product and keeps its bcast16; the other sixteen entries of Pm are used by the square-root form only)
         double w[NX];
 #pragma unroll
-        for (int n = 0; n < NX; n++) {
-            double acc = Pm[n > 0 ? n : 0][0] * o.ba[0];
+        for (int n = 0; n < NX; n++) w[n] = Pm[n][0] * o.ba[0];
+        w_chains_update(w, f, o.ba);
+        if constexpr (VEC) {
 #pragma unroll
-            for (int m = 1; m < NX; m++) acc = fma(Pm[m > n ? m : n][m > n ? n : m], o.ba[m], acc);
-            w[n] = VEC ? fma(vmask, f[NU + n], acc) : acc;
+            for (int n = 0; n < NX; n++) w[n] = fma(vmask, f[NU + n], w[n]);
         }
         // F row `li`: F_ij = Hh_ij + sum_n w_n [B A]_nj with the sparse columns of [B A] (row-uniform):
         //   x: e0   y: e1   s: e4   psi: (Xp,Yp,1,0,0)   v: (Xv,Yv,0,1,dt)   a: (Xa,Ya,0,dt,dt^2/2)   w: (Xw,Yw,dt,0,0)
         {
             // (round 6) the eight stage-dependent entries of [B A] are rows x, y of the columns a, w, psi, v -- which the lanes of those columns hold as
             // ba[0], ba[1] of their OWN column: eight row broadcasts instead of four row-uniform LDS loads of the dyn8 block (the LDS unit is the busy one)
-            const double Xa = bcast16<ZA>(o.ba[0]), Ya = bcast16<ZA>(o.ba[1]), Xw = bcast16<ZW>(o.ba[0]), Yw = bcast16<ZW>(o.ba[1]);
-            const double Xp = bcast16<ZPSI>(o.ba[0]), Yp = bcast16<ZPSI>(o.ba[1]), Xv = bcast16<ZV>(o.ba[0]), Yv = bcast16<ZV>(o.ba[1]);
-            f[ZA] = fma(w[4], shdt2, fma(w[3], dt, fma(w[1], Ya, fma(w[0], Xa, o.hk[ZA]))));
-            f[ZW] = fma(w[2], dt, fma(w[1], Yw, fma(w[0], Xw, o.hk[ZW])));
+            // (folded into the multiply-adds that open the four chains: Hh's entry + w0 X + w1 Y, accumulated on a copy of the hk operand)
+            double ha = o.hk[ZA], hw = o.hk[ZW], hp = o.hk[ZPSI], hv = o.hk[ZV];
+            f_row_update(ha, hw, hp, hv, o.ba[0], o.ba[1], w[0], w[1]);
+            f[ZA] = fma(w[4], shdt2, fma(w[3], dt, ha));
+            f[ZW] = fma(w[2], dt, hw);
             f[ZX] = o.hk[ZX] + w[0];
             f[ZY] = o.hk[ZY] + w[1];
-            f[ZPSI] = fma(w[1], Yp, fma(w[0], Xp, o.hk[ZPSI])) + w[2];
-            f[ZV] = fma(w[4], sdt, fma(w[1], Yv, fma(w[0], Xv, o.hk[ZV])) + w[3]);
+            f[ZPSI] = hp + w[2];
+            f[ZV] = fma(w[4], sdt, hv + w[3]);
             f[ZS] = o.hk[ZS] + w[4];
         }
         load_stage(nx, k > 0 ? k - 1 : 0);            // operands of the next stage, hidden under the elimination (unconditional, clamped;
@@ -584,7 +652,7 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         auto stage = [&](const Ops &o, int k) {
             const double Pb = p + dpp_shift_zero<0x106>(o.ghj);           // row_shl:6: lane 2 + i takes lane 8 + i's q_i
             double fj = o.ghj;
-            static_for<0, NX>([&](auto l_) { constexpr int l = decltype(l_)::value; fj += o.ba[l] * bcast16<NU + l>(Pb); });
+            bwd_chain_update(fj, Pb, o.ba);                                // fj += sum_l ba[l] bcast16<NU + l>(Pb)
             const double y0 = bcast16<0>(fj * o.a0);                       // lane 0: fj 1/L00
             const double y1 = bcast16<1>((fj - o.a0 * y0) * o.a1);         // lane 1: (fj - L10 y0) 1/L11   (its a0 is L10)
             p = fj - o.a0 * y0 - o.a1 * y1;                                // lanes 2..6: fj - Lxu_i0 y0 - Lxu_i1 y1

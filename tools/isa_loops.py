@@ -6,6 +6,9 @@ Two fields follow the address arithmetic of the sequential stage loops: `int` co
 side that is neither floating point nor a cross-lane move: the index / address arithmetic, selects and register copies) and `quarter` the quarter-rate
 integer forms among them (the 32-bit multiplies v_mul_lo / v_mul_hi and the 64-bit multiply-adds v_mad_u64_u32 / v_mad_i64_i32: 16 issue cycles where
 v_mul_u32_u24 / v_mad_u32_u24 take 4; csrc/tmpc_kernels.hpp, mul24).
+Two more follow the row broadcasts: `dpp` counts every DPP instruction, `fused` those among them that compute (v_fmac_f64_dpp: the broadcast folded into
+the multiply-add, fmac_bcast16 of csrc/tmpc_kernels.hpp; dpp - fused = the plain v_mov_b64_dpp), and `nop` / `nop_states` the s_nop instructions and the
+wait states they stand for (s_nop n = n + 1 states), the price of the fused form's hazard pad.
 Usage: python tools/isa_loops.py file.s kernel-name-prefix"""
 import re
 import sys
@@ -35,7 +38,7 @@ def is_instr(l):
 FLOAT = re.compile(r"_(f|bf)(16|32|64)|_pk_f")
 QUARTER = ("v_mul_lo_u32", "v_mul_lo_i32", "v_mul_hi_u32", "v_mul_hi_i32", "v_mad_u64_u32", "v_mad_i64_i32")
 def mix(a, b):
-    c = dict(valu=0, f64=0, salu=0, lds=0, vmem=0, readlane=0, dpp=0, nop=0, wait=0, trans=0, int=0, quarter=0, total=0)
+    c = dict(valu=0, f64=0, salu=0, lds=0, vmem=0, readlane=0, dpp=0, fused=0, nop=0, nop_states=0, wait=0, trans=0, int=0, quarter=0, total=0)
     for l in body[a:b + 1]:
         if not is_instr(l):
             continue
@@ -46,10 +49,13 @@ def mix(a, b):
             if "_f64" in op: c["f64"] += 1
             if "readlane" in op or "readfirstlane" in op: c["readlane"] += 1
             if "dpp" in l: c["dpp"] += 1
+            if "dpp" in l and not op.startswith("v_mov"): c["fused"] += 1
             if op.startswith(("v_rsq", "v_rcp", "v_sqrt", "v_sin", "v_cos", "v_exp", "v_log")): c["trans"] += 1
             if not FLOAT.search(op) and "lane" not in op and "dpp" not in l: c["int"] += 1
             if op.startswith(QUARTER): c["quarter"] += 1
-        elif op.startswith("s_nop"): c["nop"] += 1
+        elif op.startswith("s_nop"):
+            c["nop"] += 1
+            c["nop_states"] += int(l.split()[1], 0) + 1
         elif op.startswith("s_waitcnt"): c["wait"] += 1
         elif op.startswith("s_"): c["salu"] += 1
         elif op.startswith("ds_"): c["lds"] += 1
