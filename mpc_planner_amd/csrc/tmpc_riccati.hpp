@@ -703,13 +703,16 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         const BaLane br = ba_row4(N, j5);
         const double *const trb = CP ? L.tab + br.o0 : L.BA + j5 * NV;     // own row of [B E] in the table / of [B A] in the dense block
         const int trs = br.st * B8;
-        // stores of every lane with dummy slots outside the group, as in the backward sweep: du on lane 0, dx on lanes 2..6.  (One address register for
-        // both -- they share the stride, and lane 0's dx base is L.dv itself -- takes two VALU instructions per trip off the PREDICATED form, 65 -> 63;
-        // it does not combine with the dummy slots, where a lane is inside one group and outside the other, and measured less: +1.7 % against +2.7 %.)
+        // ONE store per stage, of every lane, with a dummy slot outside the group as in the backward sweep: lane j of the writing row stores component j of
+        // the stage's step [du; dx] -- lane 0 u0, lane 1 u1 (both are row broadcasts: every lane has them), lanes 2..6 dx.  Before, lane 0 stored the pair
+        // and lanes 2..6 dx in a second instruction through an address of its own: per stage one LDS instruction and one address multiply-add fewer for two
+        // selects (four v_cndmask_b32); the same values at the same addresses.  The vector sweeps follow their LDS instructions, not their VALU count:
+        // +2.4 % on the bench launch for 3 VALU instructions MORE per stage (profiles/forward_sweep_fused_sum_ab.jsonl, record one_store).
         double *const dumb = L.scr + (CP ? RDUM_BASE_COMPACT : RDUM_BASE_FULL);
         const bool l0 = rowl && li == 0;
-        double *const udb = l0 ? L.dv : dumb + RDUM_PAIR, *const xdb = xl ? L.dv + ls : dumb + RDUM_P;
-        const int uds = l0 ? NV * B8 : 0, xds = xl ? NV * B8 : 0;
+        const bool l1 = rowl && li == 1;
+        double *const vdb = rowl ? L.dv + ls : dumb + RDUM_P;
+        const int vds = rowl ? NV * B8 : 0;
         auto load_stage = [&](Ops &o, int k) {
             const double *Fb = at8u(fb, k, HS8);
             o.yr = *at8(yrb, k, yrs);
@@ -739,9 +742,7 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
             dxs[ZPSI - NU] = bcast16<ZPSI>(dx); dxs[ZV - NU] = bcast16<ZV>(dx);
             const double u1 = bcast16<8>(-s * o.a0);                       // lane 8: -s1 1/L11
             const double u0 = bcast16<0>((-s - o.a1 * u1) * o.a0);         // lane 0: (-s0 - L10 u1) 1/L00   (its a1 is L10)
-            double *const uk = at8(udb, k, uds);
-            uk[0] = u0; uk[1] = u1;
-            *at8(xdb, k, xds) = dx;
+            *at8(vdb, k, vds) = l0 ? u0 : (l1 ? u1 : dx);
             const double dpsi = dxs[ZPSI - NU], dvv = dxs[ZV - NU];
             // compact layouts: the table rows hold E = A - I itself (ba_tab_init); the dense [B A] of the other layouts holds A
             const double e_psi = CP ? o.a_psi : o.a_psi - i_psi, e_v = CP ? o.a_v : o.a_v - i_v;
