@@ -5,6 +5,7 @@ Host-side mirror of the reference's solver / module interface for this one hot p
   modules.py     -- per-stage parameter writers of the C++ modules (mpc_planner_modules/src/*.cpp)
   scenes.py      -- deterministic synthetic Jackal scenes
   solver.py      -- ctypes binding of the C-ABI (include/tmpc_hip.h) + batched optimize()
+  stack_writers.py -- ctypes binding of include/tmpc_hip_stack.h: obstacle and topology rows of generated solvers, by column
   csrc/          -- HIP kernels (gfx950) and the C-ABI shim
 """
 __all__ = ["parameters", "modules", "scenes"]

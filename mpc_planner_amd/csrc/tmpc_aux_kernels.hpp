@@ -80,14 +80,47 @@ __global__ void tmpc_gather_best_kernel(const int *best, int set_size, int index
     for (int e = threadIdx.x; e < nu_doubles; e += blockDim.x) out_u[(size_t)s * nu_doubles + e] = g >= 0 ? utraj[b * nu_doubles + e] : nan;
 }
 
+// ---- where a row writer puts its values.  The topology and the collision writers below are templates on it: the arithmetic is one source, the
+// destination is either the hand-written parameter layout (the problem's own counts, the ip_* offsets of tmpc_stage.hpp) or a column table the
+// caller read from a generated stack's parameter map (include/tmpc_hip_stack.h).  The table travels by value in the kernel arguments, like
+// tmpc_scatter_parameters' (at most 128 entries: 516 bytes).
+constexpr int SCATTER_MAX_COLS = 128;
+struct ScatterCols { int n; int col[SCATTER_MAX_COLS]; };
+
+struct LayoutRows {
+    __device__ __forceinline__ int n_lin(const Dims &d) const { return d.n_lin; }
+    __device__ __forceinline__ int n_obstacles(const Dims &d) const { return d.M; }
+    __device__ __forceinline__ int row_model(const Dims &d) const { return d.row_model; }
+    __device__ __forceinline__ int lin(const Dims &d, int j, int w) const { return ip_lin(d, j, w); }
+    __device__ __forceinline__ int disc_radius(const Dims &d) const { return ip_disc_radius(d); }
+    __device__ __forceinline__ int disc_offset(const Dims &d) const { return ip_disc_offset(d); }
+    __device__ __forceinline__ int ellipsoid(const Dims &d, int j, int w) const { return ip_ellipsoid(d, j, w); }
+    __device__ __forceinline__ int gauss(const Dims &d, int j, int w) const { return ip_gauss(d, j, w); }
+};
+// topology: col[3 j + w] = (a1, a2, b) of row j < count.  Collision: col[0] = ego_disc_radius, col[1] = ego_disc_0_offset, then per obstacle
+// j < count the module's fields, 7 (model 0: x, y, psi, major, minor, chi, r) or 6 (model 1: x, y, major, minor, risk, r) apart.
+struct ColumnRows {
+    ScatterCols t;
+    int count, model;
+    __device__ __forceinline__ int n_lin(const Dims &) const { return count; }
+    __device__ __forceinline__ int n_obstacles(const Dims &) const { return count; }
+    __device__ __forceinline__ int row_model(const Dims &) const { return model; }
+    __device__ __forceinline__ int lin(const Dims &, int j, int w) const { return t.col[3 * j + w]; }
+    __device__ __forceinline__ int disc_radius(const Dims &) const { return t.col[0]; }
+    __device__ __forceinline__ int disc_offset(const Dims &) const { return t.col[1]; }
+    __device__ __forceinline__ int ellipsoid(const Dims &, int j, int w) const { return t.col[2 + 7 * j + w]; }
+    __device__ __forceinline__ int gauss(const Dims &, int j, int w) const { return t.col[2 + 6 * j + w]; }
+};
+
 // ---- f-1: LinearizedConstraints::update + setParameters on device (linearized_constraints.cpp:49-189) ----------
 // one thread per (trajectory, stage)
 // n_obs dynamic obstacles (rows 0 .. n_obs-1), then n_static static halfspaces per stage copied as they are (linearized_constraints.cpp:
 // 107-123, `add_halfspaces`), then dummies up to n_lin.  obst_radius == nullptr: guidance mode, every disc has radius 1e-3 + robot_radius
 // (:99, :140); otherwise the `_use_guidance == false` branch (:63-73): obstacle j's own radius + robot_radius, in the projection and in b.
-__global__ void tmpc_linearize_topology_kernel(Dims d, int B, const double *x0, double *params, const double *obst,
-                                               const int *scene_of, const double *state_x, double robot_radius,
-                                               const uint8_t *is_original, int n_obs, const double *obst_radius, const double *stat, int n_static)
+template <class Where>
+__device__ __forceinline__ void linearize_topology_rows(const Where &where, const Dims &d, int B, const double *x0, double *params, const double *obst,
+                                                        const int *scene_of, const double *state_x, double robot_radius,
+                                                        const uint8_t *is_original, int n_obs, const double *obst_radius, const double *stat, int n_static)
 {
 #pragma clang fp contract(off)                                          // the rows too are the mirror's (modules.py::linearized_update) bit for bit: a batch whose rows
                                                                         // were built here solves exactly like the same batch built on the host (tests/test_gpu_obstacles.py)
@@ -133,7 +166,8 @@ __global__ void tmpc_linearize_topology_kernel(Dims d, int B, const double *x0, 
                 }
             }
     }
-    for (int j = 0; j < d.n_lin; j++) {
+    const int n_rows = where.n_lin(d);
+    for (int j = 0; j < n_rows; j++) {
         double a1 = 1.0, a2 = 0.0, bb = dummy_b;                        // _dummy_a1, _dummy_a2
         if (!dummy && j < n_obs) {
             const double ox = ob[((size_t)j * N + (k - 1)) * 2], oy = ob[((size_t)j * N + (k - 1)) * 2 + 1];
@@ -145,8 +179,22 @@ __global__ void tmpc_linearize_topology_kernel(Dims d, int B, const double *x0, 
             const double *hs = stat + (((size_t)sc * N + k) * n_static + (j - n_obs)) * 3;
             a1 = hs[0]; a2 = hs[1]; bb = hs[2];
         }
-        p[ip_lin(d, j, 0)] = a1; p[ip_lin(d, j, 1)] = a2; p[ip_lin(d, j, 2)] = bb;
+        p[where.lin(d, j, 0)] = a1; p[where.lin(d, j, 1)] = a2; p[where.lin(d, j, 2)] = bb;
     }
+}
+__global__ void tmpc_linearize_topology_kernel(Dims d, int B, const double *x0, double *params, const double *obst,
+                                               const int *scene_of, const double *state_x, double robot_radius,
+                                               const uint8_t *is_original, int n_obs, const double *obst_radius, const double *stat, int n_static)
+{
+    linearize_topology_rows(LayoutRows{}, d, B, x0, params, obst, scene_of, state_x, robot_radius, is_original, n_obs, obst_radius, stat, n_static);
+}
+// the same rows into the caller's columns (tmpc_stack_linearize_topology_columns): where.count rows, where.t.col[3 j + w]
+__global__ void tmpc_linearize_topology_columns_kernel(Dims d, int B, const double *x0, double *params, const double *obst,
+                                                       const int *scene_of, const double *state_x, double robot_radius,
+                                                       const uint8_t *is_original, int n_obs, const double *obst_radius, const double *stat, int n_static,
+                                                       ColumnRows where)
+{
+    linearize_topology_rows(where, d, B, x0, params, obst, scene_of, state_x, robot_radius, is_original, n_obs, obst_radius, stat, n_static);
 }
 
 // ---- a5 / f-1: Contouring's road constraints on device (contouring.cpp:181-262, `contouring/add_road_constraints`) ----------------
@@ -289,21 +337,22 @@ __global__ __launch_bounds__(PREP_THREADS) void tmpc_prepare_obstacles_kernel(in
 // ExponentialQuantile(0.5, 1 - risk), evaluated by the HOST (no device logarithm enters).  row_model 1: GaussianConstraints as
 // modules.py::gaussian_set_parameters has it (gaussian_constraints.cpp:22-79): stage 0 (x + 100, y + 100, 0.1, 0.1, 0.05, 0.1), then x, y,
 // major, minor (0 for a DETERMINISTIC obstacle, like the mirror fed by modules.py::prepare_obstacles), risk and the CONFIGURED obstacle radius.  ego_disc_radius / ego_disc_0_offset at every stage.  Nothing else is touched.
-__global__ void tmpc_set_obstacle_parameters_kernel(Dims d, int B, double *params, const double *opos, const double *oshape, const double *oradius,
-                                                    const uint8_t *ogauss, const int *scene_of, const double *state, double robot_radius,
-                                                    double disc_offset, double chi, double risk, double config_radius)
+template <class Where>
+__device__ __forceinline__ void set_obstacle_rows(const Where &where, const Dims &d, int B, double *params, const double *opos, const double *oshape,
+                                                  const double *oradius, const uint8_t *ogauss, const int *scene_of, const double *state,
+                                                  double robot_radius, double disc_offset, double chi, double risk, double config_radius)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = d.N, M = d.M;
+    const int N = d.N, M = where.n_obstacles(d);
     if (e >= B * N * M) return;
     const int j = e % M, k = (e / M) % N, b = e / (M * N);
     const int sc = scene_of[b];
     double *p = params + ((size_t)b * N + k) * d.npar;
-    if (j == 0) { p[ip_disc_radius(d)] = robot_radius; p[ip_disc_offset(d)] = disc_offset; }
+    if (j == 0) { p[where.disc_radius(d)] = robot_radius; p[where.disc_offset(d)] = disc_offset; }
     const double x = state[(size_t)sc * 4], y = state[(size_t)sc * 4 + 1];
     const size_t o = (((size_t)sc * M + j) * N + (k > 0 ? k - 1 : 0));
     const bool gaussian = ogauss[(size_t)sc * M + j] != 0;
-    if (d.row_model == 0) {
+    if (where.row_model(d) == 0) {
         double val[7] = {x + 50.0, y + 50.0, 0.0, 0.0, 0.0, 1.0, 0.1};
         if (k > 0) {
             val[0] = opos[o * 2]; val[1] = opos[o * 2 + 1]; val[2] = oshape[o * 3];
@@ -311,7 +360,7 @@ __global__ void tmpc_set_obstacle_parameters_kernel(Dims d, int B, double *param
             val[6] = oradius[(size_t)sc * M + j];
         }
 #pragma unroll
-        for (int w = 0; w < 7; w++) p[ip_ellipsoid(d, j, w)] = val[w];
+        for (int w = 0; w < 7; w++) p[where.ellipsoid(d, j, w)] = val[w];
     } else {
         double val[6] = {x + 100.0, y + 100.0, 0.1, 0.1, 0.05, 0.1};
         if (k > 0) {
@@ -319,8 +368,21 @@ __global__ void tmpc_set_obstacle_parameters_kernel(Dims d, int B, double *param
             val[4] = risk; val[5] = config_radius;
         }
 #pragma unroll
-        for (int w = 0; w < 6; w++) p[ip_gauss(d, j, w)] = val[w];
+        for (int w = 0; w < 6; w++) p[where.gauss(d, j, w)] = val[w];
     }
+}
+__global__ void tmpc_set_obstacle_parameters_kernel(Dims d, int B, double *params, const double *opos, const double *oshape, const double *oradius,
+                                                    const uint8_t *ogauss, const int *scene_of, const double *state, double robot_radius,
+                                                    double disc_offset, double chi, double risk, double config_radius)
+{
+    set_obstacle_rows(LayoutRows{}, d, B, params, opos, oshape, oradius, ogauss, scene_of, state, robot_radius, disc_offset, chi, risk, config_radius);
+}
+// the same values into the caller's columns (tmpc_stack_set_obstacle_columns): where.count obstacles per scene, row model where.model
+__global__ void tmpc_set_obstacle_columns_kernel(Dims d, int B, double *params, const double *opos, const double *oshape, const double *oradius,
+                                                 const uint8_t *ogauss, const int *scene_of, const double *state, double robot_radius,
+                                                 double disc_offset, double chi, double risk, double config_radius, ColumnRows where)
+{
+    set_obstacle_rows(where, d, B, params, opos, oshape, oradius, ogauss, scene_of, state, robot_radius, disc_offset, chi, risk, config_radius);
 }
 
 // ---- Contouring::update on a whole reference path (contouring.cpp:28-48, setSplineParameters :94-124) ---------------------------------------
@@ -614,10 +676,7 @@ __global__ __launch_bounds__(64) void tmpc_path_velocity_window_kernel(int S, in
 }
 
 // ---- caller-chosen columns of the current batch's parameter rows: the writer for generated solvers, whose column numbers the caller has in the
-// stack's parameter map.  The column list travels by value (at most 128 entries: 516 bytes of kernel arguments).
-constexpr int SCATTER_MAX_COLS = 128;
-struct ScatterCols { int n; int col[SCATTER_MAX_COLS]; };
-
+// stack's parameter map.  The column list (ScatterCols, above) travels by value (at most 128 entries: 516 bytes of kernel arguments).
 // one thread per (entry b, stage k < N, listed column c): params[b][k][col[c]] = values[scene_of[b]][c] (per_stage 0: values [n_scenes][n_cols])
 // or values[scene_of[b]][k][c] (per_stage 1: values [n_scenes][N][n_cols]); an entry whose scene is outside [0, n_scenes) is left untouched.
 // The host has checked every column against npar and the list for duplicates, so no two threads write one address.  Both models' strides.

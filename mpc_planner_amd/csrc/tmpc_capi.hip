@@ -580,6 +580,9 @@ struct Events {
 };
 }  // namespace
 
+// the entry points of include/tmpc_hip_stack.h (the row writers of generated solvers' module stacks) and the checks tmpc_prepare_obstacles shares with them
+#include "tmpc_stack_writers.hpp"
+
 extern "C" {
 
 void tmpc_default_dims(tmpc_dims *d, int32_t N, int32_t S, int32_t n_lin, int32_t M) { tmpc_default_dims_ex(d, N, S, n_lin, M, 0, 0); }
@@ -1287,28 +1290,8 @@ int tmpc_prepare_obstacles(tmpc_handle *h, int32_t n_scenes, int32_t n_slots, in
                            void *d_obstacle_gaussian, void *d_selected)
 {
     TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_prepare_obstacles");
-    if (!h) return TMPC_ERR_INVALID;
-    tmpc_obstacle_options o{};                                        // NULL: the defaults (deterministic, no passes, no distance filter)
-    o.size = sizeof(o); o.noise = 0.3;
-    if (!read_options(h, "tmpc_prepare_obstacles", "tmpc_obstacle_options", options, o)) return TMPC_ERR_INVALID;
-    if (n_scenes <= 0) { h->err = "tmpc_prepare_obstacles: n_scenes must be positive"; return TMPC_ERR_INVALID; }
-    if (n_slots < 0 || n_slots > tmpc::PREP_MAX_SLOTS) { h->err = "tmpc_prepare_obstacles: 0 <= n_slots <= 1024"; return TMPC_ERR_INVALID; }
-    if (max_obstacles <= 0 || max_obstacles > 4096) { h->err = "tmpc_prepare_obstacles: 1 <= max_obstacles <= 4096"; return TMPC_ERR_INVALID; }
-    if (!d_count || !d_state || !d_raw_pos || !d_raw_radius) { h->err = "tmpc_prepare_obstacles: NULL input (d_count, d_state, d_raw_pos, d_raw_radius)"; return TMPC_ERR_INVALID; }
-    if ((d_raw_vel == nullptr) == (d_raw_pred == nullptr)) { h->err = "tmpc_prepare_obstacles: exactly one of d_raw_vel and d_raw_pred"; return TMPC_ERR_INVALID; }
-    if (!d_obstacle_pos || !d_obstacle_shape || !d_obstacle_radius || !d_obstacle_gaussian || !d_selected) {
-        h->err = "tmpc_prepare_obstacles: NULL output buffer"; return TMPC_ERR_INVALID;
-    }
-    if (o.propagate_passes < 0 || o.propagate_passes > 2) { h->err = "tmpc_prepare_obstacles: propagate_passes is 0, 1 or 2"; return TMPC_ERR_INVALID; }
-    if ((o.probabilistic != 0 && o.probabilistic != 1) || !(o.noise >= 0.0)) { h->err = "tmpc_prepare_obstacles: probabilistic is 0 or 1, noise >= 0"; return TMPC_ERR_INVALID; }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(tmpc::tmpc_prepare_obstacles_kernel, dim3((unsigned)n_scenes), dim3(tmpc::PREP_THREADS), (size_t)max_obstacles * sizeof(int), h->stream,
-                       h->d.N, h->d.dt, n_slots, max_obstacles, (const int *)d_count, (const double *)d_state, (const double *)d_raw_pos,
-                       (const double *)d_raw_radius, (const double *)d_raw_vel, (const double *)d_raw_pred, o.probabilistic, o.noise, o.propagate_passes,
-                       o.max_obstacle_distance, (double *)d_obstacle_pos, (double *)d_obstacle_shape, (double *)d_obstacle_radius,
-                       (uint8_t *)d_obstacle_gaussian, (int *)d_selected);
-    TMPC_HIP_CHECK(h, hipGetLastError());
-    return TMPC_OK;
+    return prepare_obstacles_checked(h, "tmpc_prepare_obstacles", n_scenes, n_slots, max_obstacles, d_count, d_state, d_raw_pos, d_raw_radius, d_raw_vel,
+                                     d_raw_pred, options, d_obstacle_pos, d_obstacle_shape, d_obstacle_radius, d_obstacle_gaussian, d_selected);    // csrc/tmpc_stack_writers.hpp
 }
 
 int tmpc_set_obstacle_parameters(tmpc_handle *h, const void *d_obstacle_pos, const void *d_obstacle_shape, const void *d_obstacle_radius,
