@@ -6,6 +6,7 @@ Host-side mirror of the reference's solver / module interface for this one hot p
   scenes.py      -- deterministic synthetic Jackal scenes
   solver.py      -- ctypes binding of the C-ABI (include/tmpc_hip.h) + batched optimize()
   stack_writers.py -- ctypes binding of include/tmpc_hip_stack.h: obstacle and topology rows of generated solvers, by column
+  stack_env.py   -- ctypes binding of include/tmpc_hip_stack_env.h: path window, road and decomp rows of generated solvers, by column
   csrc/          -- HIP kernels (gfx950) and the C-ABI shim
 """
 __all__ = ["parameters", "modules", "scenes"]

@@ -4,10 +4,10 @@ from . import library as L
 from . import plugin as P
 
 
-def settings(N=20, max_obstacles=8, num_segments=5):
-    return {"N": N, "n_discs": 1, "max_obstacles": max_obstacles, "linearized_constraints": {"add_halfspaces": 0},
+def settings(N=20, max_obstacles=8, num_segments=5, add_halfspaces=0, max_constraints=12):
+    return {"N": N, "n_discs": 1, "max_obstacles": max_obstacles, "linearized_constraints": {"add_halfspaces": add_halfspaces},
             "contouring": {"num_segments": num_segments, "dynamic_velocity_reference": False},
-            "decomp": {"range": 2.0, "max_constraints": 12}}
+            "decomp": {"range": 2.0, "max_constraints": max_constraints}}
 
 
 def _base(st, slack=False):

@@ -5,7 +5,10 @@
  * whole paths along the warm start of each scene's main solver, one polygon per segment -- and setParameters() enqueues
  * tmpc_set_halfspace_rows, which writes the decomp rows and ego_disc_0_offset of the handle's current batch: what DecompConstraints::update /
  * setParameters do per scene on the host (decomp_constraints.cpp:52-189), bit for bit.  The paths are device buffers in
- * tmpc_fit_path's layout, e.g. BatchedPathTracking::paths() / pathCounts() / pathLengths(), and s0 its closestS().  For callers of the C-ABI
+ * tmpc_fit_path's layout, e.g. BatchedPathTracking::paths() / pathCounts() / pathLengths(), and s0 its closestS().  Column mode (setColumns):
+ * for a handle of a GENERATED library, where those two entries refuse -- the same steps through include/tmpc_hip_stack_env.h
+ * (tmpc_stack_decomp_halfspaces, tmpc_stack_set_halfspace_columns), the rows written into the columns of the stack's parameter map; without
+ * setColumns() nothing changes.  For callers of the C-ABI
  * (include/tmpc_hip.h) that keep a launch of many scenes on the device; needs the HIP runtime header (compile with -D__HIP_PLATFORM_AMD__
  * and the ROCm include directory).  Everything is enqueued on the handle's stream; setCostmaps() and setParameters() wait for their own
  * uploads (the staging memory is their own), not for the kernels.
@@ -16,6 +19,8 @@
 #include <mpc_planner_modules/free_space.h>
 #include <mpc_planner_solver/device_plumbing.h>
 #include <mpc_planner_types/costmap.h>
+
+#include "tmpc_hip_stack_env.h"
 
 namespace MPCPlanner
 {
@@ -59,6 +64,15 @@ namespace MPCPlanner
             _map_changed = true;
         }
 
+        /* Column mode, for a handle of a GENERATED library: decomp_cols = ego_disc_0_offset, then disc_0_decomp_{r}_{a1, a2, b} for r = 0 .. n_rows - 1,
+         * the columns of the stack's parameter map (parameter_map.yaml).  From then on update() and setParameters() use
+         * tmpc_stack_decomp_halfspaces and tmpc_stack_set_halfspace_columns. */
+        void setColumns(const std::vector<int32_t> &decomp_cols)
+        {
+            if ((int)decomp_cols.size() != 1 + 3 * _n_rows) fail("setColumns: 1 + 3 n_rows columns");
+            _columns = true; _decomp_cols = decomp_cols;
+        }
+
         /* One tick of DecompConstraints::update for every scene of the handle's CURRENT batch (tmpc_set_batch* first: the speeds are read from
          * its warm start).  d_main_of i32 [n_scenes]: the batch entry of each scene's main solver; d_path / d_path_count / d_path_length: the
          * whole paths, rows n_seg_max apart; d_s0, d_state_x f64 [n_scenes].  All device pointers.  Enqueued; nothing is read back. */
@@ -69,15 +83,20 @@ namespace MPCPlanner
                 if (tmpc_costmap_points(_h, _Q, _size_x, _size_y, _d_cost, _d_origin, _resolution, _P, _d_points, _d_count, _d_overflow)) fail(tmpc_last_error(_h));
                 _map_changed = false;
             }
-            if (tmpc_decomp_halfspaces(_h, d_main_of, _Q, n_seg_max, d_path, d_path_count, d_path_length, d_s0, d_state_x, _d_points, _d_count, _P, _range, _n_rows,
-                                       _d_rows, _d_row_count, _d_status)) fail(tmpc_last_error(_h));
+            if ((_columns ? tmpc_stack_decomp_halfspaces : tmpc_decomp_halfspaces)(_h, d_main_of, _Q, n_seg_max, d_path, d_path_count, d_path_length, d_s0, d_state_x, _d_points,
+                                                                                   _d_count, _P, _range, _n_rows, _d_rows, _d_row_count, _d_status)) fail(tmpc_last_error(_h));
         }
 
         /* The decomp rows (slack rows first_row .. first_row + n_rows - 1) and ego_disc_0_offset of the handle's current batch: scene_of[b] =
-         * scene of batch entry b, outside [0, n_scenes): the entry is left alone. */
+         * scene of batch entry b, outside [0, n_scenes): the entry is left alone.  Column mode: into decomp_cols, which name the rows (first_row is
+         * not used and must be 0). */
         void setParameters(const std::vector<int> &scene_of, double disc_offset = 0., int first_row = 0)
         {
-            if (tmpc_set_halfspace_rows(_h, _d_rows, _n_rows, first_row, uploadSceneOf(scene_of), _Q, disc_offset)) fail(tmpc_last_error(_h));
+            if (_columns && first_row != 0) fail("setParameters: the columns name the rows (first_row = 0)");
+            const void *d_scene_of = uploadSceneOf(scene_of);
+            const int rc = _columns ? tmpc_stack_set_halfspace_columns(_h, _decomp_cols.data(), _n_rows, _d_rows, d_scene_of, _Q, disc_offset)
+                                    : tmpc_set_halfspace_rows(_h, _d_rows, _n_rows, first_row, d_scene_of, _Q, disc_offset);
+            if (rc) fail(tmpc_last_error(_h));
         }
 
         /* device buffers, valid after update(): points [n_scenes][n_pts_max][2], their count (i32) and overflow flag (u8) per scene, the rows
@@ -93,6 +112,8 @@ namespace MPCPlanner
         int _Q, _size_x, _size_y, _P, _N, _n_rows;
         double _range, _resolution{0.};
         bool _map_changed{false};
+        bool _columns{false};
+        std::vector<int32_t> _decomp_cols;
         void *_d_cost{nullptr}, *_d_origin{nullptr}, *_d_points{nullptr}, *_d_count{nullptr}, *_d_overflow{nullptr};
         void *_d_rows{nullptr}, *_d_row_count{nullptr}, *_d_status{nullptr};
     };

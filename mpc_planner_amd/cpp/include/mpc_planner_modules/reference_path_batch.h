@@ -9,7 +9,9 @@
  * every path, setWaypoints() also fits the velocity profiles (PathReferenceVelocity::onDataReceived) and setVelocityParameters() enqueues
  * tmpc_path_velocity_window and tmpc_scatter_parameters: the spline_v columns of a generated stack, and referenceVelocity() for the guidance
  * planner (path_reference_velocity.cpp:59-95, guidance_constraints.cpp:91-94).  In a generated solver, whose handle has no S, track() passes the
- * twin's S as tmpc_path_options::window_segments and setSplineParameters() takes the place of setParameters().  For callers of the C-ABI
+ * twin's S as tmpc_path_options::window_segments; after setColumns() -- the 9 S spline columns of the stack's parameter map -- setParameters()
+ * and roadHalfspaces() go through include/tmpc_hip_stack_env.h (tmpc_stack_set_path_columns, tmpc_stack_road_halfspaces), the same kernels with
+ * the columns named by the caller; without setColumns() nothing changes.  For callers of the C-ABI
  * (include/tmpc_hip.h) that keep a launch of many scenes on the device; needs the HIP runtime header (compile with -D__HIP_PLATFORM_AMD__
  * and the ROCm include directory).  Everything is enqueued on the handle's stream; setPaths() and setParameters() wait for their own uploads
  * (the staging memory is their own), not for the kernels.
@@ -19,6 +21,8 @@
 
 #include <mpc_planner_modules/reference_path.h>
 #include <mpc_planner_solver/device_plumbing.h>
+
+#include "tmpc_hip_stack_env.h"
 
 namespace MPCPlanner
 {
@@ -151,13 +155,40 @@ namespace MPCPlanner
                                 _d_reached)) fail(tmpc_last_error(_h));
         }
 
+        /* Column mode, for a handle of a GENERATED library: path_cols = the 9 S columns of the stack's parameter map (parameter_map.yaml) in the
+         * window's order, spline_x{i}_a .. _d, spline_y{i}_a .. _d, spline{i}_start for i = 0 .. S - 1.  From then on setParameters() and
+         * roadHalfspaces() use tmpc_stack_set_path_columns and tmpc_stack_road_halfspaces. */
+        void setColumns(const std::vector<int32_t> &path_cols)
+        {
+            if ((int)path_cols.size() != 9 * _S) fail("setColumns: 9 S columns");
+            _columns = true; _path_cols = path_cols;
+        }
+
         /* The spline columns of the handle's CURRENT batch (tmpc_set_batch* first): scene_of[b] = scene of batch entry b, outside [0, n_scenes):
          * the entry is left alone.  d_state != nullptr (device, [B][nx], the layout tmpc_warmstart reads): its `spline` entry becomes the
          * scene's closest_s -- before tmpc_warmstart(d_state) the solve starts from the fresh value, after it from the previous tick's, as in
-         * the reference (planner.cpp:81-96). */
+         * the reference (planner.cpp:81-96).  Column mode: into path_cols (tmpc_stack_set_path_columns); otherwise tmpc_set_path_parameters. */
         void setParameters(const std::vector<int> &scene_of, void *d_state = nullptr)
         {
-            if (tmpc_set_path_parameters(_h, _d_window, uploadSceneOf(scene_of), _Q, d_state ? _d_closest_s : nullptr, d_state)) fail(tmpc_last_error(_h));
+            const void *d_scene_of = uploadSceneOf(scene_of);
+            const int rc = _columns ? tmpc_stack_set_path_columns(_h, _path_cols.data(), _S, _d_window, d_scene_of, _Q, d_state ? _d_closest_s : nullptr, d_state)
+                                    : tmpc_set_path_parameters(_h, _d_window, d_scene_of, _Q, d_state ? _d_closest_s : nullptr, d_state);
+            if (rc) fail(tmpc_last_error(_h));
+        }
+
+        /* Contouring's road rows (contouring.cpp:181-262) for every scene, after setParameters(): rows first_row, first_row + 1 of
+         * d_static_halfspaces f64 [n_scenes][N][n_static][3] (device; what tmpc_linearize_topology_ex / tmpc_stack_linearize_topology_columns read)
+         * from the warm start and the path window of batch entry d_main_of[q] (i32 [n_scenes], device).  from_bounds: bounds mode on
+         * boundWindow() (the twin was built with_bounds), offset_first = offset_second = the robot radius; otherwise centreline mode.  Column
+         * mode: tmpc_stack_road_halfspaces; otherwise tmpc_road_halfspaces.  Enqueued. */
+        void roadHalfspaces(const void *d_main_of, double offset_first, double offset_second, void *d_static_halfspaces, int n_static, int first_row = 0,
+                            bool from_bounds = false)
+        {
+            if (from_bounds && !_with_bounds) fail("roadHalfspaces: from_bounds needs a twin with bounds");
+            const void *bounds = from_bounds ? _d_bound_window : nullptr;
+            const int rc = _columns ? tmpc_stack_road_halfspaces(_h, _path_cols.data(), _S, d_main_of, _Q, bounds, offset_first, offset_second, d_static_halfspaces, n_static, first_row)
+                                    : tmpc_road_halfspaces(_h, d_main_of, _Q, bounds, offset_first, offset_second, d_static_halfspaces, n_static, first_row);
+            if (rc) fail(tmpc_last_error(_h));
         }
 
         /* The same columns in a GENERATED solver, where tmpc_set_path_parameters refuses: cols = the 9 S columns of the stack's parameter map in
@@ -203,6 +234,8 @@ namespace MPCPlanner
     private:
         int _Q, _R, _S;
         bool _with_bounds, _with_velocity{false};
+        bool _columns{false};
+        std::vector<int32_t> _path_cols;
         void *_d_path{nullptr}, *_d_count{nullptr}, *_d_length{nullptr}, *_d_segment{nullptr}, *_d_closest_s{nullptr}, *_d_window{nullptr}, *_d_reached{nullptr};
         void *_d_bounds{nullptr}, *_d_bound_window{nullptr};
         void *_d_waypoints{nullptr}, *_d_status{nullptr}, *_d_road_width{nullptr};       /* setWaypoints(): allocated on its first call */

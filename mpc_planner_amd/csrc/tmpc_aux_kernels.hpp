@@ -112,6 +112,39 @@ struct ColumnRows {
     __device__ __forceinline__ int gauss(const Dims &, int j, int w) const { return t.col[2 + 6 * j + w]; }
 };
 
+// The sibling pair for the static environment (include/tmpc_hip_stack_env.h): the path window and the slack (decomp) rows.  The layout side
+// carries the first slack row of the call; the column side names every row, so it has none.
+struct LayoutEnvRows {
+    int first_row;
+    __device__ __forceinline__ int n_segments(const Dims &d) const { return d.S; }
+    __device__ __forceinline__ int spline(const Dims &d, int i, int c) const { return ip_spline(d, i, c); }
+    __device__ __forceinline__ int slk(const Dims &d, int r, int c) const { return ip_slk(d, first_row + r, c); }
+    __device__ __forceinline__ int disc_offset(const Dims &d) const { return ip_disc_offset(d); }
+    // the centreline rows of segment i: its eight coefficients (ax bx cx dx ay by cy dy) are contiguous in the layout
+    __device__ __forceinline__ void centreline_rows(const Dims &d, const double *p, int i, double t, double off_first, double off_second, double *row) const
+    {
+        tmpc_arith::road_rows_centreline(p + ip_spline(d, i, 0), t, off_first, off_second, row);
+    }
+};
+// path: col[9 i + c] = spline_x{i}_{a,b,c,d}, spline_y{i}_{a,b,c,d}, spline{i}_start of segment i < count.  Halfspace rows: col[0] =
+// ego_disc_0_offset, col[1 + 3 r + c] = (a1, a2, b) of row r < count.
+struct ColumnEnvRows {
+    ScatterCols t;
+    int count;
+    __device__ __forceinline__ int n_segments(const Dims &) const { return count; }
+    __device__ __forceinline__ int spline(const Dims &, int i, int c) const { return t.col[9 * i + c]; }
+    __device__ __forceinline__ int slk(const Dims &, int r, int c) const { return t.col[1 + 3 * r + c]; }
+    __device__ __forceinline__ int disc_offset(const Dims &) const { return t.col[0]; }
+    // the columns need not be contiguous: gathered into a local array in the layout's order, then the same call
+    __device__ __forceinline__ void centreline_rows(const Dims &, const double *p, int i, double s, double off_first, double off_second, double *row) const
+    {
+        double local[8];
+#pragma unroll
+        for (int c = 0; c < 8; c++) local[c] = p[t.col[9 * i + c]];
+        tmpc_arith::road_rows_centreline(local, s, off_first, off_second, row);
+    }
+};
+
 // ---- f-1: LinearizedConstraints::update + setParameters on device (linearized_constraints.cpp:49-189) ----------
 // one thread per (trajectory, stage)
 // n_obs dynamic obstacles (rows 0 .. n_obs-1), then n_static static halfspaces per stage copied as they are (linearized_constraints.cpp:
@@ -208,12 +241,16 @@ __global__ void tmpc_linearize_topology_columns_kernel(Dims d, int B, const doub
 // independent modules.py::road_halfspaces(_from_bounds).  The cubic is that of segment i = max{j : start_j <= s} (0 below the first knot; the
 // last segment's cubic continues beyond the window).
 // Rows first_row, first_row + 1 of stat [n_scenes][N][n_static][3] -- what tmpc_linearize_topology_kernel copies -- and nothing else.
-__global__ void tmpc_road_halfspaces_kernel(Dims d, int B, int n_scenes, const double *x0, const double *params, const int *main_of,
-                                            const double *bounds, double off_first, double off_second, double *stat, int n_static, int first_row)
+// Where: the path window is read at the layout's ip_spline (LayoutEnvRows) or at the caller's columns (ColumnEnvRows, where.count segments;
+// the eight coefficients are gathered into a local array in the layout's order before the same tmpc_arith call).
+template <class Where>
+__device__ __forceinline__ void road_halfspace_rows(const Where &where, const Dims &d, int B, int n_scenes, const double *x0, const double *params,
+                                                    const int *main_of, const double *bounds, double off_first, double off_second, double *stat,
+                                                    int n_static, int first_row)
 {
 #pragma clang fp contract(off)
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = d.N, S = d.S;
+    const int N = d.N, S = where.n_segments(d);
     if (e >= n_scenes * N) return;
     const int sc = e / N, k = e - sc * N;
     const int b = main_of[sc];
@@ -221,15 +258,27 @@ __global__ void tmpc_road_halfspaces_kernel(Dims d, int B, int n_scenes, const d
     const double *p = params + ((size_t)b * N + k) * d.npar;
     const double s = x0[((size_t)b * (N + 1) + k) * ext_nv(d) + ZS];
     int i = 0;
-    for (int j = 0; j < S; j++) if (p[ip_spline(d, j, 8)] <= s) i = j;      // (a comparison, nothing is rounded: the kernel's own)
-    const double t = s - p[ip_spline(d, i, 8)];
+    for (int j = 0; j < S; j++) if (p[where.spline(d, j, 8)] <= s) i = j;   // (a comparison, nothing is rounded: the kernel's own)
+    const double t = s - p[where.spline(d, i, 8)];
     double *row = stat + (((size_t)sc * N + k) * n_static + first_row) * 3;
-    if (bounds == nullptr) tmpc_arith::road_rows_centreline(p + ip_spline(d, i, 0), t, off_first, off_second, row);
+    if (bounds == nullptr) where.centreline_rows(d, p, i, t, off_first, off_second, row);
     else {
         const double *bl = bounds + (((size_t)sc * 2 + 0) * S + i) * 8, *br = bounds + (((size_t)sc * 2 + 1) * S + i) * 8;
         tmpc_arith::road_row_left_bound(bl, t, off_first, row);
         tmpc_arith::road_row_right_bound(br, t, off_second, row + 3);
     }
+}
+__global__ void tmpc_road_halfspaces_kernel(Dims d, int B, int n_scenes, const double *x0, const double *params, const int *main_of,
+                                            const double *bounds, double off_first, double off_second, double *stat, int n_static, int first_row)
+{
+    road_halfspace_rows(LayoutEnvRows{0}, d, B, n_scenes, x0, params, main_of, bounds, off_first, off_second, stat, n_static, first_row);
+}
+// the same rows from the path window in the caller's columns (tmpc_stack_road_halfspaces)
+__global__ void tmpc_road_halfspaces_columns_kernel(Dims d, int B, int n_scenes, const double *x0, const double *params, const int *main_of,
+                                                    const double *bounds, double off_first, double off_second, double *stat, int n_static, int first_row,
+                                                    ColumnEnvRows where)
+{
+    road_halfspace_rows(where, d, B, n_scenes, x0, params, main_of, bounds, off_first, off_second, stat, n_static, first_row);
 }
 
 // ---- obstacle preparation on device (mpc_planner/src/data_preparation.cpp; what a wrapper's obstacle callback does before solveMPC) -----------
@@ -472,11 +521,12 @@ __global__ __launch_bounds__(64) void tmpc_track_path_kernel(int S, int n_seg_ma
 // one thread per (trajectory, stage, window slot): the nine columns ip_spline(d, slot, 0..8) of stage k < N of entry b from window
 // [n_scenes][S][9] of scene scene_of[b]; an entry whose scene is outside [0, n_scenes) is left untouched.  With closest_s and state
 // [B][nx]: state[b][spline] = closest_s[scene] (state.set("spline", closest_s), :42).  Nothing else is written; both models' strides.
-__global__ void tmpc_set_path_parameters_kernel(Dims d, int B, double *params, const double *window, const int *scene_of, int n_scenes,
-                                                const double *closest_s, double *state)
+template <class Where>
+__device__ __forceinline__ void set_path_rows(const Where &where, const Dims &d, int B, double *params, const double *window, const int *scene_of,
+                                              int n_scenes, const double *closest_s, double *state)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = d.N, S = d.S;
+    const int N = d.N, S = where.n_segments(d);
     if (e >= B * N * S) return;
     const int w = e % S, k = (e / S) % N, b = e / (S * N);
     const int sc = scene_of[b];
@@ -484,8 +534,19 @@ __global__ void tmpc_set_path_parameters_kernel(Dims d, int B, double *params, c
     double *p = params + ((size_t)b * N + k) * d.npar;
     const double *src = window + ((size_t)sc * S + w) * 9;
 #pragma unroll
-    for (int c = 0; c < 9; c++) p[ip_spline(d, w, c)] = src[c];
+    for (int c = 0; c < 9; c++) p[where.spline(d, w, c)] = src[c];
     if (k == 0 && w == 0 && closest_s && state) state[(size_t)b * ext_nx(d) + (ZS - NU)] = closest_s[sc];
+}
+__global__ void tmpc_set_path_parameters_kernel(Dims d, int B, double *params, const double *window, const int *scene_of, int n_scenes,
+                                                const double *closest_s, double *state)
+{
+    set_path_rows(LayoutEnvRows{0}, d, B, params, window, scene_of, n_scenes, closest_s, state);
+}
+// the same window into the caller's columns (tmpc_stack_set_path_columns): where.count segments, where.t.col[9 i + c]
+__global__ void tmpc_set_path_columns_kernel(Dims d, int B, double *params, const double *window, const int *scene_of, int n_scenes,
+                                             const double *closest_s, double *state, ColumnEnvRows where)
+{
+    set_path_rows(where, d, B, params, window, scene_of, n_scenes, closest_s, state);
 }
 
 // ---- waypoints -> cubic segments: Contouring::onDataReceived (contouring.cpp:126-157), PathReferenceVelocity::onDataReceived -----------------
@@ -1583,8 +1644,9 @@ __global__ __launch_bounds__(DECOMP_THREADS) void tmpc_decomp_halfspaces_kernel(
 // DecompConstraints::setParameters (:150-189) from tmpc_decomp_halfspaces_kernel's rows: one thread per (trajectory, stage, row): row r of stage k
 // of scene scene_of[b] into slack row first_row + r of entry b, and ego_disc_0_offset; an entry whose scene is outside [0, n_scenes) is left
 // untouched.  Nothing else is written.
-__global__ void tmpc_set_halfspace_rows_kernel(Dims d, int B, double *params, const double *rows, int n_rows, int first_row, const int *scene_of,
-                                               int n_scenes, double disc_offset)
+template <class Where>
+__device__ __forceinline__ void set_halfspace_rows(const Where &where, const Dims &d, int B, double *params, const double *rows, int n_rows,
+                                                   const int *scene_of, int n_scenes, double disc_offset)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const int N = d.N;
@@ -1595,8 +1657,19 @@ __global__ void tmpc_set_halfspace_rows_kernel(Dims d, int B, double *params, co
     double *p = params + ((size_t)b * N + k) * d.npar;
     const double *src = rows + (((size_t)sc * N + k) * n_rows + r) * 3;
 #pragma unroll
-    for (int c = 0; c < 3; c++) p[ip_slk(d, first_row + r, c)] = src[c];
-    if (r == 0) p[ip_disc_offset(d)] = disc_offset;
+    for (int c = 0; c < 3; c++) p[where.slk(d, r, c)] = src[c];
+    if (r == 0) p[where.disc_offset(d)] = disc_offset;
+}
+__global__ void tmpc_set_halfspace_rows_kernel(Dims d, int B, double *params, const double *rows, int n_rows, int first_row, const int *scene_of,
+                                               int n_scenes, double disc_offset)
+{
+    set_halfspace_rows(LayoutEnvRows{first_row}, d, B, params, rows, n_rows, scene_of, n_scenes, disc_offset);
+}
+// the same rows into the caller's columns (tmpc_stack_set_halfspace_columns): where.t.col[0] the disc offset, where.t.col[1 + 3 r + c] row r
+__global__ void tmpc_set_halfspace_columns_kernel(Dims d, int B, double *params, const double *rows, int n_rows, const int *scene_of, int n_scenes,
+                                                  double disc_offset, ColumnEnvRows where)
+{
+    set_halfspace_rows(where, d, B, params, rows, n_rows, scene_of, n_scenes, disc_offset);
 }
 
 // ---- f-2: cross-tick state on device ------------------------------------------------------------------------------

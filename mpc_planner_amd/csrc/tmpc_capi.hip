@@ -582,6 +582,8 @@ struct Events {
 
 // the entry points of include/tmpc_hip_stack.h (the row writers of generated solvers' module stacks) and the checks tmpc_prepare_obstacles shares with them
 #include "tmpc_stack_writers.hpp"
+// the entry points of include/tmpc_hip_stack_env.h (path window, road and decomp rows of such stacks) and the checks tmpc_decomp_halfspaces shares with them
+#include "tmpc_stack_env.hpp"
 
 extern "C" {
 
@@ -1455,26 +1457,8 @@ int tmpc_decomp_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scen
                            int32_t n_pts_max, double range, int32_t n_rows, void *d_rows, void *d_row_count, void *d_status)
 {
     TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_decomp_halfspaces");
-    if (!h) return TMPC_ERR_INVALID;
-    if (h->B <= 0 || !h->x0) { h->err = "tmpc_decomp_halfspaces: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
-    if (n_scenes <= 0) { h->err = "tmpc_decomp_halfspaces: n_scenes must be positive"; return TMPC_ERR_INVALID; }
-    if (n_seg_max < 1 || n_seg_max > tmpc::PATH_MAX_SEGMENTS) { h->err = "tmpc_decomp_halfspaces: 1 <= n_seg_max <= 1024"; return TMPC_ERR_INVALID; }
-    if (n_pts_max < 1 || n_pts_max > tmpc::DECOMP_MAX_POINTS) { h->err = "tmpc_decomp_halfspaces: 1 <= n_pts_max <= 16384"; return TMPC_ERR_INVALID; }
-    if (n_rows < 1 || n_rows > tmpc::DECOMP_MAX_ROWS) { h->err = "tmpc_decomp_halfspaces: 1 <= n_rows <= 64"; return TMPC_ERR_INVALID; }
-    if (!(range >= 0.0) || !(range < __builtin_huge_val())) { h->err = "tmpc_decomp_halfspaces: range must be finite and not negative"; return TMPC_ERR_INVALID; }
-    if (!d_main_of || !d_path || !d_path_count || !d_path_length || !d_s0 || !d_state_x || !d_points || !d_count) {
-        h->err = "tmpc_decomp_halfspaces: NULL input (d_main_of, d_path, d_path_count, d_path_length, d_s0, d_state_x, d_points, d_count)"; return TMPC_ERR_INVALID;
-    }
-    if (!d_rows || !d_row_count || !d_status) { h->err = "tmpc_decomp_halfspaces: NULL output (d_rows, d_row_count, d_status)"; return TMPC_ERR_INVALID; }
-    const int64_t n = (int64_t)n_scenes * h->d.N;
-    if (n > 0x7fffffff) { h->err = "tmpc_decomp_halfspaces: n_scenes x N too large"; return TMPC_ERR_INVALID; }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(tmpc::tmpc_decomp_halfspaces_kernel, dim3((unsigned)n), dim3(tmpc::DECOMP_THREADS), 0, h->stream, h->d, h->B, n_scenes, h->x0,
-                       (const int *)d_main_of, n_seg_max, (const double *)d_path, (const int *)d_path_count, (const double *)d_path_length,
-                       (const double *)d_s0, (const double *)d_state_x, (const double *)d_points, (const int *)d_count, n_pts_max, range, n_rows,
-                       (double *)d_rows, (int *)d_row_count, (uint8_t *)d_status);
-    TMPC_HIP_CHECK(h, hipGetLastError());
-    return TMPC_OK;
+    return decomp_halfspaces_checked(h, "tmpc_decomp_halfspaces", d_main_of, n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_s0, d_state_x,
+                                     d_points, d_count, n_pts_max, range, n_rows, d_rows, d_row_count, d_status);                              // csrc/tmpc_stack_env.hpp
 }
 
 int tmpc_set_halfspace_rows(tmpc_handle *h, const void *d_rows, int32_t n_rows, int32_t first_row, const void *d_scene_of, int32_t n_scenes,

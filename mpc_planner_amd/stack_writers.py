@@ -11,8 +11,8 @@ of the stack's parameter map -- on the library a BatchedSolver already loaded:
     tcols = topology_columns(meta["parameter_map"], 5)
     w.prepare_obstacles(...); w.set_obstacle_columns(ocols, 1, 5, ...); w.linearize_topology_columns(tcols, ...); s.solve()
 
-The same calls work on a hand-written shape with scenes.make_scene(...)["pm"]._params as the map.  Not covered for generated stacks: the
-road, decomp and scenario rows, and the path writer."""
+The same calls work on a hand-written shape with scenes.make_scene(...)["pm"]._params as the map.  The path window, the road rows and the decomp
+rows of such stacks: stack_env.py.  Not covered for generated stacks: the scenario rows."""
 import ctypes as C
 
 import numpy as np
