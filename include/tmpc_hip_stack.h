@@ -17,7 +17,7 @@
  *   tmpc_guidance_plan -> tmpc_warmstart -> tmpc_sample_guidance -> tmpc_init_with_guidance -> tmpc_stack_prepare_obstacles
  *   -> tmpc_stack_set_obstacle_columns -> tmpc_stack_linearize_topology_columns -> tmpc_solve -> tmpc_guidance_decide
  * (the path side: tmpc_track_path with window_segments, tmpc_path_velocity_window, tmpc_scatter_parameters).
- * The path window, the road rows and the decomp rows of such stacks: include/tmpc_hip_stack_env.h.  Not covered for generated stacks: the scenario rows.
+ * The path window, the road rows and the decomp rows of such stacks: include/tmpc_hip_stack_env.h; their scenario rows: include/tmpc_hip_stack_scenario.h.
  */
 #ifndef TMPC_HIP_STACK_H
 #define TMPC_HIP_STACK_H

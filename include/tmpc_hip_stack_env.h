@@ -16,7 +16,7 @@
  *   tmpc_warmstart -> tmpc_track_path (window_segments) -> tmpc_stack_set_path_columns -> tmpc_stack_prepare_obstacles
  *   -> tmpc_stack_set_obstacle_columns -> tmpc_stack_road_halfspaces -> tmpc_stack_linearize_topology_columns -> tmpc_costmap_points
  *   -> tmpc_stack_decomp_halfspaces -> tmpc_stack_set_halfspace_columns -> tmpc_solve
- * Not covered for generated stacks: the scenario rows (tmpc_scenario_halfspaces, tmpc_scenario_support).
+ * The scenario rows of such stacks (tmpc_scenario_halfspaces, tmpc_scenario_support): the fourth header, tmpc_hip_stack_scenario.h.
  */
 #ifndef TMPC_HIP_STACK_ENV_H
 #define TMPC_HIP_STACK_ENV_H

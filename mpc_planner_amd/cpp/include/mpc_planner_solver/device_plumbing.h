@@ -1,4 +1,4 @@
-/* mpc_planner_solver/device_plumbing.h -- what the batched twins (mpc_planner/data_preparation_batch.h, mpc_planner_modules/reference_path_batch.h, mpc_planner_modules/free_space_batch.h, mpc_planner_modules/guidance_handoff_batch.h)
+/* mpc_planner_solver/device_plumbing.h -- what the batched twins (mpc_planner/data_preparation_batch.h, mpc_planner_modules/reference_path_batch.h, mpc_planner_modules/free_space_batch.h, mpc_planner_modules/guidance_handoff_batch.h, mpc_planner_modules/scenario_rows_batch.h)
  * share: device allocation, host-to-device copies on the handle's stream, the scene_of upload.  A failure prints "<class name>: <what>" on
  * stderr and exits.  Needs the HIP runtime header (compile with -D__HIP_PLATFORM_AMD__ and the ROCm include directory). */
 #ifndef MPC_DEVICE_PLUMBING_HIP_H

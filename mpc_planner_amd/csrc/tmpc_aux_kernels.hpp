@@ -1091,8 +1091,11 @@ __device__ __forceinline__ bool poly_frac_alive(const PolyFrac &w) { return w.nh
 #else
 #define POLY_T(n) do { } while (0)
 #endif
-// one (trajectory, stage) = `unit` by one workgroup of 256 threads
-__device__ __forceinline__ void poly_stage(int unit, const Dims &d, int B, const double *x0, double *params, const double *samples, int n_pts,
+// one (trajectory, stage) = `unit` by one workgroup of 256 threads.  Where: the rows and ego_disc_0_offset go to the layout's ip_slk / ip_disc_offset
+// (LayoutEnvRows{0}) or to the caller's columns (ColumnEnvRows, where.count = n_rows; include/tmpc_hip_stack_scenario.h) -- every write of a
+// parameter, and nothing else, goes through it.
+template <class Where>
+__device__ __forceinline__ void poly_stage(const Where &where, int unit, const Dims &d, int B, const double *x0, double *params, const double *samples, int n_pts,
                                            int n_rows, const int *scene_of, const double *state_x, double radius, double disc_offset,
                                            int *row_sample, int cap, int *overflow, int *empty_stages, const unsigned char *discard, int n_scen)
 {
@@ -1112,9 +1115,9 @@ __device__ __forceinline__ void poly_stage(int unit, const Dims &d, int B, const
     double *p = params + ((size_t)b * N + k) * d.npar;
     const int tid = threadIdx.x;
     int *which = row_sample + (size_t)unit * n_rows;                  // the sample behind each row (-1: dummy), for tmpc_scenario_support
-    if (tid == 0) p[ip_disc_offset(d)] = disc_offset;
+    if (tid == 0) p[where.disc_offset(d)] = disc_offset;
     if (k == 0) {
-        if (tid < n_rows) { p[ip_slk(d, tid, 0)] = 1.0; p[ip_slk(d, tid, 1)] = 0.0; p[ip_slk(d, tid, 2)] = state_x[sc] + 100.0; which[tid] = -1; }
+        if (tid < n_rows) { p[where.slk(d, tid, 0)] = 1.0; p[where.slk(d, tid, 1)] = 0.0; p[where.slk(d, tid, 2)] = state_x[sc] + 100.0; which[tid] = -1; }
         return;
     }
     long long t_prev = 0; (void)t_prev;
@@ -1308,7 +1311,7 @@ __device__ __forceinline__ void poly_stage(int unit, const Dims &d, int B, const
         if (rank < n_rows) {
             const double2 q = o[i];
             const double a1 = c_ax[ci], a2 = c_ay[ci];
-            p[ip_slk(d, rank, 0)] = a1; p[ip_slk(d, rank, 1)] = a2; p[ip_slk(d, rank, 2)] = a1 * q.x + a2 * q.y - radius;
+            p[where.slk(d, rank, 0)] = a1; p[where.slk(d, rank, 1)] = a2; p[where.slk(d, rank, 2)] = a1 * q.x + a2 * q.y - radius;
             which[rank] = i;
         }
     }
@@ -1338,7 +1341,7 @@ __device__ __forceinline__ void poly_stage(int unit, const Dims &d, int B, const
             every_sample([&](int i, double ax, double ay, double, int) {
                 if (i == s_seed[0]) {
                     const double2 q = o[i];
-                    p[ip_slk(d, r, 0)] = ax; p[ip_slk(d, r, 1)] = ay; p[ip_slk(d, r, 2)] = ax * q.x + ay * q.y - radius;
+                    p[where.slk(d, r, 0)] = ax; p[where.slk(d, r, 1)] = ay; p[where.slk(d, r, 2)] = ax * q.x + ay * q.y - radius;
                     which[r] = i;
                 }
             });
@@ -1348,7 +1351,7 @@ __device__ __forceinline__ void poly_stage(int unit, const Dims &d, int B, const
         n_real = rounds;
         if (tid == 0 && empty_stages) atomicAdd(&empty_stages[b], 1);
     }
-    if (tid < n_rows && tid >= n_real) { p[ip_slk(d, tid, 0)] = 1.0; p[ip_slk(d, tid, 1)] = 0.0; p[ip_slk(d, tid, 2)] = state_x[sc] + 100.0; which[tid] = -1; }
+    if (tid < n_rows && tid >= n_real) { p[where.slk(d, tid, 0)] = 1.0; p[where.slk(d, tid, 1)] = 0.0; p[where.slk(d, tid, 2)] = state_x[sc] + 100.0; which[tid] = -1; }
 }
 
 
@@ -1356,17 +1359,34 @@ __device__ __forceinline__ void poly_stage(int unit, const Dims &d, int B, const
 // samples: the first pass (one workgroup per unit) runs with a short list (POLY_LIST_CAP) and records the rare unit whose candidates do
 // not fit (overflow[0] = their number, overflow[1..] = the units); the second pass, a few workgroups with room for every sample, redoes
 // only those.
+template <class Where>
+__device__ __forceinline__ void poly_units(const Where &where, const Dims &d, int B, const double *x0, double *params, const double *samples, int n_pts, int n_rows,
+                                           const int *scene_of, const double *state_x, double radius, double disc_offset, int *row_sample, int cap, int *overflow,
+                                           int second_pass, int *empty_stages, const unsigned char *discard, int n_scen)
+{
+    const int n_units = second_pass ? overflow[0] : B * d.N;
+    for (int q = blockIdx.x; q < n_units; q += gridDim.x) {      // (first pass: one unit per workgroup)
+        poly_stage(where, second_pass ? overflow[1 + q] : q, d, B, x0, params, samples, n_pts, n_rows, scene_of, state_x, radius, disc_offset, row_sample, cap, overflow, empty_stages, discard, n_scen);
+        __syncthreads();                                          // (the LDS tables are reused by the next unit)
+    }
+}
 __global__ __launch_bounds__(256, 4) void tmpc_scenario_halfspaces_kernel(Dims d, int B, const double *x0, double *params,
                                                                        const double *samples, int n_pts, int n_rows,
                                                                        const int *scene_of, const double *state_x,
                                                                        double radius, double disc_offset, int *row_sample, int cap, int *overflow, int second_pass,
                                                                        int *empty_stages, const unsigned char *discard, int n_scen)
 {
-    const int n_units = second_pass ? overflow[0] : B * d.N;
-    for (int q = blockIdx.x; q < n_units; q += gridDim.x) {      // (first pass: one unit per workgroup)
-        poly_stage(second_pass ? overflow[1 + q] : q, d, B, x0, params, samples, n_pts, n_rows, scene_of, state_x, radius, disc_offset, row_sample, cap, overflow, empty_stages, discard, n_scen);
-        __syncthreads();                                          // (the LDS tables are reused by the next unit)
-    }
+    poly_units(LayoutEnvRows{0}, d, B, x0, params, samples, n_pts, n_rows, scene_of, state_x, radius, disc_offset, row_sample, cap, overflow, second_pass, empty_stages, discard, n_scen);
+}
+// the same stages into the caller's columns (tmpc_stack_scenario_halfspaces): a function of its own, so its static LDS and its dynamic-LDS
+// attribute are its own too (csrc/tmpc_stack_scenario.hpp applies both to the kernel it launches)
+__global__ __launch_bounds__(256, 4) void tmpc_scenario_halfspaces_columns_kernel(Dims d, int B, const double *x0, double *params,
+                                                                               const double *samples, int n_pts, int n_rows,
+                                                                               const int *scene_of, const double *state_x,
+                                                                               double radius, double disc_offset, int *row_sample, int cap, int *overflow, int second_pass,
+                                                                               int *empty_stages, const unsigned char *discard, int n_scen, ColumnEnvRows where)
+{
+    poly_units(where, d, B, x0, params, samples, n_pts, n_rows, scene_of, state_x, radius, disc_offset, row_sample, cap, overflow, second_pass, empty_stages, discard, n_scen);
 }
 
 
@@ -1376,8 +1396,10 @@ __global__ __launch_bounds__(256, 4) void tmpc_scenario_halfspaces_kernel(Dims d
 // scenario s = sample index % n_scenarios (samples are [obstacle][scenario]: one scenario is one joint draw of all obstacles over
 // the horizon); a row is active when  a.p_disc - (b + slack) >= -tol  at the solution.  One wave per trajectory; the set is a
 // bitmask in LDS.  support[b] = number of distinct active scenarios, active_rows[b] = number of active rows.
-__global__ __launch_bounds__(64) void tmpc_scenario_support_kernel(Dims d, int B, const double *params, const double *xtraj, const int *row_sample,
-                                                                  int n_rows, int n_scenarios, double tol, int *support, int *active_rows)
+// Where: the rows and ego_disc_0_offset are read at the layout's offsets or at the caller's columns, like poly_stage writes them.
+template <class Where>
+__device__ __forceinline__ void scenario_support_rows(const Where &where, const Dims &d, int B, const double *params, const double *xtraj, const int *row_sample,
+                                                      int n_rows, int n_scenarios, double tol, int *support, int *active_rows)
 {
 #pragma clang fp contract(off)
     __shared__ unsigned int s_mask[256];                                // up to 8192 scenarios
@@ -1393,9 +1415,9 @@ __global__ __launch_bounds__(64) void tmpc_scenario_support_kernel(Dims d, int B
         if (smp < 0) continue;
         const double *p = params + ((size_t)b * N + k) * d.npar;
         const double *x = xtraj + ((size_t)b * (N + 1) + k) * nxe;
-        const double off = p[ip_disc_offset(d)], slack = d.slack ? x[NX] : 0.0;
+        const double off = p[where.disc_offset(d)], slack = d.slack ? x[NX] : 0.0;
         const double px = x[0] + off * cos(x[2]), py = x[1] + off * sin(x[2]);
-        const double h = p[ip_slk(d, r, 0)] * px + p[ip_slk(d, r, 1)] * py - (p[ip_slk(d, r, 2)] + slack);
+        const double h = p[where.slk(d, r, 0)] * px + p[where.slk(d, r, 1)] * py - (p[where.slk(d, r, 2)] + slack);
         if (h >= -tol) {
             const int s = smp % n_scenarios;
             atomicOr(&s_mask[s >> 5], 1u << (s & 31));
@@ -1407,6 +1429,16 @@ __global__ __launch_bounds__(64) void tmpc_scenario_support_kernel(Dims d, int B
     for (int w = tid; w < 256; w += 64) cnt += __popc(s_mask[w]);
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
     if (tid == 0) { support[b] = cnt; if (active_rows) active_rows[b] = s_rows; }
+}
+__global__ __launch_bounds__(64) void tmpc_scenario_support_kernel(Dims d, int B, const double *params, const double *xtraj, const int *row_sample,
+                                                                  int n_rows, int n_scenarios, double tol, int *support, int *active_rows)
+{
+    scenario_support_rows(LayoutEnvRows{0}, d, B, params, xtraj, row_sample, n_rows, n_scenarios, tol, support, active_rows);
+}
+__global__ __launch_bounds__(64) void tmpc_scenario_support_columns_kernel(Dims d, int B, const double *params, const double *xtraj, const int *row_sample,
+                                                                          int n_rows, int n_scenarios, double tol, int *support, int *active_rows, ColumnEnvRows where)
+{
+    scenario_support_rows(where, d, B, params, xtraj, row_sample, n_rows, n_scenarios, tol, support, active_rows);
 }
 
 

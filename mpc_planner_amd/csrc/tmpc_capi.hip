@@ -488,6 +488,7 @@ struct tmpc_handle {
     int *scn_sample = nullptr;
     size_t scn_cap = 0;
     int scn_rows = 0, scn_B = 0;
+    bool scn_by_column = false;               // the rows of batch scn_B were written by tmpc_stack_scenario_halfspaces, into the caller's columns
     std::vector<hipEvent_t> ev;      // per-launch timing events (pairs)
     int ev_used = 0;
     bool timing = false;
@@ -584,6 +585,8 @@ struct Events {
 #include "tmpc_stack_writers.hpp"
 // the entry points of include/tmpc_hip_stack_env.h (path window, road and decomp rows of such stacks) and the checks tmpc_decomp_halfspaces shares with them
 #include "tmpc_stack_env.hpp"
+// the entry points of include/tmpc_hip_stack_scenario.h (scenario rows and support of such stacks) and what tmpc_scenario_halfspaces shares with them
+#include "tmpc_stack_scenario.hpp"
 
 extern "C" {
 
@@ -1484,47 +1487,13 @@ int tmpc_scenario_halfspaces(tmpc_handle *h, const void *d_samples, int32_t n_pt
                              const void *d_state_x, double radius, double disc_offset)
 {
     TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_scenario_halfspaces");
-    if (!h || h->B <= 0 || !h->params || !d_samples || !d_scene_of || !d_state_x || n_pts <= 0 || n_rows <= 0 || n_rows > 64 ||
-        n_rows > h->d.n_slk) {
-        if (h) h->err = "tmpc_scenario_halfspaces: bad argument / no batch / more rows than the problem's slack rows";
+    if (!h) return TMPC_ERR_INVALID;
+    if (n_rows <= 0 || n_rows > 64 || n_rows > h->d.n_slk) {
+        h->err = "tmpc_scenario_halfspaces: n_rows must be at least 1, at most 64 and at most the problem's slack rows";
         return TMPC_ERR_INVALID;
     }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    const size_t per_entry = 3 * sizeof(double) + sizeof(int);                        // a candidate: normal, margin, index word
-    hipFuncAttributes fa;
-    TMPC_HIP_CHECK(h, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(tmpc::tmpc_scenario_halfspaces_kernel)));
-    if ((size_t)n_pts * per_entry + fa.sharedSizeBytes > 160 * 1024) {      // the second pass's list (room for every sample) + the kernel's static tables
-        h->err = "tmpc_scenario_halfspaces: that many samples per stage do not fit a workgroup's LDS (160 KiB minus the kernel's static tables: about 5480)";
-        return TMPC_ERR_INVALID;
-    }
-    const size_t units = (size_t)h->B * h->d.N;
-    const size_t need = units * n_rows + 1 + units + (size_t)h->B;  // rows' samples, the first pass's overflow list (count, units), empty-polygon stages per trajectory
-    if (int rc = grow_scratch(h, &h->scn_sample, &h->scn_cap, need)) return rc;
-    h->scn_rows = n_rows; h->scn_B = h->B;
-    // scenarios discarded for this batch (tmpc_scenario_discard after the batch was set) are left out of the polygons
-    const bool use_discard = h->scn_discard && h->scn_discard_B == h->B && h->scn_discard_S > 0 && n_pts % h->scn_discard_S == 0;
-    // first pass with a short candidate list (more workgroups per CU); second pass, with room for every sample, only for the
-    // units the first pass recorded as not fitting
-    int *overflow = h->scn_sample + units * n_rows;
-    int *empty_stages = overflow + 1 + units;
-    TMPC_HIP_CHECK(h, hipMemsetAsync(overflow, 0, sizeof(int), h->stream));
-    TMPC_HIP_CHECK(h, hipMemsetAsync(empty_stages, 0, sizeof(int) * (size_t)h->B, h->stream));
-    int list_cap = tmpc::POLY_LIST_CAP;
-    if (const char *e = lab_env("TMPC_POLY_LIST_CAP")) { const int v = atoi(e); if (v >= 64 && v <= 4096) list_cap = v; }   // experiments
-    const int cap1 = n_pts < list_cap ? n_pts : list_cap;
-    for (int pass = 0; pass < (cap1 < n_pts ? 2 : 1); pass++) {
-        const int cap = pass == 0 ? cap1 : n_pts;
-        const size_t lds = (size_t)cap * per_entry;
-        if (lds > 48 * 1024)
-            TMPC_HIP_CHECK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(tmpc::tmpc_scenario_halfspaces_kernel),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(tmpc::tmpc_scenario_halfspaces_kernel, dim3(pass == 0 ? units : (units < 512 ? units : 512)), dim3(256), lds, h->stream, h->d, h->B, h->x0,
-                           const_cast<double *>(h->params), (const double *)d_samples, n_pts, n_rows, (const int *)d_scene_of,
-                           (const double *)d_state_x, radius, disc_offset, h->scn_sample, cap, overflow, pass, empty_stages,
-                           use_discard ? h->scn_discard : nullptr, use_discard ? h->scn_discard_S : 1);
-    }
-    TMPC_HIP_CHECK(h, hipGetLastError());
-    return TMPC_OK;
+    return scenario_halfspaces_checked(h, "tmpc_scenario_halfspaces", tmpc::tmpc_scenario_halfspaces_kernel, false, d_samples, n_pts, n_rows, d_scene_of,
+                                       d_state_x, radius, disc_offset);                                                                           // csrc/tmpc_stack_scenario.hpp
 }
 
 int tmpc_sample_scenarios(tmpc_handle *h, const void *d_pred, const void *d_prob, int32_t n_solvers, int32_t n_obstacles, int32_t n_modes,
@@ -1582,11 +1551,12 @@ int tmpc_scenario_empty_stages(tmpc_handle *h, void *d_count)
 
 int tmpc_scenario_support(tmpc_handle *h, int32_t n_scenarios, double tol, void *d_support, void *d_active_rows)
 {
+    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_scenario_support");     // (its rows can only be tmpc_stack_scenario_halfspaces': read them with tmpc_stack_scenario_support)
     if (!h || !d_support || n_scenarios <= 0 || n_scenarios > 8192 || !(tol >= 0.0)) {
         if (h) h->err = "tmpc_scenario_support: bad argument (1 <= n_scenarios <= 8192, tol >= 0)";
         return TMPC_ERR_INVALID;
     }
-    if (!h->scn_sample || h->scn_B != h->B || h->B <= 0 || !h->params) {
+    if (!h->scn_sample || h->scn_B != h->B || h->B <= 0 || !h->params || h->scn_by_column) {
         h->err = "tmpc_scenario_support: the scenario rows of the current batch were not built by tmpc_scenario_halfspaces (call it after tmpc_set_batch)";
         return TMPC_ERR_INVALID;
     }

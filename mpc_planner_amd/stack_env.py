@@ -14,7 +14,7 @@ stack's parameter map -- on the library a BatchedSolver already loaded:
     env.road_halfspaces(pcols, d_main_of, n_scenes, ...); env.decomp_halfspaces(...); env.set_halfspace_columns(dcols, d_rows, d_scene_of, n_scenes)
 
 Together with stack_writers.StackWriters this is every row of a contouring stack with guidance, road and decomp rows.  The same calls work on a
-hand-written shape with scenes.make_scene(...)["pm"]._params as the map.  Not covered for generated stacks: the scenario rows."""
+hand-written shape with scenes.make_scene(...)["pm"]._params as the map.  The scenario rows of generated stacks: stack_scenario.py."""
 import ctypes as C
 
 from . import solver as _solver
