@@ -57,11 +57,11 @@ constexpr int FB_LXU = 0, FB_R0 = 10, FB_L10 = 11, FB_R1 = 12, FB_P = 13;
 
 // L.scr: SCR_COMPACT doubles in the compact one-wave carve, SCR_FULL in every other one (tmpc_fast.hpp, tmpc_kernels.hpp).  The stage loops' stores of lanes
 // outside a store group (factorisation and both vector sweeps) go to a dummy region of it that nobody reads: RDUM_EXTENT doubles from RDUM_BASE_COMPACT / RDUM_BASE_FULL -- the P row's five at
-// RDUM_P, the pair's two at RDUM_PAIR, the three pivots on top of the P row's at RDUM_PIV -- below the two-wave kernels' flag L.scr[SCR_FULL - 1] and above
+// RDUM_P (the sweeps' one double per stage goes there too), the pair's two at RDUM_PAIR -- below the two-wave kernels' flag L.scr[SCR_FULL - 1] and above
 // what the other users of L.scr take (the block reductions' slots, the parallel-in-time factorisation's four doubles at 48).
 constexpr int SCR_COMPACT = 8, SCR_FULL = 64;
-constexpr int RDUM_P = 0, RDUM_PIV = 0, RDUM_PAIR = 5, RDUM_EXTENT = 7, RDUM_BASE_COMPACT = 0, RDUM_BASE_FULL = 56;
-static_assert(RDUM_P + NX <= RDUM_PAIR && RDUM_PIV + 3 <= RDUM_PAIR && RDUM_PAIR + NU <= RDUM_EXTENT, "dummy slots of the stage loops' store groups");
+constexpr int RDUM_P = 0, RDUM_PAIR = 5, RDUM_EXTENT = 7, RDUM_BASE_COMPACT = 0, RDUM_BASE_FULL = 56;
+static_assert(RDUM_P + NX <= RDUM_PAIR && RDUM_PAIR + NU <= RDUM_EXTENT, "dummy slots of the stage loops' store groups");
 static_assert(RDUM_BASE_COMPACT + RDUM_EXTENT <= SCR_COMPACT, "the dummy region must fit the compact carve's L.scr");
 static_assert(RDUM_BASE_FULL >= 52 && RDUM_BASE_FULL + RDUM_EXTENT <= SCR_FULL - 1, "the dummy region must stay between scr + 48..51 and the flag scr[63]");
 
@@ -316,29 +316,32 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
     // Store merging (round 6).  Stores of disjoint lane sets that hold the same registers at the same point of the loop can leave in ONE LDS instruction
     // with a per-lane address.  In the FACTORISATION -- p_{k+1} of the extra row with the rows of P_{k+1}, its [y0 y1] with the Lxu pairs: four LDS
     // instructions per stage fewer -- that is +1.4 % on the saturated cfg 2 launch.  In the vector sweeps (du of lanes 0, 1 with dx of lanes 2..6; y with p)
-    // the merged store's value needs a select on the END of the stage's dependent chain, which holds the store back: -3.4 % (forward) and -2.0 %
-    // (backward), so the sweeps store separately.  profiles/round6_saturated_levers_ab.jsonl; results are bitwise the same either way.
-    // End of stage k: the Lxu pairs of lanes 2..6 and the extra row's [y0 y1] are the registers f[0], f[1] of their lanes: ONE store for both (per-lane
-    // address); lane 1 adds L10 and the two reciprocal pivots.  (p_k follows at the top of stage k - 1; p_0 is never read.)
-    // One straight-line store region per stage: the three store groups (the P row, the Lxu / y pair, lane 1's pivots) are stores of EVERY lane through a
+    // the merged store's value needs a select on the END of the stage's dependent chain: as PREDICATED stores with index arithmetic that was -3.4 %
+    // (forward) and -2.0 % (backward) in round 6 (profiles/round6_saturated_levers_ab.jsonl).  With every stream a per-lane (base, stride) pair both signs
+    // turned: the forward sweep's one store is +2.4 % (profiles/forward_sweep_fused_sum_ab.jsonl, one_store), the backward sweep's +1.3 %
+    // (profiles/riccati_pivot_pair_store_ab.jsonl); results are bitwise the same either way.
+    // End of stage k: ONE pair store of every lane, through one per-lane (base, stride) pair.  The Lxu pairs of lanes 2..6 and the extra row's [y0 y1] are
+    // the registers f[0], f[1] of their lanes.  The pivots ride in it on lanes 0 and 1, which the Lxu / y pair leaves free: after chol_rows the reciprocal
+    // pivots r0, r1 are row-uniform and lane 1's f[0] is L10, so lane 0 stores (1/L00, L10) at FB_R0 and lane 1 (L10, 1/L11) at FB_L10, both at the block
+    // stride -- slot FB_L10 is written by both lanes, with identical bits; the block [Lxu | 1/L00 L10 1/L11 | P] and its readers are what they were.
+    // Before, lane 1 stored the three doubles in two instructions through an address pair of its own: per stage two LDS instructions and one
+    // v_mad_u32_u24 fewer for one row broadcast and six v_cndmask_b32 on loop-invariant lane masks, after the end of the stage's chain (nothing in the
+    // next stage waits for this store): +1.6 % on the bench launch (profiles/riccati_pivot_pair_store_ab.jsonl).
+    // (p_k follows at the top of stage k - 1; p_0 is never read.)
+    // One straight-line store region per stage: the two store groups (the P row, the Lxu / y / pivot pair) are stores of EVERY lane through a
     // per-lane (offset, stride) pair -- evaluated once, here -- and the lanes outside a group write to a dummy slot of L.scr (stride 0) that nobody reads.
     // Predicated, each group was a divergent side block of the stage loop (saveexec / branch pairs, a lane compare re-evaluated per stage).
     const bool prl = rowl && li >= NU, vl = vec && wr;
-    // (The pair store and the pivot store cannot share an address register: lane 1 is a real lane of the pivots -- block stride -- and a dummy lane of the
-    //  pairs -- stride 0, it has to stay inside the RDUM_EXTENT doubles --, and lanes 2..6 the other way round: no choice of dummy slots makes the
-    //  difference of the two addresses the same at every stage.)
+    const bool pl0 = rowl && li == 0, pl1 = rowl && li == 1;
     double *const dum = L.scr + (CP ? RDUM_BASE_COMPACT : RDUM_BASE_FULL);
     double *const po = vl ? L.pr : prl ? L.Hh + FB_P + i5 * (i5 + 1) / 2 : dum + RDUM_P;
     const int pst = (vl ? NX : prl ? hstride<CP>() : 0) * B8;
-    double *const qo = vl ? (CP == 3 ? L.Hh + NP28 : L.y) : prl ? L.Hh + FB_LXU + 2 * i5 : dum + RDUM_PAIR;
-    const int qst = (vl ? (CP == 3 ? hstride<CP>() : NU) : prl ? hstride<CP>() : 0) * B8;
-    double *const vo = (rowl && li == 1) ? L.Hh : dum + RDUM_PIV - FB_R0;
-    const int vst = ((rowl && li == 1) ? hstride<CP>() : 0) * B8;
+    double *const qo = vl ? (CP == 3 ? L.Hh + NP28 : L.y) : prl ? L.Hh + FB_LXU + 2 * i5 : rowl ? L.Hh + FB_R0 + li : dum + RDUM_PAIR;
+    const int qst = (vl ? (CP == 3 ? hstride<CP>() : NU) : rowl ? hstride<CP>() : 0) * B8;
     auto store_pairs = [&](int k, double r0, double r1) {
+        const double l10 = bcast16<1>(f[0]);
         double *pp = at8(qo, k, qst);
-        pp[0] = f[0]; pp[1] = f[1];
-        double *Fv = at8(vo, k, vst);
-        Fv[FB_L10] = f[0]; Fv[FB_R0] = r0; Fv[FB_R1] = r1;
+        pp[0] = pl0 ? r0 : f[0]; pp[1] = pl0 ? l10 : (pl1 ? r1 : f[1]);
     };
     auto stage = [&](const Opnd &o, Opnd &nx, int k) {
         // broadcast P (lower triangle of the 5x5 cost-to-go Hessian of stage k+1: rows 2..6 after the elimination) to every lane of the row
@@ -357,6 +360,10 @@ __device__ __forceinline__ bool riccati_factor_rows(const Lds &L, const Dims &d,
         // sees one thread: it may not re-order these stores or merge two of them into one instruction (a two-address store would put lane 0's junk and
         // lane 1's value on one address at once for the pairs (2, 1) and (1, 0)) -- hence the compiler barriers between them; only the pair (4, 3), whose
         // junk lands on junk or on entries <= 2, may share an instruction.
+        // (Measured and left out: (4, 3) | (2, 1) | 0 in three instructions, with a dummy base for lane 2 -- i5 = 0, whose entries 1 and 2 are both junk --
+        //  in the middle one, so that its junk entry 2 does not meet lane 3's valid entry 1; every other piece of junk is still overwritten by a later
+        //  instruction.  One more per-lane address, zero scratch and bitwise the same results, +0.18 % at a spread of 0.39 %: inside the noise,
+        //  profiles/riccati_pivot_pair_store_ab.jsonl.)
         {
             double *Ln = at8(po, k + 1, pst);
             Ln[4] = f[NU + 4]; Ln[3] = f[NU + 3];
@@ -625,16 +632,18 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
         const int ghs = (ql ? NX : NV) * B8;
         const double *const tcb = CP ? L.tab + bc.o0 : L.BA + ls;          // own column of [B A]: rows x, y in the table / the dense block
         const int tcs = bc.st * B8;
-        // The two stores of a stage (y: lane 0, p: lanes 2..6) are stores of EVERY lane through a per-lane (base, stride) pair, as in the factorisation:
-        // the lanes outside a store's group write to its dummy slot of L.scr (stride 0), which nobody reads -- the sweeping wave is the only one at
-        // work between the barriers around the sweeps.  Predicated, each store was an s_and_saveexec / s_or pair around a block of the stage loop:
-        // 18 -> 8 SALU instructions per trip of two stages for one VALU more; the same stores in the same order on the lanes that count.  (Measured
-        // alone before the byte addresses: +0.2 ... 0.3 %, inside the spread, left out; on top of them +0.8 % / +1.1 % in two passes at a base
-        // spread of 0.12 %: profiles/riccati_stage_addresses_ab.jsonl.)
+        // ONE store per stage, of EVERY lane through a per-lane (base, stride) pair, as in the factorisation and in the forward sweep: y0 and y1 are row
+        // broadcasts (every lane has them), so lane 0 stores y0 to y_k[0], lane 1 y1 to y_k[1] -- layout 3: inside the stage's block, at the block
+        // stride --, lanes 2..6 p to pr[k NX + i], and the other lanes write to a dummy slot of L.scr (stride 0), which nobody reads -- the sweeping
+        // wave is the only one at work between the barriers around the sweeps.  Before, lane 0 stored the pair (y0, y1) and lanes 2..6 p in a second
+        // instruction through an address pair of its own: per stage one LDS instruction and one v_mad_u32_u24 fewer for two selects (four
+        // v_cndmask_b32); the same values at the same addresses, and p_k still takes the slot of q_{k-1} after that slot's load (above).  +1.3 % on the
+        // bench launch, profiles/riccati_pivot_pair_store_ab.jsonl.  (History: predicated, each store was an s_and_saveexec / s_or pair around a block
+        // of the stage loop, 18 -> 8 SALU instructions per trip of two stages, profiles/riccati_stage_addresses_ab.jsonl.)
         double *const dumb = L.scr + (CP ? RDUM_BASE_COMPACT : RDUM_BASE_FULL);
-        const bool l0 = rowl && li == 0;
-        double *const ydb = l0 ? ysl<CP>(L, 0) : dumb + RDUM_PAIR, *const pdb = xl ? L.pr + i5 : dumb + RDUM_P;
-        const int yds = l0 ? YS8 : 0, pds = xl ? NX * B8 : 0;
+        const bool l0 = rowl && li == 0, l1 = rowl && li == 1;
+        double *const pdb = xl ? L.pr + i5 : (l0 || l1) ? ysl<CP>(L, 0) + li : dumb + RDUM_P;
+        const int pds = xl ? NX * B8 : (l0 || l1) ? YS8 : 0;
         auto load_stage = [&](Ops &o, int k) {
             const double *Fb = at8u(fb, k, HS8);
             o.ghj = *at8(ghq, k, ghs);
@@ -656,9 +665,7 @@ __device__ __forceinline__ void riccati_sweeps_rows(const Lds &L, const Dims &d,
             const double y0 = bcast16<0>(fj * o.a0);                       // lane 0: fj 1/L00
             const double y1 = bcast16<1>((fj - o.a0 * y0) * o.a1);         // lane 1: (fj - L10 y0) 1/L11   (its a0 is L10)
             p = fj - o.a0 * y0 - o.a1 * y1;                                // lanes 2..6: fj - Lxu_i0 y0 - Lxu_i1 y1
-            double *const yk = at8(ydb, k, yds);
-            yk[0] = y0; yk[1] = y1;
-            *at8(pdb, k, pds) = p;
+            *at8(pdb, k, pds) = l0 ? y0 : (l1 ? y1 : p);
         };
         Ops oa, ob;
         load_stage(oa, N - 1);
