@@ -581,12 +581,9 @@ struct Events {
 };
 }  // namespace
 
-// the entry points of include/tmpc_hip_stack.h (the row writers of generated solvers' module stacks) and the checks tmpc_prepare_obstacles shares with them
-#include "tmpc_stack_writers.hpp"
-// the entry points of include/tmpc_hip_stack_env.h (path window, road and decomp rows of such stacks) and the checks tmpc_decomp_halfspaces shares with them
-#include "tmpc_stack_env.hpp"
-// the entry points of include/tmpc_hip_stack_scenario.h (scenario rows and support of such stacks) and what tmpc_scenario_halfspaces shares with them
-#include "tmpc_stack_scenario.hpp"
+// the entry points of the device row writers, for the hand-written layout (tmpc_hip.h) and for the columns of generated solvers' module stacks
+// (tmpc_hip_stack.h, tmpc_hip_stack_env.h, tmpc_hip_stack_scenario.h): one body per writer, two thin entry points; no_batch, launch_flat, read_stack_columns
+#include "tmpc_row_entries.hpp"
 
 extern "C" {
 
@@ -1243,84 +1240,6 @@ int tmpc_gather_best(tmpc_handle *h, const void *d_best, int32_t n_sets, int32_t
     return TMPC_OK;
 }
 
-int tmpc_linearize_topology_ex(tmpc_handle *h, const void *d_obstacle_pos, int32_t n_obstacles, const void *d_obstacle_radius,
-                               const void *d_static_halfspaces, int32_t n_static, const void *d_scene_of, const void *d_state_x,
-                               double robot_radius, const void *d_is_original)
-{
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_linearize_topology");
-    if (!h || h->B <= 0 || !h->params || !d_scene_of || !d_state_x || h->d.n_lin <= 0 || n_obstacles < 0 || n_static < 0 ||
-        n_obstacles + n_static > h->d.n_lin || (n_obstacles > 0 && !d_obstacle_pos) || (n_static > 0 && !d_static_halfspaces)) {
-        if (h) h->err = "tmpc_linearize_topology: bad argument / no batch / more obstacle + static rows than the problem's topology rows";
-        return TMPC_ERR_INVALID;
-    }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    const int n = h->B * h->d.N;
-    hipLaunchKernelGGL(tmpc::tmpc_linearize_topology_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d, h->B,
-                       h->x0, const_cast<double *>(h->params), (const double *)d_obstacle_pos, (const int *)d_scene_of,
-                       (const double *)d_state_x, robot_radius, (const uint8_t *)d_is_original, n_obstacles, (const double *)d_obstacle_radius,
-                       (const double *)d_static_halfspaces, n_static);
-    TMPC_HIP_CHECK(h, hipGetLastError());
-    return TMPC_OK;
-}
-
-int tmpc_linearize_topology(tmpc_handle *h, const void *d_obstacle_pos, const void *d_scene_of, const void *d_state_x,
-                            double robot_radius, const void *d_is_original)
-{
-    if (!h || !d_obstacle_pos) { if (h) h->err = "tmpc_linearize_topology: bad argument"; return TMPC_ERR_INVALID; }
-    return tmpc_linearize_topology_ex(h, d_obstacle_pos, h->d.n_lin, nullptr, nullptr, 0, d_scene_of, d_state_x, robot_radius, d_is_original);
-}
-
-int tmpc_road_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scenes, const void *d_bound_segments, double offset_first,
-                         double offset_second, void *d_static_halfspaces, int32_t n_static, int32_t first_row)
-{
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_road_halfspaces");
-    if (!h) return TMPC_ERR_INVALID;
-    if (h->B <= 0 || !h->x0 || !h->params) { h->err = "tmpc_road_halfspaces: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
-    if (!d_main_of || !d_static_halfspaces || n_scenes <= 0) { h->err = "tmpc_road_halfspaces: bad argument (d_main_of, d_static_halfspaces, n_scenes > 0)"; return TMPC_ERR_INVALID; }
-    if (first_row < 0 || n_static < first_row + 2) { h->err = "tmpc_road_halfspaces: the two road rows do not fit (n_static < first_row + 2)"; return TMPC_ERR_INVALID; }
-    if (h->d.S <= 0) { h->err = "tmpc_road_halfspaces: the problem has no path segments (S = 0)"; return TMPC_ERR_INVALID; }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    const int64_t n = (int64_t)n_scenes * h->d.N;
-    if (n > 0x7fffffff) { h->err = "tmpc_road_halfspaces: n_scenes x N too large"; return TMPC_ERR_INVALID; }
-    hipLaunchKernelGGL(tmpc::tmpc_road_halfspaces_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B, n_scenes, h->x0,
-                       h->params, (const int *)d_main_of, (const double *)d_bound_segments, offset_first, offset_second,
-                       (double *)d_static_halfspaces, n_static, first_row);
-    TMPC_HIP_CHECK(h, hipGetLastError());
-    return TMPC_OK;
-}
-
-int tmpc_prepare_obstacles(tmpc_handle *h, int32_t n_scenes, int32_t n_slots, int32_t max_obstacles, const void *d_count, const void *d_state,
-                           const void *d_raw_pos, const void *d_raw_radius, const void *d_raw_vel, const void *d_raw_pred,
-                           const tmpc_obstacle_options *options, void *d_obstacle_pos, void *d_obstacle_shape, void *d_obstacle_radius,
-                           void *d_obstacle_gaussian, void *d_selected)
-{
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_prepare_obstacles");
-    return prepare_obstacles_checked(h, "tmpc_prepare_obstacles", n_scenes, n_slots, max_obstacles, d_count, d_state, d_raw_pos, d_raw_radius, d_raw_vel,
-                                     d_raw_pred, options, d_obstacle_pos, d_obstacle_shape, d_obstacle_radius, d_obstacle_gaussian, d_selected);    // csrc/tmpc_stack_writers.hpp
-}
-
-int tmpc_set_obstacle_parameters(tmpc_handle *h, const void *d_obstacle_pos, const void *d_obstacle_shape, const void *d_obstacle_radius,
-                                 const void *d_obstacle_gaussian, const void *d_scene_of, const void *d_state, double robot_radius,
-                                 double disc_offset, double risk, double chi, double obstacle_radius)
-{
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_set_obstacle_parameters");
-    if (!h) return TMPC_ERR_INVALID;
-    if (h->B <= 0 || !h->params) { h->err = "tmpc_set_obstacle_parameters: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
-    if (h->d.M <= 0) { h->err = "tmpc_set_obstacle_parameters: the problem has no obstacle rows (M = 0)"; return TMPC_ERR_INVALID; }
-    if (!d_obstacle_pos || !d_obstacle_shape || !d_obstacle_radius || !d_obstacle_gaussian || !d_scene_of || !d_state) {
-        h->err = "tmpc_set_obstacle_parameters: NULL argument"; return TMPC_ERR_INVALID;
-    }
-    const int64_t n = (int64_t)h->B * h->d.N * h->d.M;
-    if (n > 0x7fffffff) { h->err = "tmpc_set_obstacle_parameters: B x N x M too large"; return TMPC_ERR_INVALID; }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(tmpc::tmpc_set_obstacle_parameters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B,
-                       const_cast<double *>(h->params), (const double *)d_obstacle_pos, (const double *)d_obstacle_shape,
-                       (const double *)d_obstacle_radius, (const uint8_t *)d_obstacle_gaussian, (const int *)d_scene_of, (const double *)d_state,
-                       robot_radius, disc_offset, chi, risk, obstacle_radius);
-    TMPC_HIP_CHECK(h, hipGetLastError());
-    return TMPC_OK;
-}
-
 int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const void *d_path, const void *d_path_count, const void *d_path_length,
                     const void *d_bounds, const void *d_pos, int32_t pos_stride, const tmpc_path_options *options, void *d_segment,
                     void *d_closest_s, void *d_window, void *d_bound_window, void *d_reached)
@@ -1349,24 +1268,6 @@ int tmpc_track_path(tmpc_handle *h, int32_t n_scenes, int32_t n_seg_max, const v
     hipLaunchKernelGGL(tmpc::tmpc_track_path_kernel, dim3((unsigned)n_scenes), dim3(64), 0, h->stream, S, n_seg_max, o.search_range,
                        (const double *)d_path, (const int *)d_path_count, (const double *)d_path_length, (const double *)d_bounds, (const double *)d_pos,
                        pos_stride, (int *)d_segment, (double *)d_closest_s, (double *)d_window, (double *)d_bound_window, (uint8_t *)d_reached);
-    TMPC_HIP_CHECK(h, hipGetLastError());
-    return TMPC_OK;
-}
-
-int tmpc_set_path_parameters(tmpc_handle *h, const void *d_window, const void *d_scene_of, int32_t n_scenes, const void *d_closest_s, void *d_state)
-{
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_set_path_parameters");
-    if (!h) return TMPC_ERR_INVALID;
-    if (h->B <= 0 || !h->params) { h->err = "tmpc_set_path_parameters: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
-    if (h->d.S <= 0) { h->err = "tmpc_set_path_parameters: the problem has no path segments (S = 0)"; return TMPC_ERR_INVALID; }
-    if (!d_window || !d_scene_of || n_scenes <= 0) { h->err = "tmpc_set_path_parameters: bad argument (d_window, d_scene_of, n_scenes > 0)"; return TMPC_ERR_INVALID; }
-    if ((d_closest_s == nullptr) != (d_state == nullptr)) { h->err = "tmpc_set_path_parameters: d_closest_s and d_state go together (both or neither)"; return TMPC_ERR_INVALID; }
-    const int64_t n = (int64_t)h->B * h->d.N * h->d.S;
-    if (n > 0x7fffffff) { h->err = "tmpc_set_path_parameters: B x N x S too large"; return TMPC_ERR_INVALID; }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(tmpc::tmpc_set_path_parameters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B,
-                       const_cast<double *>(h->params), (const double *)d_window, (const int *)d_scene_of, n_scenes, (const double *)d_closest_s,
-                       (double *)d_state);
     TMPC_HIP_CHECK(h, hipGetLastError());
     return TMPC_OK;
 }
@@ -1400,20 +1301,9 @@ int tmpc_scatter_parameters(tmpc_handle *h, const int32_t *cols, int32_t n_cols,
     if (n_cols < 1 || n_cols > tmpc::SCATTER_MAX_COLS) { h->err = "tmpc_scatter_parameters: 1 <= n_cols <= 128"; return TMPC_ERR_INVALID; }
     if (per_stage != 0 && per_stage != 1) { h->err = "tmpc_scatter_parameters: per_stage is 0 or 1"; return TMPC_ERR_INVALID; }
     tmpc::ScatterCols list{};
-    list.n = n_cols;
-    for (int i = 0; i < n_cols; i++) {
-        if (cols[i] < 0 || cols[i] >= h->d.npar) { h->err = "tmpc_scatter_parameters: a column outside [0, npar)"; return TMPC_ERR_INVALID; }
-        for (int j = 0; j < i; j++)
-            if (cols[j] == cols[i]) { h->err = "tmpc_scatter_parameters: a duplicate column (the value written would depend on thread order)"; return TMPC_ERR_INVALID; }
-        list.col[i] = cols[i];
-    }
-    const int64_t n = (int64_t)h->B * h->d.N * n_cols;
-    if (n > 0x7fffffff) { h->err = "tmpc_scatter_parameters: B x N x n_cols too large"; return TMPC_ERR_INVALID; }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(tmpc::tmpc_scatter_parameters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B,
+    if (!read_stack_columns(h, "tmpc_scatter_parameters: ", cols, n_cols, list)) return TMPC_ERR_INVALID;
+    return launch_flat(h, "tmpc_scatter_parameters: ", "B x N x n_cols", (int64_t)h->B * h->d.N * n_cols, tmpc::tmpc_scatter_parameters_kernel, h->d, h->B,
                        const_cast<double *>(h->params), list, (const double *)d_values, (const int *)d_scene_of, n_scenes, per_stage);
-    TMPC_HIP_CHECK(h, hipGetLastError());
-    return TMPC_OK;
 }
 
 int tmpc_fit_path(tmpc_handle *h, int32_t n_scenes, int32_t n_pts_max, int32_t n_seg_max, const void *d_xy, const void *d_count, const void *d_s,
@@ -1453,47 +1343,6 @@ int tmpc_costmap_points(tmpc_handle *h, int32_t n_scenes, int32_t size_x, int32_
                        (const uint8_t *)d_cost, (const double *)d_origin, (double *)d_points, (int *)d_count, (uint8_t *)d_overflow);
     TMPC_HIP_CHECK(h, hipGetLastError());
     return TMPC_OK;
-}
-
-int tmpc_decomp_halfspaces(tmpc_handle *h, const void *d_main_of, int32_t n_scenes, int32_t n_seg_max, const void *d_path, const void *d_path_count,
-                           const void *d_path_length, const void *d_s0, const void *d_state_x, const void *d_points, const void *d_count,
-                           int32_t n_pts_max, double range, int32_t n_rows, void *d_rows, void *d_row_count, void *d_status)
-{
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_decomp_halfspaces");
-    return decomp_halfspaces_checked(h, "tmpc_decomp_halfspaces", d_main_of, n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_s0, d_state_x,
-                                     d_points, d_count, n_pts_max, range, n_rows, d_rows, d_row_count, d_status);                              // csrc/tmpc_stack_env.hpp
-}
-
-int tmpc_set_halfspace_rows(tmpc_handle *h, const void *d_rows, int32_t n_rows, int32_t first_row, const void *d_scene_of, int32_t n_scenes,
-                            double disc_offset)
-{
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_set_halfspace_rows");
-    if (!h) return TMPC_ERR_INVALID;
-    if (h->B <= 0 || !h->params) { h->err = "tmpc_set_halfspace_rows: no batch (call tmpc_set_batch* first)"; return TMPC_ERR_INVALID; }
-    if (!d_rows || !d_scene_of || n_scenes <= 0) { h->err = "tmpc_set_halfspace_rows: bad argument (d_rows, d_scene_of, n_scenes > 0)"; return TMPC_ERR_INVALID; }
-    if (n_rows < 1 || first_row < 0 || (int64_t)first_row + n_rows > h->d.n_slk) {
-        h->err = "tmpc_set_halfspace_rows: the rows do not fit (n_rows >= 1, first_row >= 0, first_row + n_rows <= the problem's slack rows)"; return TMPC_ERR_INVALID;
-    }
-    const int64_t n = (int64_t)h->B * h->d.N * n_rows;
-    if (n > 0x7fffffff) { h->err = "tmpc_set_halfspace_rows: B x N x n_rows too large"; return TMPC_ERR_INVALID; }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(tmpc::tmpc_set_halfspace_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->B,
-                       const_cast<double *>(h->params), (const double *)d_rows, n_rows, first_row, (const int *)d_scene_of, n_scenes, disc_offset);
-    TMPC_HIP_CHECK(h, hipGetLastError());
-    return TMPC_OK;
-}
-
-int tmpc_scenario_halfspaces(tmpc_handle *h, const void *d_samples, int32_t n_pts, int32_t n_rows, const void *d_scene_of,
-                             const void *d_state_x, double radius, double disc_offset)
-{
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_scenario_halfspaces");
-    if (!h) return TMPC_ERR_INVALID;
-    if (n_rows <= 0 || n_rows > 64 || n_rows > h->d.n_slk) {
-        h->err = "tmpc_scenario_halfspaces: n_rows must be at least 1, at most 64 and at most the problem's slack rows";
-        return TMPC_ERR_INVALID;
-    }
-    return scenario_halfspaces_checked(h, "tmpc_scenario_halfspaces", tmpc::tmpc_scenario_halfspaces_kernel, false, d_samples, n_pts, n_rows, d_scene_of,
-                                       d_state_x, radius, disc_offset);                                                                           // csrc/tmpc_stack_scenario.hpp
 }
 
 int tmpc_sample_scenarios(tmpc_handle *h, const void *d_pred, const void *d_prob, int32_t n_solvers, int32_t n_obstacles, int32_t n_modes,
@@ -1546,24 +1395,6 @@ int tmpc_scenario_empty_stages(tmpc_handle *h, void *d_count)
     TMPC_HIP_CHECK(h, hipSetDevice(h->device));
     const size_t units = (size_t)h->B * h->d.N;
     TMPC_HIP_CHECK(h, hipMemcpyAsync(d_count, h->scn_sample + units * h->scn_rows + 1 + units, sizeof(int) * (size_t)h->B, hipMemcpyDeviceToDevice, h->stream));
-    return TMPC_OK;
-}
-
-int tmpc_scenario_support(tmpc_handle *h, int32_t n_scenarios, double tol, void *d_support, void *d_active_rows)
-{
-    TMPC_NOT_IN_GENERATED_SOLVER(h, "tmpc_scenario_support");     // (its rows can only be tmpc_stack_scenario_halfspaces': read them with tmpc_stack_scenario_support)
-    if (!h || !d_support || n_scenarios <= 0 || n_scenarios > 8192 || !(tol >= 0.0)) {
-        if (h) h->err = "tmpc_scenario_support: bad argument (1 <= n_scenarios <= 8192, tol >= 0)";
-        return TMPC_ERR_INVALID;
-    }
-    if (!h->scn_sample || h->scn_B != h->B || h->B <= 0 || !h->params || h->scn_by_column) {
-        h->err = "tmpc_scenario_support: the scenario rows of the current batch were not built by tmpc_scenario_halfspaces (call it after tmpc_set_batch)";
-        return TMPC_ERR_INVALID;
-    }
-    TMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(tmpc::tmpc_scenario_support_kernel, dim3(h->B), dim3(64), 0, h->stream, h->d, h->B, h->params, h->xtraj,
-                       h->scn_sample, h->scn_rows, n_scenarios, tol, (int *)d_support, (int *)d_active_rows);
-    TMPC_HIP_CHECK(h, hipGetLastError());
     return TMPC_OK;
 }
 

@@ -10,6 +10,9 @@ import os
 
 import numpy as np
 
+from . import _binding
+from ._binding import TmpcError, _pointer  # noqa: F401  (solver.TmpcError, solver._pointer: the names callers and tests use)
+
 NU, NX, NV = 2, 5, 7
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TMPC_HIP_LIBRARY") or os.path.join(_HERE, "libtmpc_hip.so")     # (TMPC_HIP_LIBRARY: lab switch, an A/B build of the same C-ABI)
@@ -61,10 +64,6 @@ def guidance_options(n_paths, use_tmpcpp=True, warmstart_with_mpc_solution=False
     """A filled tmpc_guidance_options for BatchedSolver.guidance_plan / guidance_decide."""
     return TmpcGuidanceOptions(C.sizeof(TmpcGuidanceOptions), int(n_paths), int(bool(use_tmpcpp)), int(bool(warmstart_with_mpc_solution)),
                                int(bool(shift_previous_solution_forward)), 0, float(selection_weight_consistency))
-
-
-class TmpcError(RuntimeError):
-    pass
 
 
 _int, _i32, _u32, _u64, _f64, _vp = C.c_int, C.c_int32, C.c_uint32, C.c_uint64, C.c_double, C.c_void_p
@@ -140,18 +139,7 @@ _SIGNATURES = {
 }
 EXPORTS = list(_SIGNATURES)
 
-_CTYPES = (C._SimpleCData, C.Array, C.Structure, C._Pointer, type(C.byref(_int())))
-
-
-def _pointer(v):
-    """None or 0: NULL; an integer address as it is; a ctypes object (c_void_p, byref(..), an array) untouched."""
-    return v if v is None or isinstance(v, _CTYPES) else int(v) or None
-
-
-# per function, how BatchedSolver._call() converts each argument behind the handle: counts through int() and reals through float() (a numpy
-# scalar is a TypeError to ctypes otherwise), everything else is a pointer
-_CONVERT = {name: tuple(int if t in (_int, _i32, _u32, _u64) else float if t is _f64 else _pointer for t in argtypes[1:])
-            for name, (_, argtypes) in _SIGNATURES.items()}
+_CONVERT = _binding.converters(_SIGNATURES)      # per function, how BatchedSolver._call() converts each argument behind the handle
 
 
 def has_lane_kernels(lib_path=None):
@@ -179,10 +167,7 @@ def load_library(path=None):
         raise TmpcError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(path)
-    for name, (restype, argtypes) in _SIGNATURES.items():
-        fn = getattr(lib, name, None)           # an older build of the same C-ABI (A/B runs) may lack an entry: skipped here, refused when called
-        if fn is not None:
-            fn.restype, fn.argtypes = restype, argtypes
+    _binding.bind(lib, _SIGNATURES)
     _libs[path] = lib
     return lib
 
@@ -253,16 +238,12 @@ class BatchedSolver:
             pass
 
     def _check(self, rc, what):
-        if rc != 0:
-            raise TmpcError(f"{what} failed ({rc}): {self.lib.tmpc_last_error(self._h).decode()}")
+        _binding.check(self.lib, self._h, rc, what)
 
     def _invoke(self, name, *args):
         """The one path into the library: entry `name` of _SIGNATURES on this handle, every argument converted as its type in the table
         says; returns the entry's code as it is (for the entries whose non-negative return is a value)."""
-        fn = getattr(self.lib, name, None)
-        if fn is None:
-            raise TmpcError(f"this library has no {name} (a missing kernel is an error, there is no host fallback)")
-        return fn(self._h, *[convert(a) for convert, a in zip(_CONVERT[name], args)])
+        return _binding.invoke(self.lib, self._h, name, _CONVERT, args)
 
     def _call(self, name, *args):
         """_invoke, and a non-zero code raises with the library's message."""

@@ -17,7 +17,7 @@ Together with stack_writers.StackWriters this is every row of a contouring stack
 hand-written shape with scenes.make_scene(...)["pm"]._params as the map.  The scenario rows of generated stacks: stack_scenario.py."""
 import ctypes as C
 
-from . import solver as _solver
+from ._binding import StackEntries, _cols, _column, _count
 
 _int, _i32, _f64, _vp = C.c_int, C.c_int32, C.c_double, C.c_void_p
 
@@ -33,16 +33,6 @@ EXPORTS = list(_SIGNATURES)
 
 SPLINE_COEFFICIENTS = ("a", "b", "c", "d")                                  # contouring.py: spline_x{i}_a .. spline_y{i}_d, spline{i}_start
 
-_CONVERT = {name: tuple(int if t is _i32 else float if t is _f64 else _solver._pointer for t in argtypes[1:])
-            for name, (_, argtypes) in _SIGNATURES.items()}
-
-
-def _column(parameter_map, name):
-    try:
-        return int(parameter_map[name])
-    except KeyError:
-        raise KeyError(f"the parameter map has no {name!r}: not a stack with these rows") from None
-
 
 def path_columns(parameter_map, n_segments):
     """cols of set_path_columns / road_halfspaces from a stack's parameter map (name -> column): per segment i < n_segments
@@ -57,49 +47,23 @@ def decomp_columns(parameter_map, n_rows, disc=0):
            [_column(parameter_map, f"disc_{int(disc)}_decomp_{r}_{f}") for r in range(int(n_rows)) for f in ("a1", "a2", "b")]
 
 
-def _cols(cols):
-    return None if cols is None else (C.c_int32 * max(len(cols), 1))(*[int(c) for c in cols])
-
-
-class StackEnvironment:
+class StackEnvironment(StackEntries):
     """The four entry points of tmpc_hip_stack_env.h on a BatchedSolver's library and handle (raw device pointers, like BatchedSolver's own
     wrappers).  Everything is enqueued on the handle's stream; a failure raises solver.TmpcError with the library's message."""
-
-    def __init__(self, solver):
-        self.solver = solver
-        for name, (restype, argtypes) in _SIGNATURES.items():
-            fn = getattr(solver.lib, name, None)        # a library built before the header existed lacks them: refused when called
-            if fn is not None:
-                fn.restype, fn.argtypes = restype, argtypes
-
-    def _call(self, name, *args):
-        s = self.solver
-        fn = getattr(s.lib, name, None)
-        if fn is None:
-            raise _solver.TmpcError(f"this library has no {name} (a missing kernel is an error, there is no host fallback)")
-        rc = fn(s._h, *[convert(a) for convert, a in zip(_CONVERT[name], args)])
-        if rc != 0:
-            raise _solver.TmpcError(f"{name} failed ({rc}): {s.lib.tmpc_last_error(s._h).decode()}")
-
-    @staticmethod
-    def _count(cols, per, lead=0):
-        n = 0 if not cols else len(cols) - lead
-        if n % per:
-            raise ValueError(f"cols holds {lead} + {per} per entry")
-        return n // per
+    _SIGNATURES = _SIGNATURES
 
     def set_path_columns(self, cols, d_window, d_scene_of, n_scenes, d_closest_s=None, d_state=None):
         """What BatchedSolver.set_path_parameters writes, for a stack with len(cols) / 9 path segments: track_path's d_window
         [n_scenes][n_segments][9] into the columns `cols` = path_columns(parameter_map, n_segments) of the current batch's rows
         (tmpc_stack_set_path_columns); d_closest_s / d_state as there."""
-        self._call("tmpc_stack_set_path_columns", _cols(cols), self._count(cols, 9), d_window, d_scene_of, n_scenes, d_closest_s, d_state)
+        self._call("tmpc_stack_set_path_columns", _cols(cols), _count(cols, 9), d_window, d_scene_of, n_scenes, d_closest_s, d_state)
 
     def road_halfspaces(self, cols, d_main_of, n_scenes, offset_first, offset_second, d_static_halfspaces, n_static, first_row=0,
                         d_bound_segments=None):
         """What BatchedSolver.road_halfspaces writes -- rows first_row, first_row + 1 of d_static_halfspaces [n_scenes][N][n_static][3], the
         buffer linearize_topology_columns reads -- with the path window read from the columns `cols` = path_columns(parameter_map,
         n_segments) of the main entry's rows (tmpc_stack_road_halfspaces); d_bound_segments [n_scenes][2][n_segments][8]: bounds mode."""
-        self._call("tmpc_stack_road_halfspaces", _cols(cols), self._count(cols, 9), d_main_of, n_scenes, d_bound_segments, offset_first, offset_second,
+        self._call("tmpc_stack_road_halfspaces", _cols(cols), _count(cols, 9), d_main_of, n_scenes, d_bound_segments, offset_first, offset_second,
                    d_static_halfspaces, n_static, first_row)
 
     def decomp_halfspaces(self, d_main_of, n_scenes, n_seg_max, d_path, d_path_count, d_path_length, d_s0, d_state_x, d_points, d_count, n_pts_max,
@@ -112,4 +76,4 @@ class StackEnvironment:
         """What BatchedSolver.set_halfspace_rows writes, for len(cols) // 3 rows: d_rows [n_scenes][N][n_rows][3] of every stage and
         ego_disc_0_offset into the columns `cols` = decomp_columns(parameter_map, n_rows) of the current batch's rows
         (tmpc_stack_set_halfspace_columns).  The columns name the rows: there is no first_row."""
-        self._call("tmpc_stack_set_halfspace_columns", _cols(cols), self._count(cols, 3, lead=1), d_rows, d_scene_of, n_scenes, disc_offset)
+        self._call("tmpc_stack_set_halfspace_columns", _cols(cols), _count(cols, 3, lead=1), d_rows, d_scene_of, n_scenes, disc_offset)

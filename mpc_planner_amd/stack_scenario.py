@@ -15,8 +15,7 @@ library a BatchedSolver already loaded:
 The same calls work on a hand-written shape with scenes.make_scene(...)["pm"]._params as the map."""
 import ctypes as C
 
-from . import solver as _solver
-from .stack_env import _cols, _column
+from ._binding import StackEntries, _cols, _column, _count
 
 _int, _i32, _f64, _vp = C.c_int, C.c_int32, C.c_double, C.c_void_p
 
@@ -28,9 +27,6 @@ _SIGNATURES = {
 }
 EXPORTS = list(_SIGNATURES)
 
-_CONVERT = {name: tuple(int if t is _i32 else float if t is _f64 else _solver._pointer for t in argtypes[1:])
-            for name, (_, argtypes) in _SIGNATURES.items()}
-
 
 def scenario_columns(parameter_map, n_rows, disc=0):
     """cols of halfspaces / support from a stack's parameter map (name -> column): ego_disc_{disc}_offset, then
@@ -39,32 +35,14 @@ def scenario_columns(parameter_map, n_rows, disc=0):
            [_column(parameter_map, f"disc_{int(disc)}_scenario_constraint_{r}_{f}") for r in range(int(n_rows)) for f in ("a1", "a2", "b")]
 
 
-class StackScenario:
+class StackScenario(StackEntries):
     """The two entry points of tmpc_hip_stack_scenario.h on a BatchedSolver's library and handle (raw device pointers, like BatchedSolver's
     own wrappers).  Everything is enqueued on the handle's stream; a failure raises solver.TmpcError with the library's message."""
-
-    def __init__(self, solver):
-        self.solver = solver
-        for name, (restype, argtypes) in _SIGNATURES.items():
-            fn = getattr(solver.lib, name, None)        # a library built before the header existed lacks them: refused when called
-            if fn is not None:
-                fn.restype, fn.argtypes = restype, argtypes
-
-    def _call(self, name, *args):
-        s = self.solver
-        fn = getattr(s.lib, name, None)
-        if fn is None:
-            raise _solver.TmpcError(f"this library has no {name} (a missing kernel is an error, there is no host fallback)")
-        rc = fn(s._h, *[convert(a) for convert, a in zip(_CONVERT[name], args)])
-        if rc != 0:
-            raise _solver.TmpcError(f"{name} failed ({rc}): {s.lib.tmpc_last_error(s._h).decode()}")
+    _SIGNATURES = _SIGNATURES
 
     @staticmethod
     def _rows(cols):
-        n = 0 if not cols else len(cols) - 1
-        if n % 3:
-            raise ValueError("cols holds 1 + 3 per row")
-        return n // 3
+        return _count(cols, 3, lead=1)
 
     def halfspaces(self, cols, d_samples, n_pts, d_scene_of, d_state_x, radius, disc_offset=0.0):
         """What BatchedSolver.scenario_halfspaces writes, for len(cols) // 3 rows: the polygon rows of d_samples [n_scenes][N][n_pts][2] and

@@ -12,12 +12,13 @@ of the stack's parameter map -- on the library a BatchedSolver already loaded:
     w.prepare_obstacles(...); w.set_obstacle_columns(ocols, 1, 5, ...); w.linearize_topology_columns(tcols, ...); s.solve()
 
 The same calls work on a hand-written shape with scenes.make_scene(...)["pm"]._params as the map.  The path window, the road rows and the decomp
-rows of such stacks: stack_env.py.  Not covered for generated stacks: the scenario rows."""
+rows of such stacks: stack_env.py.  Their scenario rows and the support of the solution: stack_scenario.py."""
 import ctypes as C
 
 import numpy as np
 
 from . import solver as _solver
+from ._binding import StackEntries, _cols, _column, _count
 
 _int, _i32, _f64, _vp = C.c_int, C.c_int32, C.c_double, C.c_void_p
 
@@ -32,16 +33,6 @@ EXPORTS = list(_SIGNATURES)
 
 ELLIPSOID_FIELDS = ("x", "y", "psi", "major", "minor", "chi", "r")          # ellipsoid_constraints.py:33-49
 GAUSSIAN_FIELDS = ("x", "y", "major", "minor", "risk", "r")                 # gaussian_constraints.py:40-52
-
-_CONVERT = {name: tuple(int if t is _i32 else float if t is _f64 else _solver._pointer for t in argtypes[1:])
-            for name, (_, argtypes) in _SIGNATURES.items()}
-
-
-def _column(parameter_map, name):
-    try:
-        return int(parameter_map[name])
-    except KeyError:
-        raise KeyError(f"the parameter map has no {name!r}: not a stack with these rows") from None
 
 
 def obstacle_columns(parameter_map, max_obstacles, row_model):
@@ -59,29 +50,10 @@ def topology_columns(parameter_map, n_rows):
     return [_column(parameter_map, f"lin_constraint_{j}_{f}") for j in range(int(n_rows)) for f in ("a1", "a2", "b")]
 
 
-def _cols(cols):
-    return None if cols is None else (C.c_int32 * max(len(cols), 1))(*[int(c) for c in cols])
-
-
-class StackWriters:
+class StackWriters(StackEntries):
     """The three entry points of tmpc_hip_stack.h on a BatchedSolver's library and handle (raw device pointers, like BatchedSolver's own
     wrappers).  Everything is enqueued on the handle's stream; a failure raises solver.TmpcError with the library's message."""
-
-    def __init__(self, solver):
-        self.solver = solver
-        for name, (restype, argtypes) in _SIGNATURES.items():
-            fn = getattr(solver.lib, name, None)        # a library built before the header existed lacks them: refused when called
-            if fn is not None:
-                fn.restype, fn.argtypes = restype, argtypes
-
-    def _call(self, name, *args):
-        s = self.solver
-        fn = getattr(s.lib, name, None)
-        if fn is None:
-            raise _solver.TmpcError(f"this library has no {name} (a missing kernel is an error, there is no host fallback)")
-        rc = fn(s._h, *[convert(a) for convert, a in zip(_CONVERT[name], args)])
-        if rc != 0:
-            raise _solver.TmpcError(f"{name} failed ({rc}): {s.lib.tmpc_last_error(s._h).decode()}")
+    _SIGNATURES = _SIGNATURES
 
     def prepare_obstacles(self, n_scenes, n_slots, max_obstacles, d_count, d_state, d_raw_pos, d_raw_radius, d_obstacle_pos, d_obstacle_shape,
                           d_obstacle_radius, d_obstacle_gaussian, d_selected, d_raw_vel=None, d_raw_pred=None, probabilistic=False, noise=0.3,
@@ -107,8 +79,5 @@ class StackWriters:
                                    d_static_halfspaces=None, n_static=0, d_is_original=None):
         """What BatchedSolver.linearize_topology_ex writes, for a stack with len(cols) / 3 topology rows, into the columns `cols` =
         topology_columns(parameter_map, n_rows) of the current batch's rows (tmpc_stack_linearize_topology_columns)."""
-        n = 0 if cols is None else len(cols)
-        if n % 3:
-            raise ValueError("cols holds (a1, a2, b) per row: a multiple of 3")
-        self._call("tmpc_stack_linearize_topology_columns", _cols(cols), n // 3, d_obstacle_pos, n_obstacles, d_obstacle_radius, d_static_halfspaces,
+        self._call("tmpc_stack_linearize_topology_columns", _cols(cols), _count(cols, 3), d_obstacle_pos, n_obstacles, d_obstacle_radius, d_static_halfspaces,
                    n_static, d_scene_of, d_state_x, robot_radius, d_is_original)

@@ -1,4 +1,4 @@
-"""GPU: the static environment of a generated stack by column, include/tmpc_hip_stack_env.h (csrc/tmpc_stack_env.hpp;
+"""GPU: the static environment of a generated stack by column, include/tmpc_hip_stack_env.h (csrc/tmpc_row_entries.hpp;
 mpc_planner_amd/stack_env.py) -- the path window, the road rows and the free-space (decomp) rows.
 
 1. On the product library the column entries, given the hand-written layout's own columns, leave the parameter rows, the road buffer and the

@@ -1,4 +1,4 @@
-"""GPU: the scenario rows of a generated stack by column, include/tmpc_hip_stack_scenario.h (csrc/tmpc_stack_scenario.hpp;
+"""GPU: the scenario rows of a generated stack by column, include/tmpc_hip_stack_scenario.h (csrc/tmpc_row_entries.hpp;
 mpc_planner_amd/stack_scenario.py) -- the SH-MPC polygons and the support of the solution.
 
 1. On the product library the column entries, given the hand-written cfg 5 layout's own columns, leave the parameter rows, the empty-stage

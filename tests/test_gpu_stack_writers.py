@@ -1,4 +1,4 @@
-"""GPU: the module-stack writers of include/tmpc_hip_stack.h (csrc/tmpc_stack_writers.hpp; mpc_planner_amd/stack_writers.py) -- the obstacle
+"""GPU: the module-stack writers of include/tmpc_hip_stack.h (csrc/tmpc_row_entries.hpp; mpc_planner_amd/stack_writers.py) -- the obstacle
 and topology rows of a generated solver, written on device into the columns of the stack's parameter map.
 
 1. On the product library the column entries, given the hand-written layout's own columns, leave the rows bit-equal to
