@@ -103,7 +103,7 @@ def decomp_corridor(rng, segs, state, N, n_rows=12):
         for sx, sy in ((1, 1), (1, -1), (-1, 1), (-1, -1)):
             nx_, ny_ = (sx * tx - sy * ty) / np.sqrt(2.0), (sx * ty + sy * tx) / np.sqrt(2.0)
             normals.append((nx_, ny_, 0.8 * (reach + half_w.mean())))
-        for r, (ax, ay, dist) in enumerate(normals):
+        for r, (ax, ay, dist) in enumerate(normals[:n_rows]):     # (fewer than 8 slots: the walls and caps first, then the cuts that fit)
             a1[k + 1, r] = ax; a2[k + 1, r] = ay; b[k + 1, r] = ax * px + ay * py + dist
         s += state[3] * DT
     return a1, a2, b

@@ -169,6 +169,11 @@ static void solve_impl(const orc_problem *pb, const double *xinit, const double 
                        int n_iter, double *pi_io, double *lamh_io)
 {
     const int N = pb->N, nh = pb->n_lin + pb->M + pb->n_gauss + pb->n_slk;
+    if (N < 1 || N > ORC_MAX_N || nh < 0 || nh > ORC_MAX_NH) {             /* past this build's arrays: refused, nothing else written */
+        info->pobj = 0.0; info->res_eq = 0.0; info->exit_code = ORC_EXIT_CAPACITY;
+        info->qp_status = 0; info->sqp_iter = 0; info->qp_iter_total = 0;
+        return;
+    }
     double dslack[ORC_MAX_N + 1];
     /* per-thread workspaces, zeroed per solve (fresh solver state) but allocated once */
     static __thread nlp_state *tls_st = NULL; static __thread orc_qp *tls_qp = NULL; static __thread orc_qp_sol *tls_sol = NULL;

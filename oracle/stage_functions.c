@@ -43,6 +43,8 @@ int orc_idx_slk(const orc_problem *pb, int j, int which)
     return base + 3 * j + which;
 }
 int orc_model_nx(void) { return ORC_NXE; }
+int orc_max_n(void) { return ORC_MAX_N; }
+int orc_max_nh(void) { return ORC_MAX_NH; }
 /* GaussianConstraint.define_parameters (gaussian_constraints.py:40-52): ego_disc_radius, ego_disc_0_offset, then
  * x, y, major, minor, risk, r per obstacle */
 int orc_idx_gaussian(const orc_problem *pb, int j, int which) { return orc_idx_disc_radius(pb) + 2 + 6 * j + which; }

@@ -45,8 +45,17 @@ extern "C" {
 #define ORC_NV 7
 #define ORC_NXE (ORC_NX + ORC_SLACK)
 #define ORC_NVE (ORC_NV + ORC_SLACK)
+/* Static capacities (array strides of the workspaces, of orc_debug and of lamh_io).  The default build holds 32 stages of 40 rows; the
+ * Makefile's *_wide libraries are the same sources with -DORC_MAX_N=62 -DORC_MAX_NH=98 (the HIP path's STAGE_MAX and the most rows the
+ * generic kernel's LDS footprint admits at N = 20).  orc_max_n() / orc_max_nh() report the loaded library's values; a problem past them is
+ * refused by orc_solve* with exit_code ORC_EXIT_CAPACITY and nothing else written. */
+#ifndef ORC_MAX_N
 #define ORC_MAX_N 32
+#endif
+#ifndef ORC_MAX_NH
 #define ORC_MAX_NH 40   /* general inequality rows per stage */
+#endif
+#define ORC_EXIT_CAPACITY 100
 
 /* Problem description: sizes + parameter index map (util/parameters.py:25-55). */
 typedef struct {
@@ -128,6 +137,8 @@ void orc_problem_set_goal_stack(orc_problem *pb, int model);
 void orc_problem_init(orc_problem *pb, int N, int S, int n_lin, int M);
 void orc_problem_init_ex(orc_problem *pb, int N, int S, int n_lin, int M, int n_slk);
 int orc_model_nx(void);   /* ORC_NXE of this build */
+int orc_max_n(void);      /* ORC_MAX_N of this build */
+int orc_max_nh(void);     /* ORC_MAX_NH of this build */
 /* Replace the (absent) ellipsoid module by n_gauss Gaussian chance-constraint rows; recomputes npar. */
 void orc_problem_set_gaussian(orc_problem *pb, int n_gauss);
 int orc_idx_gaussian(const orc_problem *pb, int j, int which);  /* which: 0..5 = x,y,major,minor,risk,r */
@@ -163,7 +174,7 @@ void orc_mirror(double *W, int n, double eps);
 typedef struct {
     double pobj;      /* ocp_nlp_eval_cost at the returned iterate */
     double res_eq;    /* inf-norm of dynamics defects + initial condition at the returned iterate */
-    int exit_code;    /* Forces-style: 1 success, 0 generic failure, 2 maxit, 3 minstep, 4 QP failure */
+    int exit_code;    /* Forces-style: 1 success, 0 generic failure, 2 maxit, 3 minstep, 4 QP failure; ORC_EXIT_CAPACITY: problem refused */
     int qp_status;    /* 0 ok, 2 max iter, 3 min step, 4 NaN */
     int sqp_iter;     /* RTI iterations executed */
     int qp_iter_total;/* IPM iterations summed over all QPs */

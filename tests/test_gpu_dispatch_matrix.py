@@ -21,15 +21,18 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 FIELDS = ("xtraj", "utraj", "pobj", "exit_code", "qp_status", "sqp_iter", "qp_iter_total", "res_eq")
+VERDICT = ("exit_code", "qp_status", "sqp_iter", "qp_iter_total")
 
 
-def case(cid, expect, N, n_lin, M, n_slk=0, S=5, cm=0, gauss=False, rf=0, mode=0, B=16, lab=None, scene=None, ids=(1,), refused=False, also=None, prev=None):
+def case(cid, expect, N, n_lin, M, n_slk=0, S=5, cm=0, gauss=False, rf=0, mode=0, B=16, lab=None, scene=None, ids=(1,), refused=False, also=None, prev=None,
+         doomed=()):
     """expect: the instantiation of the slot the launch runs; also: {slot: name} of other slots the handle must fill; lab: TMPC_* switches of the lab
     library; scene: make_scene keywords instead of the ones derived from the row counts; B: an int, or an expression of the thresholds tmpc_kernel_info
     reports (cp_min_B, cp2_min_B, grid_max); refused: set_latency_mode(mode) returns False (no such variant: the default kernels run); prev: the
-    launch size of (e) (the other side of a threshold) instead of a few trajectories."""
+    launch size of (e) (the other side of a threshold) instead of a few trajectories; doomed: batch entries given contradictory topology rows
+    (test_gpu_parity._make_infeasible): their failure verdicts (exit code, QP status, SQP and interior-point counts) are compared with the oracle's too."""
     return dict(id=cid, expect=expect, N=N, n_lin=n_lin, M=M, n_slk=n_slk, S=S, cm=cm, gauss=gauss, rf=rf, mode=mode, B=B, lab=lab or {},
-                scene=scene, ids=ids, refused=refused, also=also or {}, prev=prev)
+                scene=scene, ids=ids, refused=refused, also=also or {}, prev=prev, doomed=tuple(doomed))
 
 
 CFG5 = dict(M=8, slack=True, n_scenario=24)                      # SH-MPC: 24 scenario halfspaces, dims n_lin 0, M 0, n_slk 24
@@ -61,8 +64,7 @@ DISPATCH_CASES = [
     case("m0 <-1,13,3> nr=39 N=21", "fast<-1,13,3,64,Solo,0>", 21, 12, 13),
     case("m0 N=21 nr=40 generic", "generic<0>", 21, 13, 13),
     case("m0 <-1,9,6> nr=40", "fast<-1,9,6,128,Solo,0>", 20, 13, 13),
-    case("m0 <-1,9,6> nr=54", "fast<-1,9,6,128,Solo,0>", 20, 14, 14, n_slk=12),      # (the last capacity of N <= 20 is the oracle's ORC_MAX_NH = 40 rows:
-                                                                                    #  the generic kernel past it has no reference; N = 21 and 22 <= N <= 32 below)
+    case("m0 <-1,9,6> nr=54", "fast<-1,9,6,128,Solo,0>", 20, 14, 14, n_slk=12),      # (the last fast capacity of N <= 20; the generic kernel past it: below)
     # ---- latency mode 0, 22 <= N <= 32: one wave at two lanes per stage for (8,8); two waves at four lanes per stage otherwise
     case("m0 (8,8) N=22", "fast<8,8,2,64,Solo,0>", 22, 8, 8, also={"default": "compact<8,8,2,64,0>"}),
     case("m0 (8,8) N=30", "fast<8,8,2,64,Solo,0>", 30, 8, 8, ids=(1, 2), also={"default": "compact<8,8,2,64,0>", "lat2": "fast<-1,12,4,128,ScanSoloT<2>,0>",
@@ -145,6 +147,36 @@ DISPATCH_CASES = [
     case("sqrt <-1,13,3> N=20", "fast<-1,13,3,64,SoloSqrt,0>", 20, 8, 8, rf=1),
     case("sqrt <-1,12,4> N=30", "fast<-1,12,4,128,SoloSqrt,0>", 30, 8, 8, rf=1),
     case("sqrt ca (20,8) N=30", "fast<20,8,4,128,SoloSqrt,1>", 30, 8, 8, n_slk=12, cm=1, rf=1),
+    # ---- the generic kernel past every register-row instantiation: 41 and more rows per stage, horizons 33 .. STAGE_MAX = 62, each at its entry point and
+    #      at the row count where lds_doubles() reaches the 160 KB of a CU (test_gpu_parity.test_create_rejects_unsupported_dimensions: one row more is
+    #      refused).  The reference is the wide build of the oracle (tests/test_oracle_wide.py)
+    case("generic N=20 nr=55", "generic<0>", 20, 14, 15, n_slk=12),                  # first shape past fast<-1,9,6,128>
+    case("generic N=20 nh=98 LDS cap", "generic<0>", 20, 49, 49),                    # 163,536 B; the largest row table (nrows 2230)
+    case("generic N=21 nh=92 LDS cap", "generic<0>", 21, 46, 46),
+    case("generic N=32 nh=50 LDS cap", "generic<0>", 32, 25, 25),
+    case("generic N=32 (30,18) slack", "generic<0>", 32, 18, 18, n_slk=12),
+    # doomed entries of the two cases below: chosen on the CPU, with all 16 entries doomed, so that the wide oracle gives the same exit code, QP status,
+    # SQP count and interior-point count for them in all 36 of: built with and without -ffp-contract=off x either Riccati form (the kernels run the other
+    # form than the oracle's default) x the inputs as they are and eight times with every parameter, warm-start value and initial state moved by a few
+    # ulp (a factor 1 + 2^-50 N(0,1)).  A diverging QP ends on a pivot or a diagonal entry of P that exact arithmetic keeps positive, so its count can hang
+    # on rounding: scene 1 at N = 33 has six entries on which the four builds agree (1, 6, 7, 10, 11, 13), and three that also survive the moved inputs
+    # (1: QP status 2 at the limit of 50 iterations; 10, 11: status 4 after 5) -- on entry 6 the oracle itself gives 5 or 6.  At N = 62 scene 1 has one
+    # entry on which the builds agree, so that case takes scene 6, which has seven (0, 1, 5, 6, 9, 11, 15), four under moved inputs too (0, 5, 9, 11:
+    # status 4 after 5 iterations)
+    case("generic N=33 (8,8)", "generic<0>", 33, 8, 8, doomed=(1, 10)),              # first horizon with no fast kernel
+    case("generic N=33 nh=48 LDS cap", "generic<0>", 33, 24, 24),
+    case("generic N=43 nh=30 LDS cap", "generic<0>", 43, 15, 15),
+    case("generic N=48 (12,12)", "generic<0>", 48, 12, 12),
+    case("generic N=61 (6,6)", "generic<0>", 61, 6, 6),
+    case("generic N=62 (6,6) LDS cap", "generic<0>", 62, 6, 6, ids=(6,), doomed=(5, 9)),  # STAGE_MAX: lane 62 is the terminal node, lane 63 idle
+    case("generic N=62 (0,4)", "generic<0>", 62, 0, 4, ids=range(50, 66)),
+    case("generic N=62 (8,4) slack", "generic<0>", 62, 2, 4, n_slk=6),
+    case("generic ca N=40 (8,8)", "generic<1>", 40, 8, 8, cm=1),
+    case("generic g N=40 (8,8)", "generic<2>", 40, 8, 8, gauss=True),
+    case("generic cm3 N=40 (5,5)", "generic<3>", 40, 5, 5, S=3, cm=1, gauss=True),
+    case("m1 (8,8) N=33 refused", "generic<0>", 33, 8, 8, mode=1, refused=True),
+    case("m2 (8,8) N=33 refused", "generic<0>", 33, 8, 8, mode=2, refused=True),
+    case("m3 (8,8) N=33 refused", "generic<0>", 33, 8, 8, mode=3, refused=True),
     # ---- launch size, product library: the real thresholds (fast one-wave -> compact; fast two-wave -> compact two-wave), a persistent loop
     #      that wraps twice with a ragged tail
     case("B=cp_min_B (8,8) N=20", "fast<8,8,3,64,Solo,0>", 20, 8, 8, B="cp_min_B"),
@@ -203,7 +235,7 @@ def _dims(c):
 
 def _problem(c):
     import oracle_lib as O
-    assert c["n_lin"] + c["n_slk"] + c["M"] <= 40, "more rows per stage than the oracle holds (ORC_MAX_NH)"
+    assert c["N"] <= O.WIDE_N and c["n_lin"] + c["n_slk"] + c["M"] <= O.WIDE_NH, "more stages or rows per stage than the wide oracle holds"
     M, ng = (0, c["M"]) if c["gauss"] else (c["M"], 0)
     return O.problem(N=c["N"], S=c["S"], n_lin=c["n_lin"], M=M, n_slk=c["n_slk"], slack=int(c["n_slk"] > 0), n_gauss=ng, cost_model=c["cm"],
                      riccati_form=c["rf"])
@@ -226,6 +258,9 @@ def _scenes(c, B):
     sc = scenes.make_batch(ids, N=c["N"], B=per, **skw)
     sc = {k: sc[k][:B] for k in ("xinit", "x0", "params")} | {"pm": sc["pm"]}
     assert sc["xinit"].shape[0] == B
+    if c["doomed"]:
+        from test_gpu_parity import _make_infeasible
+        sc = _make_infeasible(sc, list(c["doomed"]))
     if c["scene"] is None and c["n_lin"] < c["M"] and c["n_lin"] > 0:
         drop = tuple(f"lin_constraint_{j}_" for j in range(c["n_lin"], c["M"]))
         keep = [i for n, i in sc["pm"]._params.items() if not n.startswith(drop)]
@@ -288,6 +323,12 @@ def test_dispatch_case(c, request, monkeypatch):
     else:
         worst = max(_compare(got, xt, ut, info))
     _check_selection(s.select_best(), got, info)
+    for b in c["doomed"]:                                           # the failure verdicts (_compare: exit code and SQP count of every entry)
+        print(f"[dispatch] {c['id']}: doomed entry {b}: (exit code, QP status, SQP count, interior-point count) kernel "
+              f"{tuple(int(got[f][b]) for f in VERDICT)} oracle {tuple(int(info[f][b]) for f in VERDICT)}")
+    for b in c["doomed"]:
+        assert info["exit_code"][b] != 1 and got["qp_status"][b] == info["qp_status"][b], (b, info["exit_code"][b], got["qp_status"][b], info["qp_status"][b])
+        assert got["qp_iter_total"][b] == info["qp_iter_total"][b], (b, got["qp_iter_total"][b], info["qp_iter_total"][b])
     # (c) the parity check is not made on nothing
     assert ok.sum() >= B / 2, (int(ok.sum()), B)
     # (d) launch to launch

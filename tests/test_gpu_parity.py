@@ -864,7 +864,7 @@ def test_parallel_in_time_variant_other_shapes(cfg):
 @pytest.mark.parametrize("N", [2, 5, 21, 22, 32])
 def test_horizon_edges_match_oracle(N):
     """Horizon edge cases of the kernel dispatch: N = 2 (minimum), 21 (last one-wave shape: 63 of 64 lanes), 22 (first
-    two-wave shape), 32 (all 128 lanes of the two-wave kernel; the oracle's maximum)."""
+    two-wave shape), 32 (all 128 lanes of the two-wave kernel; the maximum of the oracle's default build -- longer horizons: test_gpu_dispatch_matrix.py against the wide build)."""
     import oracle_lib as O
     from mpc_planner_amd import scenes
     B = 16
@@ -889,6 +889,15 @@ def test_create_rejects_unsupported_dimensions():
     d = solver.default_dims(N=60, n_lin=12, M=12)              # valid sizes whose generic-kernel LDS footprint exceeds a CU's 160 KB
     with pytest.raises(solver.TmpcError):
         solver.BatchedSolver(d, B_max=4)
+    # one row per stage more than the generic kernel's LDS footprint admits (lds_doubles in csrc/tmpc_kernels.hpp: 164,816 B, 165,608 B, 167,296 B of
+    # 163,840); the shapes with one row fewer are solved in test_gpu_dispatch_matrix.py
+    for N, n_lin, M in ((20, 49, 50), (33, 24, 25), (62, 6, 7)):
+        with pytest.raises(solver.TmpcError):
+            solver.BatchedSolver(solver.default_dims(N=N, n_lin=n_lin, M=M), B_max=4)
+    # the square-root Riccati form has no instantiation past N = 32: refused, never solved in the other form
+    solver.BatchedSolver(solver.default_dims(N=32, riccati_form=1), B_max=4).close()
+    with pytest.raises(solver.TmpcError):
+        solver.BatchedSolver(solver.default_dims(N=33, riccati_form=1), B_max=4)
 
 
 # ---- generated solvers (mpc_planner_amd/codegen) -------------------------------------------------------
@@ -943,6 +952,37 @@ def test_generated_tmpc_solver_equals_hand_written_kernels():
     hh = np.array(case["h"])
     np.testing.assert_allclose(o["h"][0][:8], hh[:8], rtol=1e-11, atol=1e-12)            # <= 0 rows as they are
     np.testing.assert_allclose(o["h"][0][8:], 1.0 - hh[8:], rtol=1e-11, atol=1e-12)      # >= 1 rows as 1 - h <= 0
+    sg.close(); s0.close()
+
+
+def test_generated_tmpc_solver_on_the_generic_kernel():
+    """The same generated library at N = 40, past every fast instantiation: the generic kernel with the emitted stage functions -- the only run of
+    linearise<false> under TMPC_GENERATED_STAGE (no split rows, the cost Hessian parked in L.W) -- against the hand-written generic kernel and both
+    against the (wide) oracle."""
+    import oracle_lib as O
+    from mpc_planner_amd import scenes, solver
+    path, meta = _generated_lib("tmpc_cfg2")
+    B, N = 16, 40
+    sc = scenes.make_scene(301, N=N, M=8, B=B)
+    assert {k: v for k, v in meta["parameter_map"].items()} == dict(sc["pm"]._params)
+    d = solver.default_dims(N=N, lib_path=path)
+    assert (d.N, d.n_lin, d.M, d.npar) == (N, 16, 0, 135)
+    sg = solver.BatchedSolver(d, B_max=B, lib_path=path)
+    s0 = _solver(N=N, B_max=B)
+    for s in (sg, s0):
+        assert "default=generic<0>" in s.kernel_info(), s.kernel_info()
+    sg.set_batch(sc["xinit"], sc["x0"], sc["params"]); sg.solve(); a = sg.get()
+    s0.set_batch(sc["xinit"], sc["x0"], sc["params"]); s0.solve(); b = s0.get()
+    assert np.array_equal(a["exit_code"], b["exit_code"]) and np.array_equal(a["sqp_iter"], b["sqp_iter"])
+    ok = b["exit_code"] == 1
+    assert ok.sum() >= B // 2 and np.array_equal(a["qp_iter_total"][ok], b["qp_iter_total"][ok])
+    np.testing.assert_allclose(a["xtraj"][ok], b["xtraj"][ok], rtol=0, atol=1e-9)
+    np.testing.assert_allclose(a["pobj"][ok], b["pobj"][ok], rtol=1e-10)
+    pb = O.problem(N=N, S=5, n_lin=8, M=8)
+    xt, ut, info = O.solve_batch(pb, sc["xinit"], sc["x0"].reshape(B, -1), sc["params"].reshape(B, -1))
+    wa = max(_compare(a, xt, ut, info)); wb = max(_compare(b, xt, ut, info))
+    print(f"[generated] N = {N} generic kernel: successes {int(ok.sum())}/{B}, generated vs oracle {wa:.2e}, hand-written vs oracle {wb:.2e}, "
+          f"generated vs hand-written {np.abs(a['xtraj'][ok] - b['xtraj'][ok]).max():.2e}")
     sg.close(); s0.close()
 
 
