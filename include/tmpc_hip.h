@@ -201,7 +201,14 @@ int tmpc_reset_multipliers(tmpc_handle *h);
  * the row passes at twelve (N <= 20) or eight (21 <= N <= 31: the horizon the reference ships, N = 30) lanes per stage and the wide phases of
  * the factorisation on all 256 lanes -- 10-15 % less kernel time per tick than mode 2 (measured ticks: DESIGN.md section 5), results equal to
  * mode 2's to rounding; N <= 20: MPCC or Gaussian rows; 21 <= N <= 31: every stage model, up to 34 rows per stage.  A shape without it runs
- * mode 2 (return value 1).  tmpc_latency_mode_capacity says how many trajectories a variant serves well in one launch. */
+ * mode 2 (return value 1).  tmpc_latency_mode_capacity says how many trajectories a variant serves well in one launch.
+ * GENERATED solver libraries (mpc_planner_amd/codegen, build_generated_solver(..., tick_kernels=True)) carry mode 3, for 2 <= N <= 31 and a
+ * stack with at least one row and at most 34: the run-time-shape instantiations of the same four-wave kernels around the emitted stage
+ * functions, the stage evaluation split over the waves by content (dynamics | emitted cost | the rows on two waves): 10-14 % less kernel time
+ * than the library's default kernel on 5- and 64-trajectory ticks.  Modes 1 and 2 have no generated variant (return
+ * value 1, the default kernel runs): mode 2's two-wave kernels around emitted stage functions measured slower than the default kernel.  A
+ * tick kernel that the compiler could only build with scratch for a stack is not offered either: <name>_meta.json "tick_kernels" lists each
+ * one's registers and scratch. */
 int tmpc_set_latency_mode(tmpc_handle *h, int32_t on);
 /* How many trajectories ONE launch of kernel variant `mode` (0 .. 3 as above) holds resident on this device (workgroups per CU x CUs; variant 3: ONE workgroup per CU, what it is built for), 0 if the
  * handle's shape has no such variant, < 0 on error.  A latency variant pays off while the launch fits (one dependent chain deep); above it the

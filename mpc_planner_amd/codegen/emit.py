@@ -124,12 +124,18 @@ def _cse_block(outputs, prefix):
     return lines
 
 
-def generate(modules, model, settings, name="generated", method="symbolic"):
+def generate(modules, model, settings, name="generated", method="symbolic", row_shares=False, tick_kernels=3, tick_split=1):
     """Returns dict(header=<C++ text>, params=<plugin.Parameters>, npar, nh, slack, rows=[(module row index, kind)]).
     method: "symbolic" = sympy derivatives + one common-subexpression elimination over all outputs (default: the fastest
     kernels -- 8 % off the hand-written cfg 2 kernel -- but ~30 s of generation for a contouring stack); "jets" = sparse
     forward-mode second-order differentiation at code level (jets.py: under a second of generation, kernels 18 % off the
-    hand-written one).  The two are independent implementations and are checked against each other in the tests."""
+    hand-written one).  The two are independent implementations and are checked against each other in the tests.
+    row_shares: the header a solver LIBRARY is compiled around (build.py): the emitted `rows` takes a share (first, step) and evaluates the row
+    blocks k % step == first -- the default (0, 1) is every row --, and the header carries the two constants below.  False: `rows` evaluates
+    every row (the header as it was before the tick kernels: stage-function checks on the host, the recorded digest of the reference's scripts).
+    tick_kernels: the horizon ranges for which a library compiled around this header instantiates the control-tick kernels (latency mode 3):
+    bit 0 = N <= 20, bit 1 = 21 <= N <= 31 (build.py chooses; 0 = none).  tick_split: 1 = the four-wave tick kernels split the stage
+    linearisation over their waves (csrc/tmpc_kernels.hpp linearise_generated_waves); 0 is for A/B measurements of the split."""
     params = plugin.Parameters()
     plugin.define_parameters(modules, params, settings)
     settings = dict(settings); settings["params"] = params
@@ -187,6 +193,7 @@ def generate(modules, model, settings, name="generated", method="symbolic"):
         if not (has_lo or has_up):
             raise UnsupportedStack(f"row {r} is unbounded on both sides")
     row_lines = []
+    block_open = (lambda k: f"    if ({k} % step == first) {{") if row_shares else (lambda k: "    {")
     for k, (r, kind, gexpr) in enumerate(rows):
         for i, v in enumerate(z):
             if i not in ROW_VARS:
@@ -197,7 +204,7 @@ def generate(modules, model, settings, name="generated", method="symbolic"):
             j = em.jet(gexpr)
             G = lambda a: _lit(j.g.get(a, 0.0))
             Hh = lambda a, b: _lit(j.h.get((a, b), 0.0))
-            row_lines += ["    {"] + ["    " + l for l in em.lines] + \
+            row_lines += [block_open(k)] + ["    " + l for l in em.lines] + \
                          [f"        sink({k}, {_lit(j.v)}, {G(0)}, {G(1)}, {G(2)}, {Hh(0, 0)}, {Hh(1, 0)}, {Hh(1, 1)}, {Hh(2, 0)}, {Hh(2, 1)}, {Hh(2, 2)});", "    }"]
             continue
         gx, gy, gp = (sp.diff(gexpr, z[i]) for i in ROW_VARS)
@@ -207,12 +214,30 @@ def generate(modules, model, settings, name="generated", method="symbolic"):
                   ("const double hyp_", sp.diff(gy, z[4])), ("const double hpp_", sp.diff(gp, z[4]))]
         # one block per row (own common subexpressions, values dead after the sink call): keeps the register footprint of
         # the kernel independent of the number of rows; the compiler still shares sin/cos(psi) across blocks
-        row_lines += ["    {"] + ["    " + l for l in _cse_block(outs_k, "r")] + \
+        row_lines += [block_open(k)] + ["    " + l for l in _cse_block(outs_k, "r")] + \
                      [f"        sink({k}, h_, gx_, gy_, gp_, hxx_, hxy_, hyy_, hxp_, hyp_, hpp_);", "    }"]
     nh = len(rows)
     src_rows = ", ".join(str(r) for r, _, _ in rows)
     sgn = ", ".join("1" if kind == "upper" else "-1" for _, kind, _ in rows)
     off = ", ".join(repr(float(ub[r])) if kind == "upper" else repr(float(lb[r])) for r, kind, _ in rows)
+    tick_macro = tick_const = ""
+    rows_head = """// sink(k, g_k, dg/dx, dg/dy, dg/dpsi, d2g/dxdx, dxdy, dydy, dxdpsi, dydpsi, dpsidpsi) for k = 0..NH-1
+template <class Sink>
+TMPC_GEN_FN void rows(const double *z, const double *p, int ps, double slack, Sink &&sink)
+{
+    (void)z; (void)p; (void)ps; (void)slack; (void)sink;"""
+    if row_shares:
+        tick_macro = ("// horizon ranges whose control-tick kernels (latency mode 3) a library around this header instantiates: bit 0 = N <= 20, "
+                      f"bit 1 = 21 <= N <= 31\n#define GENERATED_STAGE_TICK_KERNELS {int(tick_kernels)}\n")
+        tick_const = (f"constexpr int TICK_SPLIT = {int(tick_split)};   // control-tick kernels (four waves per trajectory): 1 = the stage "
+                      "linearisation is split over the waves\n")
+        rows_head = """// sink(k, g_k, dg/dx, dg/dy, dg/dpsi, d2g/dxdx, dxdy, dydy, dxdpsi, dydpsi, dpsidpsi) for k = 0..NH-1.
+// (first, step): this call's share -- the row blocks with k % step == first, each exactly as the unshared call evaluates it
+// (the four-wave tick kernels give the shares to different waves); the default (0, 1) is every row.
+template <class Sink>
+TMPC_GEN_FN void rows(const double *z, const double *p, int ps, double slack, Sink &&sink, int first = 0, int step = 1)
+{
+    (void)z; (void)p; (void)ps; (void)slack; (void)sink; (void)first; (void)step;"""
     header = f"""// Generated by mpc_planner_amd.codegen.emit for solver "{name}" -- do not edit.
 // Stage cost and inequality rows of the configured module stack with exact first and second derivatives.
 // z = [a, w, x, y, psi, v, spline]; p = one stage's parameter row, element i at p[i * ps]; slack = the trajectory's
@@ -229,11 +254,11 @@ def generate(modules, model, settings, name="generated", method="symbolic"):
 
 // 1 / (1 + exp(-x)), evaluated without overflow for either sign of x
 TMPC_GEN_FN double tmpc_gen_logistic(double x) {{ const double e = exp(-fabs(x)); return (x >= 0.0 ? 1.0 : e) / (1.0 + e); }}
-namespace tmpc_gen {{
+{tick_macro}namespace tmpc_gen {{
 constexpr int NPAR = {npar};
 constexpr int NH = {nh};
 constexpr int SLACK = {1 if slack_model else 0};
-constexpr int MODEL = {1 if second_order_unicycle else 0};   // 0: contouring unicycle (spline' = v); 1: SecondOrderUnicycleModel (z[6] is an inert padding slot)
+{tick_const}constexpr int MODEL = {1 if second_order_unicycle else 0};   // 0: contouring unicycle (spline' = v); 1: SecondOrderUnicycleModel (z[6] is an inert padding slot)
 constexpr double LB[7] = {{{", ".join(repr(float(v)) for v in lb7)}}};   // the model's bounds, order [a, w, x, y, psi, v, spline / padding]
 constexpr double UB[7] = {{{", ".join(repr(float(v)) for v in ub7)}}};
 constexpr int ROW_SRC[{max(nh, 1)}] = {{{src_rows or "0"}}};
@@ -253,11 +278,7 @@ TMPC_GEN_FN void cost_full(const double *z, const double *p, int ps, double slac
 {chr(10).join(cost_full)}
 }}
 
-// sink(k, g_k, dg/dx, dg/dy, dg/dpsi, d2g/dxdx, dxdy, dydy, dxdpsi, dydpsi, dpsidpsi) for k = 0..NH-1
-template <class Sink>
-TMPC_GEN_FN void rows(const double *z, const double *p, int ps, double slack, Sink &&sink)
-{{
-    (void)z; (void)p; (void)ps; (void)slack; (void)sink;
+{rows_head}
 {chr(10).join(row_lines)}
 }}
 }}  // namespace tmpc_gen

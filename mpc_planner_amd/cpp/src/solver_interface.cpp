@@ -29,16 +29,28 @@ namespace MPCPlanner
      * its resident set (tmpc_latency_mode_capacity: one workgroup per CU for variants 2 and 3) and the shape has it; otherwise the next lower
      * one is tried: a larger solveBatch() runs on the throughput kernels (round-4 advisor: variant 2 for every batch size was a throughput
      * regression for large batches).  The rule looks at the batch size the CALLER handed over, so it is the caller's choice, not the
-     * library's: a given batch always gets the same kernels. */
-    static int tickKernelVariant()
+     * library's: a given batch always gets the same kernels.
+     * A GENERATED library (mpc_planner_amd/codegen: kernels compiled around a module stack's emitted stage functions) carries variants 2 and 3 too,
+     * but a Solver / BatchContext linked against one keeps running its default kernels, as before those variants existed there: it takes a tick
+     * variant only when MPC_PLANNER_HIP_TICK_VARIANT is set explicitly (INTEGRATION.md sections 4 and 6). */
+    static int tickKernelVariant(bool *explicitly = nullptr)
     {
         const char *v = std::getenv("MPC_PLANNER_HIP_TICK_VARIANT");
-        if (v && v[0] >= '0' && v[0] <= '3' && v[1] == '\0') return v[0] - '0';
-        return 3;
+        const bool valid = v && v[0] >= '0' && v[0] <= '3' && v[1] == '\0';
+        if (explicitly) *explicitly = valid;
+        return valid ? v[0] - '0' : 3;
+    }
+    // the handle's default kernel is an instantiation around emitted stage functions (tmpc_kernel_info names it by its row count, tmpc_gen::NH)
+    static bool generatedLibraryHandle(const tmpc_handle *h)
+    {
+        char info[2048];
+        return tmpc_kernel_info(h, info, (int32_t)sizeof info) > 0 && std::strstr(info, "tmpc_gen::") != nullptr;
     }
     static void applyTickVariant(tmpc_handle *h, int batch)
     {
-        int want = tickKernelVariant();
+        bool explicitly = false;
+        int want = tickKernelVariant(&explicitly);
+        if (!explicitly && generatedLibraryHandle(h)) want = 0;
         while (want > 0) {
             const int cap = tmpc_latency_mode_capacity(h, want);
             if (cap > 0 && batch <= cap) break;

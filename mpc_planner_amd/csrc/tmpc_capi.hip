@@ -291,6 +291,11 @@ static SolveKernel pick_scan_kernel(const Dims &d, KernelSlot *s, int *sl)
     if (d.n_up == 8 && d.M == 8) return TMPC_FASTX(8, 8, 3, 64, ScanSolo, 0);
     if (d.N <= 2 * (64 / 6) && d.n_up + d.M + 14 <= 6 * 9)      // every other row mix of the one-wave shapes (cfg 1, cfg 4, cfg 5, ...): runtime row counts, two waves
         return TMPC_FASTX(-1, 9, 6, 128, ScanSolo, 0);
+#else
+    // generated solver: the slot stays empty.  The two-wave instantiations around emitted stage functions (dynamics and rows | emitted cost) were built and
+    // measured: at every shape tried they were SLOWER than the library's default kernel (tmpc_cfg2 N = 20: 1.087 against 1.008 ms at 64 trajectories, 1.178
+    // against 1.098 ms at 5; jackal_tmpc N = 30: 1.304 against 1.221 and 1.368 against 1.253 ms; profiles/generated_tick_kernels.json), so the project's rule
+    // for a tick mode -- every run below every run of the default kernel -- keeps them out.  Mode 3 (pick_quad_kernel) is the generated tick kernel.
 #endif
     (void)d; (void)s;
     return nullptr;
@@ -319,6 +324,21 @@ static SolveKernel pick_quad_kernel(const Dims &d, bool ab, KernelSlot *s, int *
     if (stage_model(d) == 2) return (d.n_up + d.M + 14 <= 12 * 4) ? TMPC_FASTX(-1, 4, 12, 256, ScanQuad, 2) : nullptr;      // Gaussian rows
     if (d.n_up == 8 && d.M == 8) return ab ? TMPC_FASTX(8, 8, 12, 256, ScanSolo, 0) : TMPC_FASTP(8, 8, 12, 256, ScanQuad);    // (a profiled twin: ScanQuad's only)
     if (d.n_up + d.M + 14 <= 12 * 4) return TMPC_FASTX(-1, 4, 12, 256, ScanQuad, 0);      // cfg 1, cfg 4, cfg 5, any row mix up to 34 rows
+#else
+    // generated solver: the run-time-shape instantiations around the emitted stage functions (tmpc_gen::NH upper-bounded rows, no ellipsoids), under the
+    // product's row caps; compiled for the horizon ranges the emitted header names (GENERATED_STAGE_TICK_KERNELS, codegen/build.py tick_kernels).  A stack
+    // without rows keeps the slot empty (no demo library covers it)
+    if (tmpc_gen::NH == 0 || d.N > 31 || d.N < 2) return nullptr;
+#if GENERATED_STAGE_TICK_KERNELS & 2
+    if (d.N > 20) {
+        if (d.n_up + d.M + 14 > 8 * 6) return nullptr;
+        *sl = 2;
+        return TMPC_FASTX(-1, 6, 8, 256, ScanQuadT<2>, 0);
+    }
+#endif
+#if GENERATED_STAGE_TICK_KERNELS & 1
+    if (d.N <= 20 && d.n_up + d.M + 14 <= 12 * 4) return TMPC_FASTX(-1, 4, 12, 256, ScanQuad, 0);
+#endif
 #endif
     (void)d; (void)ab; (void)s;
     return nullptr;
@@ -699,6 +719,12 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
     for (int i = tmpc::SLOT_LAT1; i <= tmpc::SLOT_LAT3; i++) {
         KernelSlot &s = slot[i];
         if (!s.kernel) continue;
+#ifdef TMPC_GENERATED_STAGE
+        // zero-scratch rule: the product's tick kernels are held to it by the build; around emitted stage functions the compiler decides per
+        // stack, so a tick kernel that uses scratch is not offered -- tmpc_set_latency_mode then answers 1 as for a shape without the variant
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, (const void *)s.kernel) != hipSuccess || fa.localSizeBytes > 0) { s = KernelSlot{}; continue; }
+#endif
         s.lds_bytes = tmpc::slot_lds(d, i, s, i == tmpc::SLOT_LAT3 ? sl3 : sl2);
         if ((i != tmpc::SLOT_LAT1 && s.lds_bytes > tmpc::LDS_CAP) ||
             hipFuncSetAttribute((const void *)s.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds_bytes) != hipSuccess)

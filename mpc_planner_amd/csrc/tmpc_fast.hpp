@@ -130,6 +130,9 @@ __device__ __forceinline__ void lds_add(double *p, double v) { atomicAdd(p, v); 
 template <bool SQ>
 struct SoloT {
     static constexpr int NQ = 1;
+#ifdef TMPC_GENERATED_STAGE
+    static constexpr bool TICK_SPLIT = false;          // (linearise: the default kernels evaluate an emitted stage in one piece)
+#endif
     __device__ __forceinline__ bool alive() const { return true; }
     __device__ __forceinline__ void sync() const { __syncthreads(); }
     __device__ __forceinline__ bool any(bool active) const { return active; }
@@ -149,6 +152,9 @@ using SoloSqrt = SoloT<true>;
 template <int SL>                                    // lanes per stage of the Newton solve's stage phases: 3 (N <= 20) or 2 (N <= 31)
 struct ScanSoloT {
     static constexpr int NQ = 1;
+#ifdef TMPC_GENERATED_STAGE
+    static constexpr bool TICK_SPLIT = false;          // (no generated library instantiates this policy: pick_scan_kernel, tmpc_capi.hip)
+#endif
     __device__ __forceinline__ bool alive() const { return true; }
     __device__ __forceinline__ void sync() const { __syncthreads(); }
     __device__ __forceinline__ bool any(bool active) const { return active; }
@@ -186,6 +192,9 @@ using ScanSolo = ScanSoloT<3>;
 template <int SL>
 struct ScanQuadT {
     static constexpr int NQ = 1;
+#ifdef TMPC_GENERATED_STAGE
+    static constexpr bool TICK_SPLIT = tmpc_gen::TICK_SPLIT != 0;            // (linearise: the emitted stage split over the four waves)
+#endif
     __device__ __forceinline__ bool alive() const { return true; }
     __device__ __forceinline__ void sync() const { __syncthreads(); }
     __device__ __forceinline__ bool any(bool active) const { return active; }
@@ -773,7 +782,11 @@ void tmpc_solve_fast_kernel(Dims d, int B, const double *__restrict__ xinit,
     double lam[C::RPL];
     for (int it = 0; it < d.n_sqp; it++) {
         pf.start();
+#ifdef TMPC_GENERATED_STAGE
+        linearise<true, false, NTH, CM, TEAM::TICK_SPLIT>(L, d, tid, pb, slack_of(), pb_own);      // (the tick kernels split the emitted stage over their waves)
+#else
         linearise<true, false, NTH, CM>(L, d, tid, pb, slack_of(), pb_own);
+#endif
         __syncthreads();
         pf.stop(PH_LIN);
         int iters = 0;
@@ -786,6 +799,11 @@ void tmpc_solve_fast_kernel(Dims d, int B, const double *__restrict__ xinit,
         asm volatile("" : "+v"(tid_w));                   // opaque (see ipm_fast): keeps these addresses out of the prologue
         for (int e = tid_w; e < (N + 1) * NV; e += NT) {
             const int ks = e / NV, i = e - ks * NV;
+#ifdef TMPC_GENERATED_STAGE
+            // SecondOrderUnicycleModel on the tick kernels: the inert padding slot (Dims::model) takes no step.  Its exact step is 0; the Riccati recursion's
+            // forward sweep returns that 0, the parallel-in-time solve only to rounding (1e-20, seen on the GPU), which would creep into the slot callers pad with 0
+            if (tmpc_gen::MODEL == 1 && !std::is_same<TEAM, Solo>::value && i == ZS) continue;
+#endif
             if (!(ks == N && i < NU)) L.z[e] += L.v[e];
         }
         for (int e = tid_w; e < N * NX; e += NT) L.pi[NX + e] = L.pq[NX + e];

@@ -722,10 +722,158 @@ __device__ __forceinline__ void mirror7_pair(double (*A)[NV], double eps, int la
 // (rollout with sensitivities, [B A], the multipliers' share of the Hessian) and half of the ellipsoid rows, wave 1 the cost, the halfspace
 // rows and the other ellipsoids -- which run as different code at the same time; the shares of W are exchanged through LDS and the
 // regularisation (MIRROR: more than half of a stage's chain) is shared too.  W = W_0 + W_1 associates differently from the one-wave sum (rounding level).
-template <bool FAST, bool CP = false, int NTH = 64, int CM = 0>
+// Generated solvers (emitted stage functions), the four-wave control-tick kernels only (SPLIT: latency mode 3 -- the two-wave DEFAULT kernel of
+// 22 <= N <= 32 keeps evaluating every stage in one piece): the stage is split over the waves by content.  Wave 0 the dynamics, wave 1 the emitted cost with
+// its Hessian, waves 2 and 3 the row blocks k % 2 == 0 / 1 of tmpc_gen::rows.  The cost wave passes no stash (stage_linearise parks dt H in the stage's W slot
+// only to free registers for what follows; nothing follows here) and writes its share, dt H, into the stage's W slot after the evaluation; the other shares go
+// to the exchange region behind the layout (wave 0's N x 28, then the row waves' 2 N x 6 inside the scan scratch, dead while the stage blocks are built) -- no
+// share aliases another or the W slot.  After one barrier waves 0 and 1 sum W = W_dyn + W_cost + (share_0 + share_1), always in that order: a solve is bitwise
+// reproducible from launch to launch (another association than the one-wave sum: rounding level).  MIRROR's two diagonal blocks then run on waves 0 and 1 as in
+// the hand-written multi-wave kernels.  Every branch is on the wave index (scalar): all lanes run with the full EXEC mask, lanes >= N redo stage N - 1 and do
+// not store.  (A two-wave form -- dynamics and rows | cost, for latency mode 2 -- was measured slower than the default kernels and is not kept: pick_scan_kernel.)
+#ifdef TMPC_GENERATED_STAGE
+template <int CM>
+__device__ __forceinline__ void linearise_generated_waves(const Lds &L, const Dims &d, int tid, const double *params, double slack)
+{
+    const int N = d.N;
+    int tid_l = tid;
+    asm volatile("" : "+v"(tid_l));
+    const int wv = __builtin_amdgcn_readfirstlane(tid_l >> 6), ln = tid_l & 63;
+    const bool owner = ln < N;
+    const int k = owner ? ln : N - 1;
+    double z[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) z[i] = L.z[k * NV + i];
+    const double *p = params + (size_t)k * d.npar;
+    const int nh = L.nh;
+    double W[NV][NV], g[NV], BA[NX * NV], xn[NX];
+    auto lamh = [&](int r) { return L.lamh[k * nh + r]; };
+    auto sink = [&](int r, const RowOut &ro) {
+        if (owner) {                                             // (every generated row is upper-bounded: the fast layouts keep -D)
+            double *Dr = L.D + k * L.dstride + 3 * r;
+            Dr[0] = -ro.gx; Dr[1] = -ro.gy; Dr[2] = -ro.gp;
+            L.beta[k * nh + r] = 0.0 - ro.h;
+        }
+    };
+    double *W0s = L.scan + k * NP28;
+    double *Wes = L.scan + N * NP28;
+    if (wv == 0) {                                               // dynamics
+        stage_linearise<CM>(d, z, p, 1, L.pi[(k + 1) * NX + 0], L.pi[(k + 1) * NX + 1], lamh, sink, W, g, BA, xn, slack, nullptr, 0, 3);
+        if (owner) {
+#pragma unroll
+            for (int i = 0; i < NX * NV; i++) L.BA[k * NX * NV + i] = BA[i];
+            double *d8 = L.dyn8 + k * 8;
+            d8[D8_XA] = BA[0 * NV + ZA]; d8[D8_XW] = BA[0 * NV + ZW]; d8[D8_XP] = BA[0 * NV + ZPSI]; d8[D8_XV] = BA[0 * NV + ZV];
+            d8[D8_YA] = BA[1 * NV + ZA]; d8[D8_YW] = BA[1 * NV + ZW]; d8[D8_YP] = BA[1 * NV + ZPSI]; d8[D8_YV] = BA[1 * NV + ZV];
+#pragma unroll
+            for (int i = 0; i < NX; i++) L.b[k * NX + i] = xn[i] - L.z[(k + 1) * NV + NU + i];
+#pragma unroll
+            for (int i = 0; i < NV; i++)
+#pragma unroll
+                for (int j = 0; j <= i; j++) W0s[pidx(i, j)] = W[i][j];
+        }
+    } else if (wv == 1) {                                        // the emitted cost
+        stage_linearise<CM>(d, z, p, 1, 0.0, 0.0, lamh, sink, W, g, BA, xn, slack, nullptr, 0, 6);
+        if (owner) {
+#pragma unroll
+            for (int i = 0; i < NV; i++) L.g[k * NV + i] = g[i];
+#pragma unroll
+            for (int i = 0; i < NV; i++)
+#pragma unroll
+                for (int j = 0; j <= i; j++) L.W[k * NP28 + pidx(i, j)] = W[i][j];
+        }
+    } else {                                                     // the rows: wave 2 the even row blocks, wave 3 the odd ones
+        const int first_ = wv - 2;
+        stage_linearise<CM>(d, z, p, 1, 0.0, 0.0, lamh, sink, W, g, BA, xn, slack, nullptr, 0, 7, [&]() { return first_; }, 2, true);
+        if (owner) {
+            double *x = Wes + (first_ * N + k) * 6;
+            x[0] = W[ZX][ZX]; x[1] = W[ZX][ZY]; x[2] = W[ZY][ZY]; x[3] = W[ZX][ZPSI]; x[4] = W[ZY][ZPSI]; x[5] = W[ZPSI][ZPSI];
+        }
+    }
+    __syncthreads();                                             // every share of W is in LDS
+    if (wv >= 2) { __syncthreads(); return; }                   // (the row waves are done: they only attend the barrier below)
+    {
+        double w0[NP28], w1[NP28];
+#pragma unroll
+        for (int e = 0; e < NP28; e++) { w0[e] = W0s[e]; w1[e] = L.W[k * NP28 + e]; }
+#pragma unroll
+        for (int i = 0; i < NV; i++)
+#pragma unroll
+            for (int j = 0; j <= i; j++) { W[i][j] = w0[pidx(i, j)] + w1[pidx(i, j)]; W[j][i] = W[i][j]; }
+        const double *x0 = Wes + k * 6, *x1 = Wes + (N + k) * 6;
+        const double e0 = x0[0] + x1[0], e1 = x0[1] + x1[1], e2 = x0[2] + x1[2], e3 = x0[3] + x1[3], e4 = x0[4] + x1[4], e5 = x0[5] + x1[5];
+        W[ZX][ZX] += e0; W[ZY][ZY] += e2; W[ZPSI][ZPSI] += e5;
+        W[ZX][ZY] += e1; W[ZY][ZX] += e1;
+        W[ZX][ZPSI] += e3; W[ZPSI][ZX] += e3;
+        W[ZY][ZPSI] += e4; W[ZPSI][ZY] += e4;
+    }
+    __syncthreads();                                             // ... and read by both waves: the W slot may be overwritten
+    constexpr int IA[4] = {ZA, ZW, ZPSI, ZV}, IB[3] = {ZX, ZY, ZS};
+    bool coupled = false;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) coupled |= (W[IA[i]][IB[j]] != 0.0) | (W[IB[j]][IA[i]] != 0.0);
+    if (wv == 0) {
+        if (coupled) {                                           // (a row with a disc offset couples psi with x, y: the 7 x 7 iteration, on wave 0)
+            mirror_n<NV>(W, d.reg_eps);
+            if (owner) {
+#pragma unroll
+                for (int i = 0; i < NV; i++)
+#pragma unroll
+                    for (int j = 0; j <= i; j++) L.W[k * NP28 + pidx(i, j)] = W[i][j];
+            }
+        } else {
+            double Ba[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) Ba[i][j] = W[IA[i]][IA[j]];
+            mirror_n<4, true>(Ba, d.reg_eps);
+            if (owner) {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) if (IA[i] >= IA[j]) L.W[k * NP28 + pidx(IA[i], IA[j])] = Ba[i][j];
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+#pragma unroll
+                    for (int j = 0; j < 3; j++) L.W[k * NP28 + sidx(IA[i], IB[j])] = 0.0;      // (the cross entries: exactly zero here)
+            }
+        }
+        if (tid_l == N) {                                        // terminal node: zero cost, no rows: MIRROR(0) = eps I on the state block
+            const int wN = N * NP28, gN = N * NV;
+            for (int e = 0; e < NP28; e++) L.W[wN + e] = 0.0;
+            for (int i = NU; i < NV; i++) L.W[wN + pidx(i, i)] = d.reg_eps;
+            for (int i = 0; i < NV; i++) L.g[gN + i] = 0.0;
+        }
+    } else if (!coupled) {
+        double Bb[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) Bb[i][j] = W[IB[i]][IB[j]];
+        mirror_n<3>(Bb, d.reg_eps);
+        if (owner) {
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+#pragma unroll
+                for (int j = 0; j < 3; j++) if (IB[i] >= IB[j]) L.W[k * NP28 + pidx(IB[i], IB[j])] = Bb[i][j];
+        }
+    }
+}
+#endif
+
+template <bool FAST, bool CP = false, int NTH = 64, int CM = 0, bool SPLIT = false>
 __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, const double *params, double slack, const double *params_own = nullptr)
 {
     const int N = d.N;
+#ifdef TMPC_GENERATED_STAGE
+    if constexpr (SPLIT && FAST && !CP && NTH == 256) {
+        linearise_generated_waves<CM>(L, d, tid, params, slack);
+        return;
+    }
+#endif
 #ifndef TMPC_GENERATED_STAGE
     if constexpr (FAST && NTH == 256) {
         // Four waves per trajectory (round 6, the control-tick kernel: a whole CU serves one trajectory, one wave per SIMD).  The stage evaluation is

@@ -760,13 +760,19 @@ TMPC_HD void stage_linearise(const Dims &d, const double *z, const double *p, in
 #ifdef TMPC_GENERATED_STAGE
     // The emitted cost is long straight-line code: evaluate it first and park dt * Hessian in `stash` (28 doubles of LDS, the
     // stage's own W slot), so that its temporaries are dead before the dynamics / rows / W accumulation start.
+    // part (compile-time at every call site; the four-wave tick kernels, linearise): 0 = the whole stage; 3 = dynamics alone (W = the multipliers' share
+    // of the Lagrangian Hessian, BA, xn; g untouched); 6 = the cost alone (g, W = dt * its Hessian; call without a stash: the cost has the wave to itself);
+    // 7 = the rows alone, the share (ell_first(), ell_step) of tmpc_gen::rows (W = that share of the rows' Hessian).
+    const bool with_cost = part == 0 || part == 6, with_dyn = part == 0 || part == 3, with_rows = part == 0 || part == 7;
     CostOut co;
-    cost_eval(d, z, p, pstride, co, true, slack);
+    if (with_cost) {
+        cost_eval(d, z, p, pstride, co, true, slack);
 #pragma unroll
-    for (int i = 0; i < NV; i++) g[i] = d.dt * co.g[i];          // stage cost scaled by the shooting interval
-    if (stash) {
+        for (int i = 0; i < NV; i++) g[i] = d.dt * co.g[i];          // stage cost scaled by the shooting interval
+        if (stash) {
 #pragma unroll
-        for (int e = 0; e < NP28; e++) stash[e] = d.dt * co.H[e];
+            for (int e = 0; e < NP28; e++) stash[e] = d.dt * co.H[e];
+        }
     }
 #endif
 #pragma unroll
@@ -775,6 +781,8 @@ TMPC_HD void stage_linearise(const Dims &d, const double *z, const double *p, in
         for (int j = 0; j < NV; j++) W[i][j] = 0.0;
 #ifndef TMPC_GENERATED_STAGE
     if (part != 2 && part != 6 && part != 7)
+#else
+    if (with_dyn)
 #endif
     {
         DynOut dy;
@@ -785,27 +793,30 @@ TMPC_HD void stage_linearise(const Dims &d, const double *z, const double *p, in
         dyn_add_hessian(dy, rows_only ? 0.0 : pix, rows_only ? 0.0 : piy, W);
     }
 #ifdef TMPC_GENERATED_STAGE
-    if (stash) {
+    if (with_cost) {
+        if (stash) {
 #pragma unroll
-        for (int i = 0; i < NV; i++)
+            for (int i = 0; i < NV; i++)
 #pragma unroll
-            for (int j = 0; j <= i; j++) {
-                const double h = stash[i * (i + 1) / 2 + j];
-                W[i][j] += h;
-                if (i != j) W[j][i] += h;
-            }
-    } else {
-        cost_add_hessian(co, d.dt, W);
+                for (int j = 0; j <= i; j++) {
+                    const double h = stash[i * (i + 1) / 2 + j];
+                    W[i][j] += h;
+                    if (i != j) W[j][i] += h;
+                }
+        } else {
+            cost_add_hessian(co, d.dt, W);
+        }
     }
     // generated rows, all normalised to g(z) <= 0 (internal order = emitted order, every row upper-bounded)
-    tmpc_gen::rows(z, p, pstride, slack, [&](int k, double h, double gx, double gy, double gp, double hxx, double hxy, double hyy,
-                                             double hxp, double hyp, double hpp) {
-        RowOut ro;
-        ro.h = h; ro.gx = gx; ro.gy = gy; ro.gp = gp;
-        ro.Hxx = hxx; ro.Hxy = hxy; ro.Hyy = hyy; ro.Hxp = hxp; ro.Hyp = hyp; ro.Hpp = hpp;
-        row_add_hessian(ro, lamh(k), W);
-        sink(k, ro);
-    });
+    if (with_rows)
+        tmpc_gen::rows(z, p, pstride, slack, [&](int k, double h, double gx, double gy, double gp, double hxx, double hxy, double hyy,
+                                                 double hxp, double hyp, double hpp) {
+            RowOut ro;
+            ro.h = h; ro.gx = gx; ro.gy = gy; ro.gp = gp;
+            ro.Hxx = hxx; ro.Hxy = hxy; ro.Hyy = hyy; ro.Hxp = hxp; ro.Hyp = hyp; ro.Hpp = hpp;
+            row_add_hessian(ro, lamh(k), W);
+            sink(k, ro);
+        }, ell_first(), ell_step);
 #else
     RowOut ro;
     if (part == 3) return;
