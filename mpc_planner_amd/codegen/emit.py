@@ -135,7 +135,7 @@ def generate(modules, model, settings, name="generated", method="symbolic", row_
     every row (the header as it was before the tick kernels: stage-function checks on the host, the recorded digest of the reference's scripts).
     tick_kernels: the horizon ranges for which a library compiled around this header instantiates the control-tick kernels (latency mode 3):
     bit 0 = N <= 20, bit 1 = 21 <= N <= 31 (build.py chooses; 0 = none).  tick_split: 1 = the four-wave tick kernels split the stage
-    linearisation over their waves (csrc/tmpc_kernels.hpp linearise_generated_waves); 0 is for A/B measurements of the split."""
+    linearisation over their waves (csrc/tmpc_kernels.hpp, the four-wave form of linearise); 0 is for A/B measurements of the split."""
     params = plugin.Parameters()
     plugin.define_parameters(modules, params, settings)
     settings = dict(settings); settings["params"] = params

@@ -402,9 +402,9 @@ static size_t slot_lds(const Dims &d, int slot, const KernelSlot &s, int sl)
     if (s.kind == KernelSlot::GENERIC) return sizeof(double) * (size_t)lds_doubles(d.N, nh);
     if (s.kind == KernelSlot::COMPACT) return sizeof(double) * (size_t)lds_doubles_compact(d.N, d.n_lin, nh, s.threads, s.dpad, s.lay);
     size_t n = lds_doubles_fast(d.N, nh);
-    // two-wave (128-thread) fast kernels park one share of W per stage behind the layout while they linearise (linearise<.., 128>), and so do all
-    // latency kernels; the four-wave one parks the W shares of its split linearisation there (wave 0's N x 28) and inside the scan scratch (the
-    // obstacle lanes' 36 N / 24 N), which is dead then
+    // two-wave (128-thread) fast kernels park wave 0's share of W per stage behind the layout while they linearise (the NTH = 128 form of linearise,
+    // tmpc_kernels.hpp), and so do all latency kernels; the four-wave form parks wave 0's share there too (N x 28) and the row lanes' shares inside the
+    // scan scratch (hand-written stages 36 N / 24 N doubles, emitted stages 12 N), which is dead then
     if (s.threads == 128 || slot >= SLOT_LAT1) n += (size_t)d.N * NP28;
     if (slot == SLOT_LAT2 || slot == SLOT_LAT3) n += sl == 3 ? scan::lds_doubles<3>(d.N) : scan::lds_doubles<2>(d.N);
     return sizeof(double) * n;

@@ -783,7 +783,7 @@ void tmpc_solve_fast_kernel(Dims d, int B, const double *__restrict__ xinit,
     for (int it = 0; it < d.n_sqp; it++) {
         pf.start();
 #ifdef TMPC_GENERATED_STAGE
-        linearise<true, false, NTH, CM, TEAM::TICK_SPLIT>(L, d, tid, pb, slack_of(), pb_own);      // (the tick kernels split the emitted stage over their waves)
+        linearise<true, false, NTH, CM, TEAM::TICK_SPLIT>(L, d, tid, pb, slack_of(), pb_own);      // (TICK_SPLIT: the four-wave form of linearise takes the emitted stage; without it every lane evaluates a stage in one piece)
 #else
         linearise<true, false, NTH, CM>(L, d, tid, pb, slack_of(), pb_own);
 #endif

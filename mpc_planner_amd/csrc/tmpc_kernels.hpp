@@ -717,21 +717,101 @@ __device__ __forceinline__ void mirror7_pair(double (*A)[NV], double eps, int la
     }
 }
 
-// ---- stage linearisation by lane k --------------------------------------------------------------
-// NTH = 128 (fast layout, two waves per trajectory; hand-written stages): the stage evaluation is split over the waves -- wave 0 the dynamics
-// (rollout with sensitivities, [B A], the multipliers' share of the Hessian) and half of the ellipsoid rows, wave 1 the cost, the halfspace
-// rows and the other ellipsoids -- which run as different code at the same time; the shares of W are exchanged through LDS and the
-// regularisation (MIRROR: more than half of a stage's chain) is shared too.  W = W_0 + W_1 associates differently from the one-wave sum (rounding level).
-// Generated solvers (emitted stage functions), the four-wave control-tick kernels only (SPLIT: latency mode 3 -- the two-wave DEFAULT kernel of
-// 22 <= N <= 32 keeps evaluating every stage in one piece): the stage is split over the waves by content.  Wave 0 the dynamics, wave 1 the emitted cost with
-// its Hessian, waves 2 and 3 the row blocks k % 2 == 0 / 1 of tmpc_gen::rows.  The cost wave passes no stash (stage_linearise parks dt H in the stage's W slot
-// only to free registers for what follows; nothing follows here) and writes its share, dt H, into the stage's W slot after the evaluation; the other shares go
-// to the exchange region behind the layout (wave 0's N x 28, then the row waves' 2 N x 6 inside the scan scratch, dead while the stage blocks are built) -- no
-// share aliases another or the W slot.  After one barrier waves 0 and 1 sum W = W_dyn + W_cost + (share_0 + share_1), always in that order: a solve is bitwise
-// reproducible from launch to launch (another association than the one-wave sum: rounding level).  MIRROR's two diagonal blocks then run on waves 0 and 1 as in
-// the hand-written multi-wave kernels.  Every branch is on the wave index (scalar): all lanes run with the full EXEC mask, lanes >= N redo stage N - 1 and do
-// not store.  (A two-wave form -- dynamics and rows | cost, for latency mode 2 -- was measured slower than the default kernels and is not kept: pick_scan_kernel.)
+// ---- the steps that the wave forms of the stage linearisation share (linearise below) ------------
+// Only the steps that compile to the SAME device code as the text they replace are helpers: the row sink's body, the rows' parked share of W, the terminal
+// node, and the dynamics store of the multi-wave forms (in the one-wave form the same call moves the register allocation: it stays written out there).
+// The packed W store and sum, the symmetric add of the rows' share and the two-wave MIRROR tail were tried as helpers too, with W by pointer and by
+// reference, and taken back: each moved the register allocation of whole kernels and their times both ways (profiles/linearise_refactor.json, records
+// `attempt_*`), so the forms keep that text in place.  With the helpers below every solve kernel, hand-written and generated, compiles to the
+// instructions it had without them.
 #ifdef TMPC_GENERATED_STAGE
+constexpr bool GENERATED_STAGE = true;               // emitted stage functions (mpc_planner_amd/codegen): linearise asks this constant only
+#else
+constexpr bool GENERATED_STAGE = false;
+#endif
+
+// What a form's row sink does on the lane that writes row r of stage k (every row is evaluated by exactly one lane, which writes it): the Jacobian and
+// beta = bound - h go into the layout.  Fast layouts (the register-row kernels) keep the SIGNED row Jacobian sgn D -- upper-bounded rows -1, lower-bounded
+// +1 -- so that the row passes of ipm_fast read their coefficients as they are; the generic kernel keeps D and applies the sign itself.  The forms call it
+// from a `[&]` lambda written in place: a closure returned from a helper compiled to other registers and, in one kernel, to other last bits.
+// ALL_UPPER (the four-wave form of generated solvers): every emitted row is upper-bounded, and tmpc_create admits a generated library's dims only with
+// n_lin == tmpc_gen::NH, M == 0, n_slk == 0 and row_model == 0, so derive_dims gives n_up = n_lin + n_slk = NH: r < d.n_up holds for every emitted row and
+// CM has no Gaussian bit -- the general text gives -D and 0 - h for them, and ALL_UPPER only says so at compile time.
+template <bool FAST, bool CP, int CM, bool ALL_UPPER = false>
+__device__ __forceinline__ void store_row(const Lds &L, const Dims &d, int k, int nh, int r, const RowOut &ro)
+{
+    const double sg = FAST ? ((ALL_UPPER || r < d.n_up) ? -1.0 : 1.0) : 1.0;
+    if constexpr (CP) {
+        // packed Jacobians: (gx, gy) for topology rows (gp == 0 exactly, lin_row_eval), triples for the others
+        double *Dr = L.D + k * L.dstride + (r < L.n_pair ? 2 * r : 3 * r - L.n_pair);
+        Dr[0] = sg * ro.gx; Dr[1] = sg * ro.gy;
+        if (r >= L.n_pair) Dr[2] = sg * ro.gp;
+    } else {
+        double *Dr = FAST ? L.D + k * L.dstride + 3 * r : L.D + (k * nh + r) * 3;      // (fast layout: padded stage stride, carve_fast)
+        Dr[0] = sg * ro.gx; Dr[1] = sg * ro.gy; Dr[2] = sg * ro.gp;
+    }
+    const double bound = (ALL_UPPER || r < d.n_up || cm_gaussian_rows(CM)) ? 0.0 : 1.0;     // ellipsoid rows: h >= 1; Gaussian rows: h >= 0
+    L.beta[k * nh + r] = bound - ro.h;
+}
+
+// the rows' share of W is its (x, y, psi) block: 6 entries, parked for the lane that sums them (every form sums in its own order, visible in the sign
+// of a zero)
+__device__ __forceinline__ void put_xypsi(double *x, double (*W)[NV])
+{
+    x[0] = W[ZX][ZX]; x[1] = W[ZX][ZY]; x[2] = W[ZY][ZY]; x[3] = W[ZX][ZPSI]; x[4] = W[ZY][ZPSI]; x[5] = W[ZPSI][ZPSI];
+}
+
+// [B A], its 8 non-constant entries and the defects b of stage k, by the lane that evaluated the dynamics (the multi-wave forms: wave 0's owner lane).
+// Compact layout: b lives in the global workspace and [B A] is kept as the 8 entries only.
+template <bool CP>
+__device__ __forceinline__ void store_dynamics(const Lds &L, int k, const double *BA, const double *xn)
+{
+    if constexpr (!CP) {
+#pragma unroll
+        for (int i = 0; i < NX * NV; i++) L.BA[k * NX * NV + i] = BA[i];
+    }
+    double *d8 = (CP ? L.tab : L.dyn8) + k * 8;
+    d8[D8_XA] = BA[0 * NV + ZA]; d8[D8_XW] = BA[0 * NV + ZW]; d8[D8_XP] = BA[0 * NV + ZPSI]; d8[D8_XV] = BA[0 * NV + ZV];
+    d8[D8_YA] = BA[1 * NV + ZA]; d8[D8_YW] = BA[1 * NV + ZW]; d8[D8_YP] = BA[1 * NV + ZPSI]; d8[D8_YV] = BA[1 * NV + ZV];
+#pragma unroll
+    for (int i = 0; i < NX; i++) L.b[k * NX + i] = xn[i] - L.z[(k + 1) * NV + NU + i];
+}
+
+// terminal node: zero cost, no rows: MIRROR(0) = eps I on the state block (one lane)
+__device__ __forceinline__ void linearise_terminal(const Lds &L, const Dims &d, int N)
+{
+    const int wN = N * NP28, gN = N * NV;
+    for (int e = 0; e < NP28; e++) L.W[wN + e] = 0.0;
+    for (int i = NU; i < NV; i++) L.W[wN + pidx(i, i)] = d.reg_eps;
+    for (int i = 0; i < NV; i++) L.g[gN + i] = 0.0;
+}
+
+// ---- stage linearisation by lane k --------------------------------------------------------------
+// Three forms, by the threads of a trajectory.  Every branch between waves is on the wave index: all lanes run with the full EXEC mask, lanes that own no
+// stage redo stage N - 1 and do not store.
+// NTH = 64, and the generic kernel: one lane evaluates the whole stage (below, with the one-wave kernels' split of a stage's rows over three lanes).
+// NTH = 128 (fast and compact layout, hand-written stages): the stage evaluation is split over the two waves -- wave 0 the dynamics (rollout with
+// sensitivities, [B A], the multipliers' share of the Hessian) and half of the ellipsoid rows, wave 1 the cost, the halfspace rows and the other ellipsoids --
+// which run as different code at the same time; the shares of W are exchanged through LDS and the regularisation (MIRROR: more than half of a stage's
+// chain) is shared too.  W = W_0 + W_1 associates differently from the one-wave sum (rounding level).
+// NTH = 256 (fast layout; round 6, the control-tick kernels: a whole CU serves one trajectory, one wave per SIMD): the stage evaluation is split FOUR ways,
+// by what is computed rather than by stage: wave 0 the dynamics (rollout with sensitivities, [B A], defects, the multipliers' share of the Hessian), wave 1
+// the cost with its Hessian, waves 2 and 3 the rows.  The cost wave writes its share into the stage's W slot; the other shares go to the exchange region
+// behind the layout (wave 0's N x 28, then the row lanes' 6 each, inside the scan scratch, dead while the stage blocks are built) -- no share aliases another
+// or the W slot.  After one barrier waves 0 and 1 sum W = W_dyn + W_cost + (the row lanes' shares), always in that order: a solve is bitwise reproducible
+// from launch to launch (another association than the one-wave sum: rounding level).  MIRROR's two diagonal blocks then run on waves 0 and 1 as in the
+// two-wave kernels.  The form is written twice, for hand-written stages inside linearise and for emitted stages as linearise_generated_waves: one text
+// with the differences behind `if constexpr` was built and compiled the generated tick kernels to other code with more registers (the same record), so it
+// was not kept.  They differ in this:
+//   - hand-written stages: G lane groups per row wave, so a lane evaluates at most ceil(n / 2 G) rows of each class (halfspace, scenario / decomp, obstacle).
+//     N <= 21: three lanes per stage on the row waves (six shares); 22 <= N <= 32 (the shipped jackal / jackalsimulator horizon, N = 30): two (four
+//     shares).  The shares are summed 0.0 + share_0 + share_1 + ...
+//   - emitted stages (generated solvers, SPLIT: latency mode 3 only -- their two-wave DEFAULT kernel of 22 <= N <= 32 and every other kernel evaluate a
+//     stage in one piece, the one-wave form): one lane group, wave 2 the row blocks k % 2 == 0 of tmpc_gen::rows and wave 3 the odd ones, summed share_0 +
+//     share_1.  The wave index is made scalar (readfirstlane), there is no own parameter row (own_delta = 0), and the cost wave passes no stash
+//     (stage_linearise parks dt H in the stage's W slot only to free registers for what follows; nothing follows here).  (A two-wave form -- dynamics and
+//     rows | cost, for latency mode 2 -- was measured slower than the default kernels and is not kept: pick_scan_kernel.)
+// the four-wave form around emitted stage functions (see above; compiled in every build, called by generated solvers only)
 template <int CM>
 __device__ __forceinline__ void linearise_generated_waves(const Lds &L, const Dims &d, int tid, const double *params, double slack)
 {
@@ -748,25 +828,13 @@ __device__ __forceinline__ void linearise_generated_waves(const Lds &L, const Di
     const int nh = L.nh;
     double W[NV][NV], g[NV], BA[NX * NV], xn[NX];
     auto lamh = [&](int r) { return L.lamh[k * nh + r]; };
-    auto sink = [&](int r, const RowOut &ro) {
-        if (owner) {                                             // (every generated row is upper-bounded: the fast layouts keep -D)
-            double *Dr = L.D + k * L.dstride + 3 * r;
-            Dr[0] = -ro.gx; Dr[1] = -ro.gy; Dr[2] = -ro.gp;
-            L.beta[k * nh + r] = 0.0 - ro.h;
-        }
-    };
+    auto sink = [&](int r, const RowOut &ro) { if (owner) store_row<true, false, CM, true>(L, d, k, nh, r, ro); };
     double *W0s = L.scan + k * NP28;
     double *Wes = L.scan + N * NP28;
     if (wv == 0) {                                               // dynamics
         stage_linearise<CM>(d, z, p, 1, L.pi[(k + 1) * NX + 0], L.pi[(k + 1) * NX + 1], lamh, sink, W, g, BA, xn, slack, nullptr, 0, 3);
         if (owner) {
-#pragma unroll
-            for (int i = 0; i < NX * NV; i++) L.BA[k * NX * NV + i] = BA[i];
-            double *d8 = L.dyn8 + k * 8;
-            d8[D8_XA] = BA[0 * NV + ZA]; d8[D8_XW] = BA[0 * NV + ZW]; d8[D8_XP] = BA[0 * NV + ZPSI]; d8[D8_XV] = BA[0 * NV + ZV];
-            d8[D8_YA] = BA[1 * NV + ZA]; d8[D8_YW] = BA[1 * NV + ZW]; d8[D8_YP] = BA[1 * NV + ZPSI]; d8[D8_YV] = BA[1 * NV + ZV];
-#pragma unroll
-            for (int i = 0; i < NX; i++) L.b[k * NX + i] = xn[i] - L.z[(k + 1) * NV + NU + i];
+            store_dynamics<false>(L, k, BA, xn);
 #pragma unroll
             for (int i = 0; i < NV; i++)
 #pragma unroll
@@ -786,8 +854,7 @@ __device__ __forceinline__ void linearise_generated_waves(const Lds &L, const Di
         const int first_ = wv - 2;
         stage_linearise<CM>(d, z, p, 1, 0.0, 0.0, lamh, sink, W, g, BA, xn, slack, nullptr, 0, 7, [&]() { return first_; }, 2, true);
         if (owner) {
-            double *x = Wes + (first_ * N + k) * 6;
-            x[0] = W[ZX][ZX]; x[1] = W[ZX][ZY]; x[2] = W[ZY][ZY]; x[3] = W[ZX][ZPSI]; x[4] = W[ZY][ZPSI]; x[5] = W[ZPSI][ZPSI];
+            put_xypsi(Wes + (first_ * N + k) * 6, W);
         }
     }
     __syncthreads();                                             // every share of W is in LDS
@@ -841,12 +908,7 @@ __device__ __forceinline__ void linearise_generated_waves(const Lds &L, const Di
                     for (int j = 0; j < 3; j++) L.W[k * NP28 + sidx(IA[i], IB[j])] = 0.0;      // (the cross entries: exactly zero here)
             }
         }
-        if (tid_l == N) {                                        // terminal node: zero cost, no rows: MIRROR(0) = eps I on the state block
-            const int wN = N * NP28, gN = N * NV;
-            for (int e = 0; e < NP28; e++) L.W[wN + e] = 0.0;
-            for (int i = NU; i < NV; i++) L.W[wN + pidx(i, i)] = d.reg_eps;
-            for (int i = 0; i < NV; i++) L.g[gN + i] = 0.0;
-        }
+        if (tid_l == N) linearise_terminal(L, d, N);
     } else if (!coupled) {
         double Bb[3][3];
 #pragma unroll
@@ -862,36 +924,25 @@ __device__ __forceinline__ void linearise_generated_waves(const Lds &L, const Di
         }
     }
 }
-#endif
 
 template <bool FAST, bool CP = false, int NTH = 64, int CM = 0, bool SPLIT = false>
 __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, const double *params, double slack, const double *params_own = nullptr)
 {
     const int N = d.N;
-#ifdef TMPC_GENERATED_STAGE
-    if constexpr (SPLIT && FAST && !CP && NTH == 256) {
+    if constexpr (GENERATED_STAGE && SPLIT && FAST && !CP && NTH == 256) {
         linearise_generated_waves<CM>(L, d, tid, params, slack);
         return;
     }
-#endif
-#ifndef TMPC_GENERATED_STAGE
-    if constexpr (FAST && NTH == 256) {
-        // Four waves per trajectory (round 6, the control-tick kernel: a whole CU serves one trajectory, one wave per SIMD).  The stage evaluation is
-        // split FOUR ways, by what is computed rather than by stage: wave 0 the dynamics (rollout with sensitivities, [B A], defects, the multipliers'
-        // share of the Hessian), wave 1 the cost, waves 2 and 3 the rows (halfspace, scenario / decomp, obstacle) -- three lanes per stage each, so a
-        // lane evaluates at most ceil(n / 6) rows of each class.  The shares of W meet in LDS (the scan scratch behind the layout is dead while the stage blocks are
-        // built); MIRROR's two diagonal blocks then run on waves 0 and 1 as in the two-wave kernels.  W = W_dyn + W_cost + sum of the six obstacle
-        // shares, in that order (associates differently from the one-wave sum: rounding level).  Fast layout only.  N <= 21: three lanes per stage on the
-        // obstacle waves (six shares); 22 <= N <= 32 (the shipped jackal / jackalsimulator horizon, N = 30): two (four shares).
+    if constexpr (!GENERATED_STAGE && FAST && NTH == 256) {
         static_assert(!CP, "four-wave linearisation: fast layout");
         int tid_l = tid;
         asm volatile("" : "+v"(tid_l));
         const int wv = tid_l >> 6, ln = tid_l & 63;
-        const int G = 3 * N <= 64 ? 3 : 2;                         // lane groups of a wave
-        const int grp = ln >= 2 * N ? 2 : (ln >= N ? 1 : 0);       // lane group inside the wave: 0 owner, 1 / 2 helpers (waves 2, 3 only)
+        const int G = 3 * N <= 64 ? 3 : 2;                            // lane groups of a row wave
+        const int grp = ln >= 2 * N ? 2 : (ln >= N ? 1 : 0);          // lane group inside the wave: 0 owner, 1 / 2 helpers (waves 2, 3 only)
         const bool owner = ln < N;                                  // (full EXEC mask: other lanes redo a stage and do not store)
         const bool inrng = ln < G * N;
-        const bool rowlane = wv >= 2 && inrng;                      // an obstacle-row lane
+        const bool rowlane = wv >= 2 && inrng;                      // a row lane
         const int k = inrng ? ln - grp * N : N - 1;
         double z[NV];
 #pragma unroll
@@ -902,28 +953,14 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
         double W[NV][NV], g[NV], BA[NX * NV], xn[NX];
         auto lamh = [&](int r) { return L.lamh[k * nh + r]; };
         const bool writes = wv >= 2 ? rowlane : owner;
-        auto sink = [&](int r, const RowOut &ro) {
-            if (writes) {
-                const double sg = (r < d.n_up) ? -1.0 : 1.0;     // fast layouts keep the SIGNED row Jacobian (ipm_fast reads it as it is)
-                double *Dr = L.D + k * L.dstride + 3 * r;
-                Dr[0] = sg * ro.gx; Dr[1] = sg * ro.gy; Dr[2] = sg * ro.gp;
-                const double bound = (r < d.n_up || cm_gaussian_rows(CM)) ? 0.0 : 1.0;
-                L.beta[k * nh + r] = bound - ro.h;
-            }
-        };
-        // exchange region: [0, N 28): wave 0's share of W (as in the two-wave kernels); [N 28, N 28 + 2 G N 6): the obstacle lanes' shares (x, y, psi block)
+        auto sink = [&](int r, const RowOut &ro) { if (writes) store_row<FAST, CP, CM>(L, d, k, nh, r, ro); };
+        // exchange region: [0, N 28): wave 0's share of W (as in the two-wave kernels); [N 28, N 28 + 2 G N 6): the row lanes' shares (x, y, psi block)
         double *W0s = L.scan + k * NP28;
         double *Wes = L.scan + N * NP28;
         if (wv == 0) {                                           // dynamics
             stage_linearise<CM>(d, z, p, 1, L.pi[(k + 1) * NX + 0], L.pi[(k + 1) * NX + 1], lamh, sink, W, g, BA, xn, slack, nullptr, own_delta, 3);
             if (owner) {
-#pragma unroll
-                for (int i = 0; i < NX * NV; i++) L.BA[k * NX * NV + i] = BA[i];
-                double *d8 = L.dyn8 + k * 8;
-                d8[D8_XA] = BA[0 * NV + ZA]; d8[D8_XW] = BA[0 * NV + ZW]; d8[D8_XP] = BA[0 * NV + ZPSI]; d8[D8_XV] = BA[0 * NV + ZV];
-                d8[D8_YA] = BA[1 * NV + ZA]; d8[D8_YW] = BA[1 * NV + ZW]; d8[D8_YP] = BA[1 * NV + ZPSI]; d8[D8_YV] = BA[1 * NV + ZV];
-#pragma unroll
-                for (int i = 0; i < NX; i++) L.b[k * NX + i] = xn[i] - L.z[(k + 1) * NV + NU + i];
+                store_dynamics<CP>(L, k, BA, xn);
 #pragma unroll
                 for (int i = 0; i < NV; i++)
 #pragma unroll
@@ -939,16 +976,13 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
 #pragma unroll
                     for (int j = 0; j <= i; j++) L.W[k * NP28 + pidx(i, j)] = W[i][j];
             }
-        } else {                                                 // the rows (halfspace, scenario / decomp, obstacle): lane (wave, group) takes rows first, first + 2 G, ... of each class
+        } else {                                                 // the rows: lane (wave, group) takes rows first, first + 2 G, ... of each class
             const int first_ = (wv - 2) * G + grp;
             stage_linearise<CM>(d, z, p, 1, 0.0, 0.0, lamh, sink, W, g, BA, xn, slack, nullptr, own_delta, 7, [&]() { return first_; }, 2 * G, true);
-            if (rowlane) {
-                double *x = Wes + (first_ * N + k) * 6;
-                x[0] = W[ZX][ZX]; x[1] = W[ZX][ZY]; x[2] = W[ZY][ZY]; x[3] = W[ZX][ZPSI]; x[4] = W[ZY][ZPSI]; x[5] = W[ZPSI][ZPSI];
-            }
+            if (rowlane) put_xypsi(Wes + (first_ * N + k) * 6, W);
         }
         __syncthreads();                                         // every share of W is in LDS
-        if (wv >= 2) { __syncthreads(); return; }               // (the obstacle waves are done: they only attend the barrier below)
+        if (wv >= 2) { __syncthreads(); return; }               // (the row waves are done: they only attend the barrier below)
         {
             double w0[NP28], w1[NP28];
 #pragma unroll
@@ -1006,12 +1040,7 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
                         for (int j = 0; j < 3; j++) L.W[k * NP28 + sidx(IA[i], IB[j])] = 0.0;      // (the cross entries: exactly zero here)
                 }
             }
-            if (tid_l == N) {                                // terminal node: zero cost, no rows: MIRROR(0) = eps I on the state block
-                const int wN = N * NP28, gN = N * NV;
-                for (int e = 0; e < NP28; e++) L.W[wN + e] = 0.0;
-                for (int i = NU; i < NV; i++) L.W[wN + pidx(i, i)] = d.reg_eps;
-                for (int i = 0; i < NV; i++) L.g[gN + i] = 0.0;
-            }
+            if (tid_l == N) linearise_terminal(L, d, N);
         } else if (!coupled) {
             double Bb[3][3];
 #pragma unroll
@@ -1028,7 +1057,7 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
         }
         return;
     }
-    if constexpr (FAST && NTH == 128) {                  // (both layouts: the compact one differs in where the blocks go, not in the arithmetic)
+    if constexpr (!GENERATED_STAGE && FAST && NTH == 128) {  // (both layouts: the compact one differs in where the blocks go, not in the arithmetic)
         int tid_l = tid;
         asm volatile("" : "+v"(tid_l));
         const int wv = tid_l >> 6, ln = tid_l & 63;
@@ -1042,25 +1071,10 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
         const int nh = L.nh;
         double W[NV][NV], g[NV], BA[NX * NV], xn[NX];
         auto lamh = [&](int r) { return L.lamh[k * nh + r]; };
-        auto sink = [&](int r, const RowOut &ro) {
-            if (owner) {
-                const double sg = (r < d.n_up) ? -1.0 : 1.0;     // fast layouts keep the SIGNED row Jacobian (ipm_fast reads it as it is)
-                if constexpr (CP) {                               // packed: (gx, gy) for topology rows, triples for the others
-                    double *Dr = L.D + k * L.dstride + (r < L.n_pair ? 2 * r : 3 * r - L.n_pair);
-                    Dr[0] = sg * ro.gx; Dr[1] = sg * ro.gy;
-                    if (r >= L.n_pair) Dr[2] = sg * ro.gp;
-                } else {
-                    double *Dr = FAST ? L.D + k * L.dstride + 3 * r : L.D + (k * nh + r) * 3;      // (fast layout: padded stage stride, carve_fast)
-                    Dr[0] = sg * ro.gx; Dr[1] = sg * ro.gy; Dr[2] = sg * ro.gp;
-                }
-                const double bound = (r < d.n_up || cm_gaussian_rows(CM)) ? 0.0 : 1.0;     // ellipsoid rows: h >= 1; Gaussian rows: h >= 0
-                L.beta[k * nh + r] = bound - ro.h;
-            }
-        };
-        // both waves park their share of W (wave 1 in the stage's W slot, wave 0 in the -- idle -- residual arrays of the interior-point
-        // work region), so that after the barrier each of them has the complete W and MIRROR can be shared as well: with a zero disc offset
-        // W is block diagonal under {a, w, psi, v} | {x, y, spline} (mirror7), and the two blocks are regularised on different waves --
-        // bitwise what mirror7 computes.  A coupled W (any cross entry != 0) takes the 7 x 7 iteration on wave 0.
+        auto sink = [&](int r, const RowOut &ro) { if (owner) store_row<FAST, CP, CM>(L, d, k, nh, r, ro); };
+        // both waves park their share of W (wave 1 in the stage's W slot, wave 0 behind the layout), so that after the barrier each of them has the
+        // complete W and MIRROR can be shared as well: with a zero disc offset W is block diagonal under {a, w, psi, v} | {x, y, spline} (mirror7), and the
+        // two blocks are regularised on different waves -- bitwise what mirror7 computes.  A coupled W (any cross entry != 0) takes the 7 x 7 iteration on wave 0.
         double *W0s = L.scan + k * NP28;                     // (N * NP28 doubles behind the layout: every two-wave launch allocates them; compact layout: in the global workspace)
         if (wv == 1) {                                       // cost, halfspace rows, second half of the ellipsoid rows
             stage_linearise<CM>(d, z, p, 1, 0.0, 0.0, lamh, sink, W, g, BA, xn, slack, nullptr, own_delta, 2);
@@ -1075,15 +1089,7 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
         } else {                                             // dynamics, first half of the ellipsoid rows
             stage_linearise<CM>(d, z, p, 1, L.pi[(k + 1) * NX + 0], L.pi[(k + 1) * NX + 1], lamh, sink, W, g, BA, xn, slack, nullptr, own_delta, 1);
             if (owner) {
-                if constexpr (!CP) {
-#pragma unroll
-                    for (int i = 0; i < NX * NV; i++) L.BA[k * NX * NV + i] = BA[i];
-                }
-                double *d8 = (CP ? L.tab : L.dyn8) + k * 8;
-                d8[D8_XA] = BA[0 * NV + ZA]; d8[D8_XW] = BA[0 * NV + ZW]; d8[D8_XP] = BA[0 * NV + ZPSI]; d8[D8_XV] = BA[0 * NV + ZV];
-                d8[D8_YA] = BA[1 * NV + ZA]; d8[D8_YW] = BA[1 * NV + ZW]; d8[D8_YP] = BA[1 * NV + ZPSI]; d8[D8_YV] = BA[1 * NV + ZV];
-#pragma unroll
-                for (int i = 0; i < NX; i++) L.b[k * NX + i] = xn[i] - L.z[(k + 1) * NV + NU + i];
+                store_dynamics<CP>(L, k, BA, xn);
 #pragma unroll
                 for (int i = 0; i < NV; i++)
 #pragma unroll
@@ -1134,12 +1140,7 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
                         for (int j = 0; j < 3; j++) L.W[k * NP28 + sidx(IA[i], IB[j])] = 0.0;      // (the cross entries: exactly zero here)
                 }
             }
-            if (tid_l == N) {                                // terminal node: zero cost, no rows: MIRROR(0) = eps I on the state block
-                const int wN = N * NP28, gN = N * NV;
-                for (int e = 0; e < NP28; e++) L.W[wN + e] = 0.0;
-                for (int i = NU; i < NV; i++) L.W[wN + pidx(i, i)] = d.reg_eps;
-                for (int i = 0; i < NV; i++) L.g[gN + i] = 0.0;
-            }
+            if (tid_l == N) linearise_terminal(L, d, N);
         } else if (!coupled) {
             double Bb[3][3];
 #pragma unroll
@@ -1156,7 +1157,6 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
         }
         return;
     }
-#endif
     // Every lane runs the (register-hungry) stage evaluation with the full EXEC mask -- lanes >= N redo stage N-1 and
     // simply do not store -- so that no spill/reload of live registers happens under a partial mask.
     int tid_l = tid;
@@ -1170,11 +1170,8 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
     // instructions, no extra issue slots.  The sum of the three shares associates differently from the sequential
     // sum over the rows (rounding level).  `split`: the wave has the lanes and the exchange buffer lies clear of the staging region -- a fact of the
     // SHAPE, computed once on the host (split_rows_for below) so that the fast and the compact kernel of a shape always take the same path.
-#ifdef TMPC_GENERATED_STAGE
-    const bool split = false;                            // (emitted stage functions evaluate all their rows in one piece: tmpc_gen::rows has no notion of a share)
-#else
-    const bool split = FAST && NTH == 64 && 3 * N <= 64 && L.nh >= 3 && d.split_rows;       // (Dims::split_rows: the exchange buffer -- dv and dpi, 12 (N + 1) contiguous doubles -- lies clear of the staging region in EVERY layout of the shape)
-#endif
+    // (Emitted stage functions evaluate all their rows in one piece: tmpc_gen::rows has no notion of a share.)
+    const bool split = !GENERATED_STAGE && FAST && NTH == 64 && 3 * N <= 64 && L.nh >= 3 && d.split_rows;       // (Dims::split_rows: the exchange buffer -- dv and dpi, 12 (N + 1) contiguous doubles -- lies clear of the staging region in EVERY layout of the shape)
     const bool helper = split && tid_l >= N && tid_l < 3 * N;
     const int k = owner ? tid_l : (helper ? (tid_l >= 2 * N ? tid_l - 2 * N : tid_l - N) : N - 1);
     auto ell_first = [&]() { return split ? (tid_l >= N ? 1 : 0) + (tid_l >= 2 * N ? 1 : 0) : 0; };     // the lane's group: owner 0, helpers 1 and 2
@@ -1191,32 +1188,12 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
             const double sgn = (r < d.n_up) ? -1.0 : 1.0;
             return -sgn * L.lam[k * nh + r];
         };
-        auto sink = [&](int r, const RowOut &ro) {
-            if (owner || helper) {                            // (every row is evaluated by exactly one of a stage's three lanes, which writes it)
-                // fast layouts (the register-row kernels) keep the SIGNED row Jacobian sgn D -- upper-bounded rows -1, lower-bounded +1 -- so that
-                // the row passes of ipm_fast read their coefficients as they are; the generic kernel keeps D and applies the sign itself
-                const double sg = FAST ? ((r < d.n_up) ? -1.0 : 1.0) : 1.0;
-                if constexpr (CP) {
-                    // packed Jacobians: (gx, gy) for topology rows (gp == 0 exactly, lin_row_eval), triples for the others
-                    double *Dr = L.D + k * L.dstride + (r < L.n_pair ? 2 * r : 3 * r - L.n_pair);
-                    Dr[0] = sg * ro.gx; Dr[1] = sg * ro.gy;
-                    if (r >= L.n_pair) Dr[2] = sg * ro.gp;
-                } else {
-                    double *Dr = FAST ? L.D + k * L.dstride + 3 * r : L.D + (k * nh + r) * 3;      // (fast layout: padded stage stride, carve_fast)
-                    Dr[0] = sg * ro.gx; Dr[1] = sg * ro.gy; Dr[2] = sg * ro.gp;
-                }
-                const double bound = (r < d.n_up || cm_gaussian_rows(CM)) ? 0.0 : 1.0;     // ellipsoid rows: h >= 1; Gaussian rows: h >= 0
-                L.beta[k * nh + r] = bound - ro.h;
-            }
-        };
+        auto sink = [&](int r, const RowOut &ro) { if (owner || helper) store_row<FAST, CP, CM>(L, d, k, nh, r, ro); };
         stage_linearise<CM>(d, z, p, 1, L.pi[(k + 1) * NX + 0], L.pi[(k + 1) * NX + 1], lamh, sink, W, g, BA, xn, slack,
                         L.W + k * NP28, own_delta, 0, ell_first, split ? 3 : 1, helper);   // (generated solvers park the cost Hessian in the stage's W slot)
         if (split) {                                        // the helpers' W = their share of the obstacle rows' Hessian (x, y, psi block) -> the owner
             double *xe = L.dv;                              // 2 N x 6 doubles (dv and dpi are contiguous: 252 doubles at N = 20)
-            if (helper) {
-                double *x = xe + (tid_l - N) * 6;                      // ((group - 1) N + k)
-                x[0] = W[ZX][ZX]; x[1] = W[ZX][ZY]; x[2] = W[ZY][ZY]; x[3] = W[ZX][ZPSI]; x[4] = W[ZY][ZPSI]; x[5] = W[ZPSI][ZPSI];
-            }
+            if (helper) put_xypsi(xe + (tid_l - N) * 6, W);                // ((group - 1) N + k)
             __syncthreads();
             if (owner) {
                 const double *x1 = xe + k * 6, *x2 = xe + (N + k) * 6;
@@ -1231,12 +1208,10 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
         // everything but W leaves the registers BEFORE the register-hungry MIRROR
         // compact layout: g, b, W live in the global workspace (same [stage][entry] layout: a lane's stores of one array share
         // one address register and differ in the immediate offset); [B A] is kept as its 8 non-constant entries only
-        constexpr int es = 1;
-        const int gk = k * NV, bk = k * NX, wk = k * NP28;
         if (owner) {
 #pragma unroll
-            for (int i = 0; i < NV; i++) L.g[gk + i * es] = g[i];
-            if constexpr (!CP) {
+            for (int i = 0; i < NV; i++) L.g[k * NV + i] = g[i];
+            if constexpr (!CP) {                            // (store_dynamics, written out: as a call it moves this form's register allocation)
 #pragma unroll
                 for (int i = 0; i < NX * NV; i++) L.BA[k * NX * NV + i] = BA[i];
             }
@@ -1244,7 +1219,7 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
             d8[D8_XA] = BA[0 * NV + ZA]; d8[D8_XW] = BA[0 * NV + ZW]; d8[D8_XP] = BA[0 * NV + ZPSI]; d8[D8_XV] = BA[0 * NV + ZV];
             d8[D8_YA] = BA[1 * NV + ZA]; d8[D8_YW] = BA[1 * NV + ZW]; d8[D8_YP] = BA[1 * NV + ZPSI]; d8[D8_YV] = BA[1 * NV + ZV];
 #pragma unroll
-            for (int i = 0; i < NX; i++) L.b[bk + i * es] = xn[i] - L.z[(k + 1) * NV + NU + i];
+            for (int i = 0; i < NX; i++) L.b[k * NX + i] = xn[i] - L.z[(k + 1) * NV + NU + i];
         }
         // MIRROR: the two diagonal blocks of every stage in different lanes at the same time where the wave has the lanes (2 N <= 64) and the
         // exchange buffer -- the tail of the interior-point work region, dead while the stage blocks are built -- lies clear of the staging
@@ -1255,17 +1230,10 @@ __device__ __forceinline__ void linearise(const Lds &L, const Dims &d, int tid, 
 #pragma unroll
             for (int i = 0; i < NV; i++)
 #pragma unroll
-                for (int j = 0; j <= i; j++) L.W[wk + pidx(i, j) * es] = W[i][j];
+                for (int j = 0; j <= i; j++) L.W[k * NP28 + pidx(i, j)] = W[i][j];
         }
     }
-    if (tid == N) {
-        // terminal node: zero cost, no rows: MIRROR(0) = eps I on the state block
-        constexpr int es = 1;
-        const int wN = N * NP28, gN = N * NV;
-        for (int e = 0; e < NP28; e++) L.W[wN + e * es] = 0.0;
-        for (int i = NU; i < NV; i++) L.W[wN + pidx(i, i) * es] = d.reg_eps;
-        for (int i = 0; i < NV; i++) L.g[gN + i * es] = 0.0;
-    }
+    if (tid == N) linearise_terminal(L, d, N);
 }
 
 // ---- completeOneIteration (acados_solver_interface.cpp:162-204): cost, trajectories, res_eq, exit-code mapping ----

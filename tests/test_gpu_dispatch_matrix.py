@@ -25,14 +25,16 @@ VERDICT = ("exit_code", "qp_status", "sqp_iter", "qp_iter_total")
 
 
 def case(cid, expect, N, n_lin, M, n_slk=0, S=5, cm=0, gauss=False, rf=0, mode=0, B=16, lab=None, scene=None, ids=(1,), refused=False, also=None, prev=None,
-         doomed=()):
+         doomed=(), disc_offset=0.0):
     """expect: the instantiation of the slot the launch runs; also: {slot: name} of other slots the handle must fill; lab: TMPC_* switches of the lab
     library; scene: make_scene keywords instead of the ones derived from the row counts; B: an int, or an expression of the thresholds tmpc_kernel_info
     reports (cp_min_B, cp2_min_B, grid_max); refused: set_latency_mode(mode) returns False (no such variant: the default kernels run); prev: the
     launch size of (e) (the other side of a threshold) instead of a few trajectories; doomed: batch entries given contradictory topology rows
-    (test_gpu_parity._make_infeasible): their failure verdicts (exit code, QP status, SQP and interior-point counts) are compared with the oracle's too."""
+    (test_gpu_parity._make_infeasible): their failure verdicts (exit code, QP status, SQP and interior-point counts) are compared with the oracle's too;
+    disc_offset: ego_disc_0_offset of every stage (the scenes give 0): a non-zero offset couples psi with x, y in the rows' Hessian, so that W is not block
+    diagonal and MIRROR takes its 7 x 7 iteration -- without the curvature-aware cost, no other case reaches that branch."""
     return dict(id=cid, expect=expect, N=N, n_lin=n_lin, M=M, n_slk=n_slk, S=S, cm=cm, gauss=gauss, rf=rf, mode=mode, B=B, lab=lab or {},
-                scene=scene, ids=ids, refused=refused, also=also or {}, prev=prev, doomed=tuple(doomed))
+                scene=scene, ids=ids, refused=refused, also=also or {}, prev=prev, doomed=tuple(doomed), disc_offset=disc_offset)
 
 
 CFG5 = dict(M=8, slack=True, n_scenario=24)                      # SH-MPC: 24 scenario halfspaces, dims n_lin 0, M 0, n_slk 24
@@ -185,6 +187,13 @@ DISPATCH_CASES = [
     case("B=cp2_min_B (20,8) N=30", "fast<20,8,4,128,Solo,0>", 30, 8, 8, n_slk=12, B="cp2_min_B"),
     case("B=cp2_min_B+1 (20,8) N=30", "compact<20,8,4,128,0>", 30, 8, 8, n_slk=12, B="cp2_min_B+1", prev="cp2_min_B"),
     case("B=2*grid_max+3 (20,8) N=30", "compact<20,8,4,128,0>", 30, 8, 8, n_slk=12, B="2*grid_max+3", prev="cp2_min_B+1"),
+    # ---- a disc offset: the coupled W (MIRROR's 7 x 7 iteration) of the plain cost, on every form of the linearisation -- two waves, four waves in both
+    #      horizon ranges, one wave (mirror7_pair), two waves with the compact layout
+    case("offset <-1,9,4> nr=25 N=22", "fast<-1,9,4,128,Solo,0>", 22, 5, 6, disc_offset=0.1),
+    case("offset m3 <-1,4,12> nr=39 N=5", "fast<-1,4,12,256,ScanQuad,0>", 5, 12, 13, mode=3, disc_offset=0.1),
+    case("offset m3 (8,8) N=21", "fast<-1,6,8,256,ScanQuadT<2>,0>", 21, 8, 8, mode=3, disc_offset=0.1),
+    case("offset (8,8) N=5", "fast<8,8,3,64,Solo,0>", 5, 8, 8, disc_offset=0.1),
+    case("offset <-1,9,4> nr=25 N=22 cp2", "compact<-1,9,4,128,0>", 22, 5, 6, lab=CP2_0, disc_offset=0.1),
 ]
 
 # instantiations the pick functions name that no case above reaches
@@ -258,6 +267,10 @@ def _scenes(c, B):
     sc = scenes.make_batch(ids, N=c["N"], B=per, **skw)
     sc = {k: sc[k][:B] for k in ("xinit", "x0", "params")} | {"pm": sc["pm"]}
     assert sc["xinit"].shape[0] == B
+    if c["disc_offset"]:
+        sc["params"] = sc["params"].copy()
+        sc["offset_col"] = sc["pm"].index("ego_disc_0_offset")
+        sc["params"][:, :, sc["offset_col"]] = c["disc_offset"]
     if c["doomed"]:
         from test_gpu_parity import _make_infeasible
         sc = _make_infeasible(sc, list(c["doomed"]))
@@ -265,6 +278,8 @@ def _scenes(c, B):
         drop = tuple(f"lin_constraint_{j}_" for j in range(c["n_lin"], c["M"]))
         keep = [i for n, i in sc["pm"]._params.items() if not n.startswith(drop)]
         sc["params"] = np.ascontiguousarray(sc["params"][:, :, keep])
+        if "offset_col" in sc:
+            sc["offset_col"] = keep.index(sc["offset_col"])
     return sc
 
 
@@ -329,6 +344,20 @@ def test_dispatch_case(c, request, monkeypatch):
     for b in c["doomed"]:
         assert info["exit_code"][b] != 1 and got["qp_status"][b] == info["qp_status"][b], (b, info["exit_code"][b], got["qp_status"][b], info["qp_status"][b])
         assert got["qp_iter_total"][b] == info["qp_iter_total"][b], (b, got["qp_iter_total"][b], info["qp_iter_total"][b])
+    if c["disc_offset"]:
+        # The offset reaches the kernel: the zero-offset solve of the same batch gives other bits.  No bound on the size of the change: at N = 5 no obstacle of the
+        # scenes is within reach, the rows' multipliers stay near zero and the offset moves the result at rounding level only (2e-16, the oracle likewise) -- the
+        # cross entries of W are non-zero all the same, which is all MIRROR's `coupled` test asks; at N = 21, 22 it moves the trajectories by tenths of a metre.
+        zero = sc["params"].copy()
+        assert (zero[:, :, sc["offset_col"]] == c["disc_offset"]).all()
+        zero[:, :, sc["offset_col"]] = 0.0
+        s.set_batch(sc["xinit"], sc["x0"], zero); s.solve()
+        moved = np.abs(s.get()["xtraj"][ok] - got["xtraj"][ok]).max()
+        print(f"[dispatch] {c['id']}: the offset moves the trajectories by {moved:.2e}")
+        assert moved > 0.0
+        got2 = _solve(s, sc)
+        for f in FIELDS:
+            assert np.array_equal(got2[f], got[f]), f
     # (c) the parity check is not made on nothing
     assert ok.sum() >= B / 2, (int(ok.sum()), B)
     # (d) launch to launch

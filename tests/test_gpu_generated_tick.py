@@ -1,6 +1,6 @@
 """Control-tick kernel (tmpc_set_latency_mode 3, four waves per trajectory) of GENERATED solver libraries: the run-time-shape instantiations compiled
-around emitted stage functions, with the stage linearisation split over the four waves by content (csrc/tmpc_kernels.hpp
-linearise_generated_waves).  Every demo stack with rows, both horizon ranges: against the CPU oracle (the interface's rule for another
+around emitted stage functions, with the stage linearisation split over the four waves by content (csrc/tmpc_kernels.hpp, the
+four-wave form of linearise).  Every demo stack with rows, both horizon ranges: against the CPU oracle (the interface's rule for another
 factorisation of the Newton systems: _compare_relaxed_iterations), against the product library's hand-written kernels of the same mode, and -- the
 new exchange region -- bitwise from launch to launch, alone as in a batch, and after the LDS was filled with NaN patterns.
 
@@ -156,6 +156,39 @@ def test_cfg2_mode_3_equals_the_hand_written_mode_2_to_rounding():
     got = _solve(s, sc, 3)
     s.close()
     assert _against_product(got, sc, 2, relaxed_iterations=True) >= 32
+
+
+def test_cfg2_disc_offset_takes_the_coupled_mirror_against_its_own_default_kernel():
+    """A non-zero ego_disc_0_offset couples psi with x, y in the rows' Hessian: W is not block diagonal and the four-wave linearisation takes MIRROR's
+    7 x 7 iteration on wave 0, which no other test of a generated library reaches.  Mode 3 against the same library's default kernel, to rounding, at
+    N = 5 and at N = 20.  At N = 5 no obstacle of the scene is within reach, the rows' multipliers stay near zero and the offset moves the result at
+    rounding level only (W's cross entries are non-zero all the same, which is all MIRROR's `coupled` test asks); that the library reads the offset at
+    all is therefore checked at N = 20, in mode 3: the zero-offset solve differs by more than the tolerance of the comparison."""
+    from mpc_planner_amd import scenes
+    from test_gpu_parity import _generated_lib
+    col = _generated_lib("tmpc_cfg2")[1]["parameter_map"]["ego_disc_0_offset"]
+    for N in (5, 20):
+        sc = scenes.make_scene(3, N=N, M=8, B=16)
+        params = sc["params"].copy()
+        params[:, :, col] = 0.1
+        zero = dict(xinit=sc["xinit"], x0=sc["x0"], params=sc["params"])
+        sc = dict(xinit=sc["xinit"], x0=sc["x0"], params=params)
+        s = _gen_solver("tmpc_cfg2", N, sc["xinit"].shape[0])
+        base = _solve(s, sc, 0)
+        ok = base["exit_code"] == 1
+        assert ok.sum() >= ok.size // 2
+        got = _solve(s, sc, 3)
+        assert NARROW in s.kernel_info(), s.kernel_info()
+        assert np.array_equal(got["exit_code"], base["exit_code"]) and np.array_equal(got["sqp_iter"], base["sqp_iter"])
+        dit = np.abs(got["qp_iter_total"][ok] - base["qp_iter_total"][ok])
+        assert dit.max() <= 2 and (dit > 0).mean() <= 0.10, dit
+        err = max(np.abs(got["xtraj"][ok] - base["xtraj"][ok]).max(), np.abs(got["utraj"][ok] - base["utraj"][ok]).max())
+        moved = np.abs(_solve(s, zero, 3)["xtraj"][ok] - got["xtraj"][ok]).max()       # mode 3 both
+        print(f"[generated tick] disc offset 0.1, N = {N}: mode 3 against mode 0: {err:.2e} on {int(ok.sum())} solves; the offset moves mode 3's trajectories by {moved:.2e}")
+        assert err < 1e-8, err
+        if N == 20:
+            assert moved > 1e-8, moved
+        s.close()
 
 
 # ---- horizon edges on the same library at run-time N ------------------------------------------------------------------------------------------------
