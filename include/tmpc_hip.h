@@ -112,6 +112,8 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
 int tmpc_create_v2(tmpc_handle **out, const tmpc_dims *dims, uint32_t dims_size, int32_t B_max, int32_t device);
 /* Replaces Solver_acados_free + Solver_acados_free_capsule (:54,60). */
 void tmpc_destroy(tmpc_handle *h);
+/* h == NULL: why the calling thread's last tmpc_create* was refused, where the refusal has a message (the model bounds: a NaN, or
+ * lb[i] >= ub[i]); "null handle" otherwise. */
 const char *tmpc_last_error(const tmpc_handle *h);
 
 /* Replaces, for B solvers: ocp_nlp_constraints_model_set(lbx/ubx = xinit) (:124-125),

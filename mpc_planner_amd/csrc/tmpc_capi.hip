@@ -652,8 +652,18 @@ int tmpc_create_v2(tmpc_handle **out, const tmpc_dims *dims_in, uint32_t dims_si
     return tmpc_create(out, &d, B_max, device);
 }
 
+// why the calling thread's last tmpc_create* was refused, where the refusal has a message: there is no handle to keep it in (tmpc_last_error(NULL))
+static thread_local std::string g_create_error;
+
+static int refuse_create(const std::string &why)
+{
+    g_create_error = why;
+    return TMPC_ERR_INVALID;
+}
+
 int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t device)
 {
+    g_create_error.clear();
     if (!out || !dims || B_max <= 0) return TMPC_ERR_INVALID;
     *out = nullptr;
     {
@@ -665,6 +675,14 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
             !(dims->ipm_mu0 > 0.0) || !(dims->ipm_thr0 > 0.0) || (dims->cost_model != 0 && dims->cost_model != 1) ||
             (dims->riccati_form != TMPC_RICCATI_SCHUR && dims->riccati_form != TMPC_RICCATI_SQUARE_ROOT))
             return TMPC_ERR_INVALID;
+        // the model bounds: a NaN, or a box with nothing inside, is no problem to solve with (infinite bounds are not looked at here)
+        static const char *const var[TMPC_NV] = {"a", "w", "x", "y", "psi", "v", "spline"};
+        for (int i = 0; i < TMPC_NV; i++) {
+            if (dims->lb[i] != dims->lb[i] || dims->ub[i] != dims->ub[i]) return refuse_create(std::string("tmpc_create: a bound of ") + var[i] + " is NaN");
+            if (dims->lb[i] >= dims->ub[i])
+                return refuse_create(std::string("tmpc_create: lb[") + std::to_string(i) + "] >= ub[" + std::to_string(i) + "] (" + var[i] + ": " +
+                                     std::to_string(dims->lb[i]) + " >= " + std::to_string(dims->ub[i]) + ")");
+        }
 #ifdef TMPC_GENERATED_STAGE
         if (dims->n_lin != tmpc_gen::NH || dims->M != 0 || dims->n_slk != 0 || dims->slack != tmpc_gen::SLACK || dims->cost_model != 0 || dims->row_model != 0) return TMPC_ERR_INVALID;
 #endif
@@ -794,7 +812,7 @@ int tmpc_create(tmpc_handle **out, const tmpc_dims *dims, int32_t B_max, int32_t
 
 void tmpc_destroy(tmpc_handle *h) { delete h; }
 
-const char *tmpc_last_error(const tmpc_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *tmpc_last_error(const tmpc_handle *h) { return h ? h->err.c_str() : g_create_error.empty() ? "null handle" : g_create_error.c_str(); }
 
 int tmpc_set_batch(tmpc_handle *h, int32_t B, const double *xinit, const double *x0, const double *params)
 {

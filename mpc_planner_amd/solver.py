@@ -223,7 +223,8 @@ class BatchedSolver:
         self._h = C.c_void_p()
         rc = self.lib.tmpc_create(C.byref(self._h), C.byref(dims), self.B_max, int(device))
         if rc != 0:
-            raise TmpcError(f"tmpc_create failed with code {rc} (-1 invalid dims, -2 HIP error, -3 no gfx950 device)")
+            why = self.lib.tmpc_last_error(None).decode()          # (no handle: the refusal's message, where it has one)
+            raise TmpcError(f"tmpc_create failed with code {rc} (-1 invalid dims, -2 HIP error, -3 no gfx950 device)" + ("" if why == "null handle" else f": {why}"))
         self.N, self.npar = dims.N, dims.npar
 
     def close(self):

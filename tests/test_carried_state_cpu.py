@@ -35,6 +35,30 @@ def test_scene_supports_the_loop_and_the_oracle_agrees_with_itself_in_both_forms
     assert worst < 1e-8, worst                                      # (observed: at most 5.6e-9, on the Gaussian rows at N = 30; 1.5e-9 elsewhere)
 
 
+@pytest.mark.parametrize("cid", sorted(CS.BOUNDED_LOOPS))
+def test_scene_supports_the_loop_with_active_bounds(cid):
+    """The loop of CS.BOUNDED_LOOPS (no doomed entry): every entry succeeds at every tick with the three upper bounds active, in both Riccati forms, with the
+    same integers and the same active sets."""
+    import solver_option_cases as SC
+    scene, _ = CS.BOUNDED_LOOPS[cid]
+    opts = CS.bounded_options(cid)
+    (schur, differs), (sqrt, differs_sq) = CS.oracle_loop(cid, rf=0, opts=opts, scene=scene), CS.oracle_loop(cid, rf=1, opts=opts, scene=scene)
+    CS.check_bounded_loop_inputs(cid, schur, differs)
+    CS.check_bounded_loop_inputs(cid, sqrt, differs_sq)
+    worst = 0.0; counts = []
+    for t, (a, b) in enumerate(zip(schur, sqrt)):
+        for k in ("exit_code", "sqp_iter", "qp_status", "qp_iter_total"):
+            np.testing.assert_array_equal(a[k], b[k], err_msg=f"{cid}: tick {t}: {k}")
+        for var in CS.BOUNDED_LOOPS[cid][1]:
+            np.testing.assert_array_equal(SC.active_entries(a["xtraj"], a["utraj"], opts, "ub", var), SC.active_entries(b["xtraj"], b["utraj"], opts, "ub", var))
+        counts.append({var: int(SC.active_entries(a["xtraj"], a["utraj"], opts, "ub", var).sum()) for var in CS.BOUNDED_LOOPS[cid][1]})
+        worst = max(worst, np.abs(a["xtraj"] - b["xtraj"]).max(), np.abs(a["utraj"] - b["utraj"]).max())
+    print(f"[carried] {cid} with active bounds: scene {scene}: active entries per tick {counts}; Schur against square-root form {worst:.2e}; carried multipliers "
+          f"move the oracle by {differs:.2e}")
+    assert worst < 1e-8, worst
+    assert set(CS.BOUNDED_LOOPS) <= set(CS.LOOP_CASES)
+
+
 def test_every_kernel_family_has_a_closed_loop_case():
     import test_gpu_dispatch_matrix as T
     from test_dispatch_table import pick_instantiations

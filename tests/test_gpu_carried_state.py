@@ -41,11 +41,26 @@ GENERATED_DEFAULT = "fast<tmpc_gen::NH,0,3,64,Solo,0>"
 TIGHT = 1e-8
 
 
-def _case(cid):
+# The loop with model bounds that bind (tests/solver_option_cases.py "bounds upper": a, v and s from above) in force over the 4 ticks: case id -> (scene, the
+# upper bounds).  Derived on the CPU from the oracle's own loop on that scene; no doomed entry -- every Solver carries its multipliers through all 4 ticks.  (What a slot
+# keeps is pi and the general rows' lamh: a box row is linear and adds nothing to the Hessian.  The loop is here for the multipliers that were formed next to
+# binding box rows, and for the warm start that sits on a bound.)  Preconditions: tests/test_carried_state_cpu.py
+BOUNDED_LOOPS = {
+    "m0 (8,8) N=20": (19, dict(v=1.8, s=6.5, a=0.5)),             # active entries per tick: v 13 13 12 5, s 0 0 7 7, a 15 7 8 10
+    "m0 (20,8) N=30 cp2": (0, dict(v=1.93, s=10.58, a=0.46)),      # v 11 11 11 0, s 0 0 0 11, a 4 4 4 4
+}
+
+
+def bounded_options(cid):
+    import solver_option_cases as SC
+    return SC._box({}, BOUNDED_LOOPS[cid][1])
+
+
+def _case(cid, scene=None):
     import test_gpu_dispatch_matrix as T
     (c,) = [c for c in T.DISPATCH_CASES if c["id"] == cid]
     assert isinstance(c["B"], int) and not c["refused"] and not c["doomed"] and not c["disc_offset"], cid
-    return dict(c, ids=(SCENE_OF.get(cid, SCENE),), B=B)
+    return dict(c, ids=(SCENE_OF.get(cid, SCENE) if scene is None else scene,), B=B)
 
 
 def family(name):
@@ -64,28 +79,31 @@ def _shape_key(c, rf):
 _loops = {}
 
 
-def oracle_loop(cid, rf=None, fresh=True):
+def oracle_loop(cid, rf=None, fresh=True, opts=None, scene=None):
     """The closed loop on the oracle alone (every tick's inputs follow from the oracle's previous results; a failed entry keeps its old warm start):
     per tick a dict of the inputs (xinit, x0, params) and the oracle's results, and how far carrying the multipliers moves a trajectory against a
-    fresh oracle solve of the same inputs.  rf: the Riccati form of the oracle (default: the case's).  Cached per shape, shared, never written to."""
+    fresh oracle solve of the same inputs.  rf: the Riccati form of the oracle (default: the case's).  opts: orc_problem fields off their defaults, in force
+    over the whole loop -- and then no entry is doomed; scene: another scene than the case's.  Cached per shape, shared, never written to."""
     import oracle_lib as O
     import test_gpu_dispatch_matrix as T
     from mpc_planner_amd import modules as md
-    c = _case(cid)
+    c = _case(cid, scene)
     rf = c["rf"] if rf is None else rf
-    key = _shape_key(c, rf)
+    key = _shape_key(c, rf) + (None if opts is None else tuple(sorted(opts.items())),)
     if key in _loops and (_loops[key][1] is not None or not fresh):
         return _loops[key]
     sc = T._scenes(c, B)
     pm = sc["pm"]; N = c["N"]
     pb = T._problem(dict(c, rf=rf)); fr = T._problem(dict(c, rf=rf))
+    for k, v in (opts or {}).items():
+        setattr(pb, k, v); setattr(fr, k, v)
     xinit, x0, params = sc["xinit"].copy(), sc["x0"].copy(), sc["params"].copy()
     assert xinit.shape[0] == B and params.shape[2] == pb.npar
     pi = np.zeros((B, (N + 1) * O.NX)); lamh = np.zeros((B, N * pb.capacity[1]))
     ticks = []; differs = 0.0 if fresh else None
     for tick in range(TICKS):
         p_t = params.copy()
-        if tick == DOOMED_TICK:                                    # contradictory topology rows on one trajectory for this tick only
+        if tick == DOOMED_TICK and opts is None:                   # contradictory topology rows on one trajectory for this tick only
             for j, sg in ((0, 1.0), (1, -1.0)):
                 p_t[DOOMED, 1:, pm.index(f"lin_constraint_{j}_a1")] = sg
                 p_t[DOOMED, 1:, pm.index(f"lin_constraint_{j}_a2")] = 0.0
@@ -126,6 +144,29 @@ def check_loop_inputs(cid, ticks, differs):
         assert differs > 1e-7, (cid, differs)                      # carrying the multipliers matters on this scene (exact Hessian of the first RTI iteration)
 
 
+def check_bounded_loop_inputs(cid, ticks, differs):
+    """The same for the loop of BOUNDED_LOOPS: every entry succeeds at every tick; at every tick at least two of the three bounds are active
+    (tests/solver_option_cases.ACTIVE) in at least 2 entries each, and each bound is at some tick (the robot moves: v binds while it accelerates, s once the
+    horizon reaches it); no entry sits within THRESHOLD_GUARD of that threshold; no bound is violated; and carrying the multipliers matters."""
+    import solver_option_cases as SC
+    opts = bounded_options(cid)
+    ever = {var: 0 for var in BOUNDED_LOOPS[cid][1]}
+    for t, r in enumerate(ticks):
+        assert (r["exit_code"] == 1).all(), (cid, t, r["exit_code"])
+        lo, hi = SC.gaps(r["xtraj"], r["utraj"], opts["lb"], opts["ub"])
+        assert min(lo.min(), hi.min()) > -SC.VIOLATED, (cid, t)
+        now = 0
+        for var in ever:
+            gap = hi[:, SC.VARS.index(var)]
+            assert (np.abs(np.abs(gap) - SC.ACTIVE) > SC.THRESHOLD_GUARD).all(), (cid, t, var, gap)
+            n = int((np.abs(gap) < SC.ACTIVE).sum())
+            ever[var] = max(ever[var], n); now += n >= 2
+        assert now >= 2, (cid, t)
+    assert min(ever.values()) >= 2, (cid, ever)
+    if differs is not None:
+        assert differs > 1e-7, (cid, differs)
+
+
 # ---- handles ---------------------------------------------------------------------------------------------------------------------------------------
 def _lab(c, request, monkeypatch):
     if c["lab"]:
@@ -134,11 +175,15 @@ def _lab(c, request, monkeypatch):
         request.getfixturevalue("lab_library")
 
 
-def _handle(c, B_max=B, launch=B):
-    """A handle of the case's shape in the case's mode; the slot a launch of `launch` entries runs holds the expected instantiation."""
+def _handle(c, B_max=B, launch=B, opts=None):
+    """A handle of the case's shape in the case's mode; the slot a launch of `launch` entries runs holds the expected instantiation.  opts: tmpc_dims fields
+    off their defaults."""
     import test_gpu_dispatch_matrix as T
     from mpc_planner_amd import solver
-    s = solver.BatchedSolver(T._dims(c), B_max=B_max)
+    dims = T._dims(c)
+    for k, v in (opts or {}).items():
+        setattr(dims, k, v)
+    s = solver.BatchedSolver(dims, B_max=B_max)
     assert s.set_latency_mode(c["mode"]) or c["mode"] == 0
     slots, th = T._slots(s.kernel_info())
     slot = T._running(slots, c["mode"], launch, th)
@@ -174,11 +219,14 @@ def _against_oracle(g, r, relaxed, what):
     return max((np.abs(g["xtraj"][ok] - r["xtraj"][ok]) / sx).max(), (np.abs(g["utraj"][ok] - r["utraj"][ok]) / su).max())
 
 
-def _closed_loop(cid, make, relaxed):
+def _closed_loop(cid, make, relaxed, opts=None, scene=None):
     """The loop on handles `make()` builds: per tick against the oracle; then the doomed entry's tick after its failure against a handle with nothing
-    stored."""
-    ticks, differs = oracle_loop(cid)
-    check_loop_inputs(cid, ticks, differs)
+    stored.  opts, scene: of oracle_loop (the handles `make()` builds have the same options) -- no entry is doomed then."""
+    ticks, differs = oracle_loop(cid, opts=opts, scene=scene)
+    if opts is None:
+        check_loop_inputs(cid, ticks, differs)
+    else:
+        check_bounded_loop_inputs(cid, ticks, differs)
     N = ticks[0]["utraj"].shape[1]
     s = make()
     worst = 0.0; got = []
@@ -191,6 +239,18 @@ def _closed_loop(cid, make, relaxed):
     print(f"[carried] {cid}: worst rel diff over {TICKS} ticks {worst:.3e}; carried multipliers move the oracle by {differs:.2e}")
     assert worst < HARD, worst
     assert worst < TIGHT, worst
+    if opts is not None:
+        import solver_option_cases as SC
+        # the bounds bind on the device where they bind on the oracle, tick by tick; none is violated; and the multipliers the Solvers carried matter
+        for t, (g, r) in enumerate(zip(got, ticks)):
+            lo, hi = SC.gaps(g["xtraj"], g["utraj"], opts["lb"], opts["ub"])
+            assert min(lo.min(), hi.min()) > -SC.VIOLATED, (cid, t)
+            for var in BOUNDED_LOOPS[cid][1]:
+                want = SC.active_entries(r["xtraj"], r["utraj"], opts, "ub", var)
+                np.testing.assert_array_equal(SC.active_entries(g["xtraj"], g["utraj"], opts, "ub", var), want, err_msg=f"{cid}: tick {t}: ub {var}")
+        f = make(); fresh = _tick(f, ticks[2]); f.close()
+        assert any(not np.array_equal(got[2]["xtraj"][b], fresh["xtraj"][b]) for b in range(B)), cid
+        return worst
     if N == 2:
         return worst
     # the doomed Solver's first solve after its failure: bit for bit what a handle with nothing stored returns for it (where its stale warm start dooms it
@@ -214,6 +274,21 @@ def test_closed_loop_carries_multipliers_like_the_oracle(cid, request, monkeypat
         return s
     probe = make(); probe.close()
     _closed_loop(cid, make, relaxed=slot_of["slot"] == "lat2")
+
+
+@pytest.mark.parametrize("cid", sorted(BOUNDED_LOOPS))
+def test_closed_loop_carries_the_multipliers_of_active_bounds(cid, request, monkeypatch):
+    """The loop with three model bounds binding at every tick."""
+    c = _case(cid, BOUNDED_LOOPS[cid][0])
+    _lab(c, request, monkeypatch)
+    opts = bounded_options(cid)
+    slot_of = {}
+
+    def make():
+        s, slot_of["slot"] = _handle(c, opts=opts)
+        return s
+    probe = make(); probe.close()
+    _closed_loop(cid, make, relaxed=slot_of["slot"] == "lat2", opts=opts, scene=BOUNDED_LOOPS[cid][0])
 
 
 @pytest.mark.parametrize("mode", [0, 3])

@@ -130,6 +130,39 @@ def test_cfg2_tick_of_64(scene):
     s.close()
 
 
+@pytest.mark.parametrize("mode", [0, 3])
+@pytest.mark.parametrize("oid", ["bounds upper", "all off + bounds upper"])
+def test_cfg2_with_active_bounds_and_options_off_their_defaults(oid, mode):
+    """The generated T-MPC stack under two option cases of tests/solver_option_cases.py (model bounds that bind; those plus dt, erk_steps, reg_eps, ipm_mu0,
+    ipm_thr0, n_sqp off their defaults), on its default kernel and on its control-tick kernel, against the hand-written cfg-2 oracle problem under the
+    same options: integers equal, 1e-8, the discrimination rule and the active sets of tests/test_gpu_solver_options.py."""
+    import solver_option_cases as SC
+    import test_gpu_dispatch_matrix as T
+    from test_gpu_carried_state import GENERATED_DEFAULT
+    from test_gpu_parity import _compare
+    r = SC.oracle_runs("N=20 (8,8) S=5", oid)
+    sc, opts, xt, ut, info = r["sc"], r["opts"], r["xt"], r["ut"], r["info"]
+    B = sc["xinit"].shape[0]
+    s = _gen_solver("tmpc_cfg2", 20, B, **opts)
+    assert s.set_latency_mode(mode) or mode == 0
+    slots, th = T._slots(s.kernel_info())
+    slot = T._running(slots, mode, B, th)
+    assert (slot, slots[slot]) == (("lat3", NARROW.split("=")[1]) if mode else ("default", GENERATED_DEFAULT)), (slot, slots)
+    assert s.npar == sc["params"].shape[2]
+    s.set_batch(sc["xinit"], sc["x0"], sc["params"]); s.solve(); got = s.get()
+    assert (info["exit_code"] == 1).all()
+    worst = max(_compare(got, xt, ut, info))
+    dist = SC.distance(got["xtraj"], got["utraj"], xt, ut)
+    assert (10.0 * dist[r["mask"]] <= r["moved"][r["mask"]]).all() and r["mask"].mean() >= 0.25, (dist, r["moved"])
+    lo, hi = SC.gaps(got["xtraj"], got["utraj"], opts["lb"], opts["ub"])
+    assert min(lo.min(), hi.min()) > -SC.VIOLATED
+    for side, var in SC.OPTION[oid]["active"]:
+        want = SC.active_entries(xt, ut, opts, side, var)
+        assert want.sum() >= 2 and np.array_equal(SC.active_entries(got["xtraj"], got["utraj"], opts, side, var), want), (side, var)
+    print(f"[generated tick] {oid}: {slot}={slots[slot]}: worst rel diff {worst:.2e}")
+    s.close()
+
+
 @pytest.mark.parametrize("scene", [1, 4])
 def test_cfg2_mode_2_keeps_an_empty_slot(scene):
     sc, _ = _cfg2_case(scene)

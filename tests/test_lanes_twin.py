@@ -84,3 +84,44 @@ def test_lane_program_matches_oracle(name):
         assert np.abs(g["res_eq"][ok] - info["res_eq"][ok]).max() < 1e-8
         n_ok += int(ok.sum())
     assert n_ok >= 3
+
+
+# The lane program under option cases of tests/solver_option_cases.py, on the cfg 2 shape: model bounds that bind from above and from below, everything off its
+# default at once, and the three options a kernel can keep at their defaults without the others noticing (erk_steps at a dt where it shows, ipm_mu0 and
+# ipm_thr0 apart, so that a swap shows).  The same cases run on the device in tests/test_gpu_parity.py::test_throughput_mode_option_cases
+OPTION_CASES = ["bounds upper", "bounds w lower", "all off + bounds upper", "erk 1 at dt 0.4", "mu0 only 0.1", "thr0 only 0.1"]
+OPTION_SHAPE = "N=20 (8,8) S=5"
+
+
+def check_option_case(got, oid):
+    """The assertions of tests/test_gpu_solver_options.py on a result of the lane program: the oracle's integers, 1e-8, discrimination, active sets."""
+    import solver_option_cases as SC
+    r = SC.oracle_runs(OPTION_SHAPE, oid)
+    xt, ut, info, opts = r["xt"], r["ut"], r["info"], r["opts"]
+    assert (info["exit_code"] == 1).all() and r["mask"].mean() >= 0.25
+    for k in SC.VERDICT:
+        np.testing.assert_array_equal(got[k], info[k], err_msg=k)
+    dist = SC.distance(got["xtraj"], got["utraj"], xt, ut)
+    pobj = (np.abs(got["pobj"] - info["pobj"]) / np.maximum(np.abs(info["pobj"]), 1.0)).max()
+    assert dist.max() < 1e-8 and pobj < 1e-8, (dist.max(), pobj)
+    ints_base = np.ones(len(dist), bool)
+    for k in SC.VERDICT:
+        ints_base &= got[k] == r["ib"][k]
+    told = (10.0 * dist <= r["moved"]) | ~ints_base                # (the integers are the option run's: asserted above)
+    assert told[r["mask"]].all(), (dist[r["mask"]], r["moved"][r["mask"]])
+    lo, hi = SC.gaps(got["xtraj"], got["utraj"], opts.get("lb", SC.DEFAULT_LB), opts.get("ub", SC.DEFAULT_UB))
+    assert min(lo.min(), hi.min()) > -SC.VIOLATED
+    for side, var in SC.OPTION[oid]["active"]:
+        want = SC.active_entries(xt, ut, opts, side, var)
+        assert want.sum() >= 2 and np.array_equal(SC.active_entries(got["xtraj"], got["utraj"], opts, side, var), want), (side, var)
+    return dist.max()
+
+
+@pytest.mark.parametrize("oid", OPTION_CASES)
+def test_lane_program_option_cases(oid):
+    import solver_option_cases as SC
+    r = SC.oracle_runs(OPTION_SHAPE, oid)
+    dims = solver.default_dims(**CASES["cfg2"][1], **r["opts"])
+    sc = r["sc"]
+    worst = check_option_case(twin_solve(dims, sc["xinit"], sc["x0"], sc["params"]), oid)
+    print(f"[lanes twin] {oid}: worst rel diff {worst:.2e}; the option matters on {int(r['mask'].sum())}/{len(r['mask'])} entries")
