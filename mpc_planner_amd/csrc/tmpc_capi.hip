@@ -1682,3 +1682,66 @@ int tmpc_debug_sweep_profile(tmpc_handle *h, uint64_t *out, int32_t n)
 #endif
 
 }  // extern "C"
+
+#ifdef TMPC_LAB_SWITCHES
+// Lab library only (not part of include/tmpc_hip.h): the wave and workgroup reductions of the solve kernels (tmpc_kernels.hpp) on caller-supplied lane
+// values, one case per workgroup of `threads` (64, 128 or 256) threads -- tests/test_gpu_wave_reductions.py compares every result bit for bit with a
+// numpy restatement of the same pairing order.  in: [n_cases][5][threads] doubles (arrays 0 .. 3: the four residual maxima of blk_residuals, array 4:
+// its sum; the single-array reductions take array 0).  out: [n_cases][LAB_RED_SCALARS + 3 threads]:
+//   [0, 4) wave_max of wave w, [8, 12) wave_min, [12, 16) wave_sum (waves the block does not have: untouched), 16 blk_max, 18 blk_min, 19 blk_sum,
+//   20 / 21 blk_residuals' worst / mu; [4, 8), [28, 32), [24, 28) maximum, minimum and sum of wave w by lab_reduce_identity, the network with the
+//   operation's identity moved into the vacated lanes and fmax / fmin on the operands (the form the kernels had before the fill was dropped);
+//   then per lane stage_sum3, stage_sum_quad<false>, stage_sum_quad<true>.
+constexpr int LAB_RED_SCALARS = 32;
+template <typename Op>
+__device__ __forceinline__ double lab_reduce_identity(double x, double identity, Op op)
+{
+    x = op(x, tmpc::dpp_move<0x111, 0xf>(x, identity)); x = op(x, tmpc::dpp_move<0x112, 0xf>(x, identity));
+    x = op(x, tmpc::dpp_move<0x114, 0xf>(x, identity)); x = op(x, tmpc::dpp_move<0x118, 0xf>(x, identity));
+    x = op(x, tmpc::dpp_move<0x142, 0xa>(x, identity)); x = op(x, tmpc::dpp_move<0x143, 0xc>(x, identity));
+    return __shfl(x, 63, 64);
+}
+template <int NTH>
+__global__ __launch_bounds__(NTH) void tmpc_lab_reductions_kernel(const double *in, double *out)
+{
+    __shared__ double scr[64];
+    const int tid = threadIdx.x, w = tid >> 6;
+    const double *x = in + (size_t)blockIdx.x * 5 * NTH;
+    double *o = out + (size_t)blockIdx.x * (LAB_RED_SCALARS + 3 * NTH);
+    const double a = x[tid], b = x[NTH + tid], c = x[2 * NTH + tid], m = x[3 * NTH + tid], s = x[4 * NTH + tid];
+    const double wmax = tmpc::wave_max(a), wmin = tmpc::wave_min(a), wsum = tmpc::wave_sum(a);
+    const double imax = lab_reduce_identity(a, -__builtin_huge_val(), [](double p, double q) { return fmax(p, q); });
+    const double imin = lab_reduce_identity(a, __builtin_huge_val(), [](double p, double q) { return fmin(p, q); });
+    const double isum = lab_reduce_identity(a, 0.0, [](double p, double q) { return p + q; });
+    if ((tid & 63) == 0) { o[w] = wmax; o[4 + w] = imax; o[8 + w] = wmin; o[12 + w] = wsum; o[24 + w] = isum; o[28 + w] = imin; }
+    const double bmax = tmpc::blk_max<NTH>(a, scr, tid, 2), bmin = tmpc::blk_min<NTH>(a, scr, tid, 4), bsum = tmpc::blk_sum<NTH>(a, scr, tid, 5);
+    double worst, mu = s;
+    tmpc::blk_residuals<NTH>(worst, a, b, c, m, mu, scr, tid);
+    if (tid == 0) { o[16] = bmax; o[18] = bmin; o[19] = bsum; o[20] = worst; o[21] = mu; }
+    o[LAB_RED_SCALARS + tid] = tmpc::stage_sum3(a);
+    o[LAB_RED_SCALARS + NTH + tid] = tmpc::stage_sum_quad<false>(a);
+    o[LAB_RED_SCALARS + 2 * NTH + tid] = tmpc::stage_sum_quad<true>(a);
+}
+
+extern "C" int tmpc_lab_reductions(int32_t threads, int32_t n_cases, const double *in_host, double *out_host)
+{
+    if ((threads != 64 && threads != 128 && threads != 256) || n_cases < 1 || n_cases > 4096 || !in_host || !out_host) return TMPC_ERR_INVALID;
+    const size_t n_in = (size_t)n_cases * 5 * threads, n_out = (size_t)n_cases * (LAB_RED_SCALARS + 3 * threads);
+    double *din = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc((void **)&din, n_in * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void **)&dout, n_out * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(din, in_host, n_in * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dout, out_host, n_out * sizeof(double), hipMemcpyHostToDevice);      // (slots the kernel leaves alone keep the caller's values)
+    if (e == hipSuccess) {
+        if (threads == 64) hipLaunchKernelGGL(tmpc_lab_reductions_kernel<64>, dim3(n_cases), dim3(64), 0, 0, din, dout);
+        else if (threads == 128) hipLaunchKernelGGL(tmpc_lab_reductions_kernel<128>, dim3(n_cases), dim3(128), 0, 0, din, dout);
+        else hipLaunchKernelGGL(tmpc_lab_reductions_kernel<256>, dim3(n_cases), dim3(256), 0, 0, din, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out_host, dout, n_out * sizeof(double), hipMemcpyDeviceToHost);
+    if (din) (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    return e == hipSuccess ? TMPC_OK : TMPC_ERR_HIP;
+}
+#endif

@@ -369,6 +369,12 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
         }
         else return c0 * x + c1 * y + c2 * pp + CU(s) * vec[VAR(s)];
     };
+    // SLIM: the maxima of the row passes are taken by fmax_quiet (csrc/tmpc_kernels.hpp: their operands are results of arithmetic) -- in every instantiation
+    // but the two-waves-per-SIMD ones with more than ten rows per lane, which sit at their 256 registers: the compiler's allocation of that form spills
+    // there (the build refuses scratch), so they keep fmax
+    constexpr bool SLIM = !(OCC2 && RPL > 10);
+    // (slot kinds are ordered: a shape has a general slot, KIND 0, iff its first slot is one; the run-time shapes have none and skip the fold's last step)
+    constexpr bool FOLD0 = SLIM && C::template KIND<0> == 0;
     team.sync();                                             // staging is dead from here on
     // QP start: dz = 0 except dx_0 = xinit - x_0; duals 0
     for (int e = tid_q; e < (N + 1) * NV; e += NT) L.v[e] = 0.0;
@@ -499,9 +505,9 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
 #pragma unroll
             for (int i = 0; i < NV; i++) {
                 double acc = rgk[i];
-                if (i >= NU && ks >= 1) acc -= po[i - NU];
-                const bool skip = (ks == N && i < NU) || (ks == 0 && i >= NU);
-                acc = skip ? 0.0 : acc;
+                // inputs: no entry at node N; states: - pi_k from node 1 on, no entry at node 0 (dx_0 is fixed) -- one select per element
+                if (i < NU) acc = ks == N ? 0.0 : acc;
+                else acc = ks >= 1 ? acc - po[i >= NU ? i - NU : 0] : 0.0;
                 if (nd) { L.rg[mul24(ks, NV) + i] = acc; L.gh[mul24(ks, NV) + i] = acc; }
             }
             {                                              // rb = b + [B A] v_k - dx_{k+1}, row by row
@@ -537,7 +543,7 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
                 const double comp = lam[s] * t[s];
                 const double dd = lam[s] * INVT(s);
                 const double w = dd * rds;
-                if (a) { res_d = fmax(res_d, fabs(r)); res_m = fmax(res_m, comp); mu += comp; }
+                if (a) { res_d = row_max_abs<SLIM>(res_d, r); res_m = row_max<SLIM>(res_m, comp); mu += comp; }
                 if constexpr (K != 1) {
                     gs0 += lam[s] * c0s; gs1 += lam[s] * c1s; gs2 += lam[s] * c2s;
                     rs0 += w * c0s; rs1 += w * c1s; rs2 += w * c2s;
@@ -560,12 +566,12 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
             // aligned quads: two DPP quad permutations sum each quad in registers, its first lane adds -- three-way conflicts, like the one-wave kernels.
             if constexpr (QSUM) {
                 // (eight lanes per stage: a stage is half a 16-lane row, so one row shift by four folds its second quad into the first: no conflict left)
-                auto quad = [](double x) { x += dpp_move<0xB1, 0xf>(x, 0.0); x += dpp_move<0x4E, 0xf>(x, 0.0); if constexpr (LPS == 8) x += dpp_shift_zero<0x104>(x); return x; };      // quad_perm [1,0,3,2], then [2,3,0,1]; row_shl:4
+                auto quad = [](double x) { return stage_sum_quad<LPS == 8>(x); };
                 gs0 = quad(gs0); gs1 = quad(gs1); gs2 = quad(gs2); rs0 = quad(rs0); rs1 = quad(rs1); rs2 = quad(rs2);
                 h00 = quad(h00); h10 = quad(h10); h11 = quad(h11); h20 = quad(h20); h21 = quad(h21); h22 = quad(h22);
             }
             if constexpr (TSUM) {                 // three lanes per stage: x[l] + x[l + 1] + x[l + 2] by two wave shifts (wave_shl:1), the stage's first lane adds
-                auto tri3 = [](double x) { const double t = x + dpp_shift_zero<0x130>(x); return x + dpp_shift_zero<0x130>(t); };
+                auto tri3 = [](double x) { return stage_sum3(x); };
                 gs0 = tri3(gs0); gs1 = tri3(gs1); gs2 = tri3(gs2); rs0 = tri3(rs0); rs1 = tri3(rs1); rs2 = tri3(rs2);
                 h00 = tri3(h00); h10 = tri3(h10); h11 = tri3(h11); h20 = tri3(h20); h21 = tri3(h21); h22 = tri3(h22);
             }
@@ -582,7 +588,7 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
         double res_g = 0.0;
         for (int e = tl; e < (N + 1) * NV; e += NT) {
             const double r = L.rg[e];                                          // (load, then select: see the residual loops above)
-            res_g = fmax(res_g, (e >= NU && e < NV) ? 0.0 : fabs(r));          // dx_0 is fixed: its stationarity row is not a residual
+            res_g = fmax_quiet_abs(res_g, (e >= NU && e < NV) ? 0.0 : r);      // dx_0 is fixed: its stationarity row is not a residual
         }
         double res_worst;
         blk_residuals<NTH>(res_worst, res_g, res_b, res_d, res_m, mu, L.scr, tl);
@@ -628,14 +634,19 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
         {
             const double dx = L.dv[mul24(kk, NV) + ZX], dy = L.dv[mul24(kk, NV) + ZY], dp = L.dv[mul24(kk, NV) + ZPSI];
             const double vx = L.v[mul24(kk, NV) + ZX], vy = L.v[mul24(kk, NV) + ZY], vp = L.v[mul24(kk, NV) + ZPSI];
+            // general slots of a tuned shape (KIND 0) are live on exactly the stage lanes: their ratios are folded unselected (a dead lane's value, NaN
+            // included, goes nowhere else) and selected once behind the pass; gmax >= +0.0, so the fold with +0.0 on the other lanes returns its bits
+            double gmax0 = 0.0;
             static_for<0, RPL>([&](auto s_) {
                 constexpr int s = decltype(s_)::value;
                 const bool a = ACT(s_);
                 const double dt = row_dt(s_, dx, dy, dp, vx, vy, vp);
                 if constexpr (!DIET_DT) dt_[DIET_DT ? 0 : s] = dt;
                 const double q = dt * INVT(s);
-                gmax = fmax(gmax, a ? fmax(-q, 1.0 + q) : 0.0);
+                if constexpr (SLIM && C::template KIND<s> == 0) gmax0 = fmax_quiet(gmax0, fmax(-q, 1.0 + q));
+                else gmax = row_max<SLIM>(gmax, a ? fmax(-q, 1.0 + q) : 0.0);
             });
+            if constexpr (FOLD0) gmax = fmax_quiet(gmax, stage_lane ? gmax0 : 0.0);
             gmax = blk_max<NTH>(gmax, L.scr, tl, 5);
             a_aff = gmax > 1.0 ? 1.0 / gmax : 1.0;          // min(1, alpha_max)
             ROW_PASS_BEGIN();
@@ -674,11 +685,11 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
                 if constexpr (K != 0) { if (a && (K == 1 || (box >> s & 1))) lds_add(&L.gh[mul24(k, NV) + VARK(s_)], w * CUK(s_)); }
             });
             if constexpr (QSUM) {
-                auto quad = [](double x) { x += dpp_move<0xB1, 0xf>(x, 0.0); x += dpp_move<0x4E, 0xf>(x, 0.0); if constexpr (LPS == 8) x += dpp_shift_zero<0x104>(x); return x; };
+                auto quad = [](double x) { return stage_sum_quad<LPS == 8>(x); };
                 cs0 = quad(cs0); cs1 = quad(cs1); cs2 = quad(cs2);
             }
             if constexpr (TSUM) {
-                auto tri3 = [](double x) { const double t = x + dpp_shift_zero<0x130>(x); return x + dpp_shift_zero<0x130>(t); };
+                auto tri3 = [](double x) { return stage_sum3(x); };
                 cs0 = tri3(cs0); cs1 = tri3(cs1); cs2 = tri3(cs2);
             }
             if (stage_lane && (!QSUM || (c & (LPS == 8 ? 7 : 3)) == 0) && (!TSUM || c == 0 || c == 3)) { lds_add(&L.gh[mul24(k, NV) + ZX], cs0); lds_add(&L.gh[mul24(k, NV) + ZY], cs1); lds_add(&L.gh[mul24(k, NV) + ZPSI], cs2); }
@@ -693,6 +704,7 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
         ROW_PASS_BEGIN();
         const double dxc = L.dv[mul24(kk, NV) + ZX], dyc = L.dv[mul24(kk, NV) + ZY], dpc = L.dv[mul24(kk, NV) + ZPSI];
         const double vxc = L.v[mul24(kk, NV) + ZX], vyc = L.v[mul24(kk, NV) + ZY], vpc = L.v[mul24(kk, NV) + ZPSI];
+        double gmax0c = 0.0;                           // (general slots: as in the affine pass above)
         static_for<0, RPL>([&](auto s_) {
             constexpr int s = decltype(s_)::value;
             const bool a = ACT(s_);
@@ -700,8 +712,10 @@ __device__ __forceinline__ int ipm_fast(const Lds &L, const Dims &d, int tid, co
             if constexpr (!DIET_DT) dt_[DIET_DT ? 0 : s] = dt;
             const double it_ = INVT(s);
             const double dl = -qt[s] - lam[s] * it_ * dt;
-            gmax = fmax(gmax, a ? fmax(-dt * it_, -dl * rcp_nr(lam[s])) : 0.0);
+            if constexpr (SLIM && C::template KIND<s> == 0) gmax0c = fmax_quiet(gmax0c, fmax(-dt * it_, -dl * rcp_nr(lam[s])));
+            else gmax = row_max<SLIM>(gmax, a ? fmax(-dt * it_, -dl * rcp_nr(lam[s])) : 0.0);
         });
+        if constexpr (FOLD0) gmax = fmax_quiet(gmax, stage_lane ? gmax0c : 0.0);
         gmax = blk_max<NTH>(gmax, L.scr, tl, 7);
         const double alpha = 0.999 > gmax ? 1.0 : 0.999 / gmax;        // min(1, 0.999 alpha_max)
         pf.stop(PH_ROWS);

@@ -214,42 +214,95 @@ __device__ __forceinline__ double dpp_move(double x, double identity)
     o.i[1] = __builtin_amdgcn_update_dpp(o.i[1], u.i[1], CTRL, ROW_MASK, 0xf, false);
     return o.d;
 }
-// row shift whose vacated lanes read 0 (bound_ctrl:0): for sums no identity value has to be materialised first
-template <int CTRL>
+// DPP move whose lanes without a source read 0 (bound_ctrl:0): no value has to be moved into the destination first (two v_mov_b32 per step).  Rows
+// outside ROW_MASK are not written and hold no defined value afterwards: only for callers that never read them (the row broadcasts of wave_reduce)
+template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ double dpp_shift_zero(double x)
 {
     union { double d; int i[2]; } u, o;
     u.d = x;
-    o.i[0] = __builtin_amdgcn_mov_dpp(u.i[0], CTRL, 0xf, 0xf, true);
-    o.i[1] = __builtin_amdgcn_mov_dpp(u.i[1], CTRL, 0xf, 0xf, true);
+    o.i[0] = __builtin_amdgcn_mov_dpp(u.i[0], CTRL, ROW_MASK, 0xf, true);
+    o.i[1] = __builtin_amdgcn_mov_dpp(u.i[1], CTRL, ROW_MASK, 0xf, true);
     return o.d;
 }
-template <typename Op>
-__device__ __forceinline__ double wave_reduce(double x, double identity, Op op)
+// fmax / fmin of two doubles that are never SIGNALLING NaNs (results of arithmetic, constants, quiet NaNs): the bits of fmax(a, b) / fmin(a, b) without the
+// canonicalising v_max_f64 x, x, x that they put in front of every operand the compiler cannot prove quiet (a DPP move's result, a select, a value
+// carried round a loop).  fmax_quiet_abs(a, b) = fmax(a, fabs(b)).  The kernels run in the default IEEE mode (MODE.IEEE = 1), in which v_max_f64 / v_min_f64
+// return the other operand for a QUIET NaN, as fmax / fmin do, but a quieted NaN for a SIGNALLING one, where fmax / fmin (which canonicalise first) return the
+// other operand: never pass a value loaded from caller memory.  Today's callers pass residuals, step ratios and LDS entries the kernel computed itself.
+// (Inline assembly: the compiler neither folds constants through these nor sees their latency; they stand where the operands are run-time values.)
+__device__ __forceinline__ double fmax_quiet(double a, double b)
 {
-    x = op(x, dpp_move<0x111, 0xf>(x, identity));      // row_shr:1
-    x = op(x, dpp_move<0x112, 0xf>(x, identity));      // row_shr:2
-    x = op(x, dpp_move<0x114, 0xf>(x, identity));      // row_shr:4
-    x = op(x, dpp_move<0x118, 0xf>(x, identity));      // row_shr:8
-    x = op(x, dpp_move<0x142, 0xa>(x, identity));      // row_bcast:15 into rows 1 and 3
-    x = op(x, dpp_move<0x143, 0xc>(x, identity));      // row_bcast:31 into rows 2 and 3
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double fmin_quiet(double a, double b)
+{
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double fmax_quiet_abs(double a, double b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// the running maxima of the interior-point row passes: QUIET chooses fmax_quiet (see SLIM in ipm_fast, tmpc_fast.hpp)
+template <bool QUIET> __device__ __forceinline__ double row_max(double a, double b) { if constexpr (QUIET) return fmax_quiet(a, b); else return fmax(a, b); }
+template <bool QUIET> __device__ __forceinline__ double row_max_abs(double a, double b) { if constexpr (QUIET) return fmax_quiet_abs(a, b); else return fmax(a, fabs(b)); }
+// The wave's result is lane 63's, and no vacated lane's fill reaches it: the row shifts are an inclusive scan, in which lane 15 of a row combines, step by
+// step, lanes that have themselves only combined lanes of the row (15 <- 14, 13 <- 12 | 15 <- 13 | 15 <- 11, 11 <- 7 | 15 <- 7); row 3 is written by both
+// broadcasts, from lane 47 (read in the step that would write row 2) and lane 31 (row 1, written by the first broadcast).  So no identity value is moved
+// in: vacated lanes read 0, rows a broadcast does not write are left undefined (three instructions per step where there were five or six).
+// Precondition: all 64 lanes of the wave are enabled (EXEC full).  A disabled SOURCE lane reads 0 under bound_ctrl:0 -- it no longer reads the operation's
+// identity, as it did when one was moved in -- so a reduction under divergent control flow would take zeros for the missing lanes.  Every call site is
+// reached by whole waves (the interior-point loop's `active` and the epilogue are uniform per wave).
+template <typename Op>
+__device__ __forceinline__ double wave_reduce(double x, Op op)
+{
+    x = op(x, dpp_shift_zero<0x111>(x));            // row_shr:1
+    x = op(x, dpp_shift_zero<0x112>(x));            // row_shr:2
+    x = op(x, dpp_shift_zero<0x114>(x));            // row_shr:4
+    x = op(x, dpp_shift_zero<0x118>(x));            // row_shr:8
+    x = op(x, dpp_shift_zero<0x142, 0xa>(x));       // row_bcast:15 into rows 1 and 3
+    x = op(x, dpp_shift_zero<0x143, 0xc>(x));       // row_bcast:31 into rows 2 and 3
     union { double d; int i[2]; } u;
     u.d = x;
     u.i[0] = __builtin_amdgcn_readlane(u.i[0], 63);
     u.i[1] = __builtin_amdgcn_readlane(u.i[1], 63);
     return u.d;
 }
+// (every caller reduces results of arithmetic: fmax_quiet / fmin_quiet)
 __device__ __forceinline__ double wave_max(double x)
 {
-    return wave_reduce(x, -__builtin_huge_val(), [](double a, double b) { return fmax(a, b); });
+    return wave_reduce(x, [](double a, double b) { return fmax_quiet(a, b); });
 }
 __device__ __forceinline__ double wave_min(double x)
 {
-    return wave_reduce(x, __builtin_huge_val(), [](double a, double b) { return fmin(a, b); });
+    return wave_reduce(x, [](double a, double b) { return fmin_quiet(a, b); });
 }
 __device__ __forceinline__ double wave_sum(double x)
 {
-    return wave_reduce(x, 0.0, [](double a, double b) { return a + b; });
+    return wave_reduce(x, [](double a, double b) { return a + b; });
+}
+
+// Pre-reductions of a stage's row sums in registers before its first lane adds them to LDS (ipm_fast: a ds_add_f64 whose lanes hit one address is serialised).
+// Three lanes per stage: x[l] + (x[l + 1] + x[l + 2]) by two wave shifts (wave_shl:1; a stage may straddle two 16-lane rows).
+__device__ __forceinline__ double stage_sum3(double x)
+{
+    const double t = x + dpp_shift_zero<0x130>(x);
+    return x + dpp_shift_zero<0x130>(t);
+}
+// Aligned quads: quad_perm [1,0,3,2], then [2,3,0,1] -- every lane of the quad holds its sum; FOLD8 (eight lanes per stage, half a 16-lane row): one row
+// shift by four (row_shl:4) folds the stage's second quad into the first
+template <bool FOLD8>
+__device__ __forceinline__ double stage_sum_quad(double x)
+{
+    x += dpp_move<0xB1, 0xf>(x, 0.0); x += dpp_move<0x4E, 0xf>(x, 0.0);
+    if constexpr (FOLD8) x += dpp_shift_zero<0x104>(x);
+    return x;
 }
 
 // Workgroup reductions for the multi-wave variants of the fast kernel (NTH = 128: two waves, 256: four): wave reduction, then one LDS exchange.
@@ -289,7 +342,7 @@ template <int NTH> __device__ __forceinline__ double blk_sum(double x, double *s
 template <int NTH>
 __device__ __forceinline__ void blk_residuals(double &worst, double g, double b, double dd, double m, double &mu, double *scr, int tid)
 {
-    worst = wave_max(fmax(fmax(g, b), fmax(dd, m))); mu = wave_sum(mu);
+    worst = wave_max(fmax_quiet(fmax_quiet(g, b), fmax_quiet(dd, m))); mu = wave_sum(mu);
     if constexpr (NTH > 64) {
         constexpr int NW = NTH / 64;
         if ((tid & 63) == 0) { const int w = tid >> 6; scr[w] = worst; scr[NW + w] = mu; }
