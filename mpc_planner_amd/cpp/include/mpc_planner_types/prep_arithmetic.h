@@ -1,6 +1,6 @@
 /* mpc_planner_types/prep_arithmetic.h -- the double-precision arithmetic of data preparation (road rows, obstacle preparation, path tracking,
- * path fitting, free-space decomposition, the guidance hand-off), written ONCE for the device kernels (csrc/tmpc_aux_kernels.hpp) and the Solver-free C++ headers
- * (reference_path.h, free_space.h, guidance_handoff.h, data_preparation.h, Contouring in modules_hip.h): both compile these functions, so they cannot drift apart.  The independent statement the
+ * path fitting, free-space decomposition, the guidance hand-off, the episode step), written ONCE for the device kernels (csrc/tmpc_aux_kernels.hpp) and the Solver-free C++ headers
+ * (reference_path.h, free_space.h, guidance_handoff.h, data_preparation.h, episode.h, Contouring in modules_hip.h): both compile these functions, so they cannot drift apart.  The independent statement the
  * tests compare both against is the numpy mirror, mpc_planner_amd/modules.py; every function keeps the mirror's operation order, and nothing is
  * fused into multiply-adds (the pragma under clang; build host code with -ffp-contract=off).  Plain functions on doubles: no containers, no
  * planner types.  A cubic is its eight coefficients c = (ax bx cx dx ay by cy dy): x(t) = ((ax t + bx) t + cx) t + dx, the same for y. */
@@ -360,6 +360,63 @@ namespace tmpc_arith
         for (int p = 0; p < P; p++) ids[p] = guidance_id[p];
         if (best >= 0) { sel[0] = guidance_id[best]; sel[1] = (use_tmpcpp && best == P - 1) ? 1 : 0; }
         sel[2] = best;
+    }
+
+    /* ---- the episode step: the velocity-commanded unicycle plant, the obstacles' motion and the intrusion measure.
+     * + - x /, sqrt and comparisons only: no libm trigonometry ---- */
+    /* sin a, cos a and sin a / a for |a| <= 1/16 as fixed Horner polynomials in a^2: terms through a^9, a^10 and a^8 (the first omitted
+     * terms, a^11 / 11! and a^12 / 12!, stay below 2e-21 there).  sin a = a (sin a / a): the same polynomial, one evaluation */
+    TMPC_ARITH_FN void small_angle(double a, double &sn, double &cs, double &sinc)
+    {
+        TMPC_ARITH_NO_FMA
+        const double z = a * a;
+        sinc = (((z * (1.0 / 362880.0) + (-1.0 / 5040.0)) * z + (1.0 / 120.0)) * z + (-1.0 / 6.0)) * z + 1.0;
+        cs = ((((z * (-1.0 / 3628800.0) + (1.0 / 40320.0)) * z + (-1.0 / 720.0)) * z + (1.0 / 24.0)) * z + (-1.0 / 2.0)) * z + 1.0;
+        sn = a * sinc;
+    }
+    /* one substep h of the plant p = (x, y, psi, v, c, s), (c, s) the heading as a unit vector: w clipped to +-max_w by two comparisons (a NaN
+     * passes), dv = cmd_v - v clipped to +-max_acc h when max_acc > 0, the exact arc of the mean velocity at constant w through the half angle
+     * a = (w h) / 2 -- chord (vm h) (sin a / a) along the mid heading --, (c, s) rotated twice by a and renormalised, psi += w h */
+    TMPC_ARITH_FN void plant_substep(double cmd_v, double cmd_w, double h, double max_acc, double max_w, double *p)
+    {
+        TMPC_ARITH_NO_FMA
+        double w = cmd_w;
+        if (w > max_w) w = max_w;
+        if (w < -max_w) w = -max_w;
+        double dv = cmd_v - p[3];
+        if (max_acc > 0.0) {
+            const double lim = max_acc * h;
+            if (dv > lim) dv = lim;
+            if (dv < -lim) dv = -lim;
+        }
+        const double v1 = p[3] + dv, vm = (p[3] + v1) / 2.0;
+        const double a = (w * h) / 2.0;
+        double sn, cs, sinc;
+        small_angle(a, sn, cs, sinc);
+        const double cm = p[4] * cs - p[5] * sn, sm = p[5] * cs + p[4] * sn;
+        const double d = (vm * h) * sinc;
+        p[0] = p[0] + d * cm;
+        p[1] = p[1] + d * sm;
+        const double c2 = cm * cs - sm * sn, s2 = sm * cs + cm * sn;
+        const double n = sqrt(c2 * c2 + s2 * s2);
+        p[4] = c2 / n; p[5] = s2 / n;
+        p[2] = p[2] + w * h;
+        p[3] = v1;
+    }
+    /* one coordinate of an obstacle over a control period: pos += vel dt; with a box, a position now outside [lo, hi] flips the velocity's
+     * sign and stays where it is */
+    TMPC_ARITH_FN void obstacle_step(double &pos, double &vel, double dt, bool boxed, double lo, double hi)
+    {
+        TMPC_ARITH_NO_FMA
+        pos = pos + vel * dt;
+        if (boxed && (pos < lo || pos > hi)) vel = -vel;
+    }
+    /* how far the robot's disc at (x, y) and the obstacle's at (ox, oy) overlap: negative when apart, 0 when they touch */
+    TMPC_ARITH_FN double intrusion_candidate(double robot_radius, double radius, double ox, double oy, double x, double y)
+    {
+        TMPC_ARITH_NO_FMA
+        const double dx = ox - x, dy = oy - y;
+        return (robot_radius + radius) - sqrt(dx * dx + dy * dy);
     }
 }
 #endif

@@ -864,6 +864,108 @@ __global__ void tmpc_guidance_decide_kernel(int n_scenes, GuidanceOptions o, int
                                       exit_out + q, cmd + (size_t)q * 2, planner_ids + f, selection + (size_t)q * 3);
 }
 
+// ---- the episode step (include/tmpc_hip_episode.h): plant, obstacle motion, intrusion, termination, log, restart ----------------
+// the options of tmpc_episode_step, by value
+struct EpisodeOptions { int substeps, timeout_ticks, max_episodes; double control_dt, max_acceleration, max_angular_velocity, robot_radius, goal_x; };
+constexpr int EPISODE_MAX_SLOTS = 1024, EPISODE_MAX_SUBSTEPS = 16, EPISODE_MAX_LOG = 4096;
+
+// One wave per scene q.  The plant, the verdict and the counters are functions of the scene's own few numbers: every lane evaluates them on
+// the same operands (wave-uniform: no branch, nothing to broadcast, the same bits in every lane) and lane 0 stores them.  Lane l moves the
+// obstacle slots l, l + 64, ... (at most 16 at R = 1024) and takes their intrusion candidates; a 64-lane __shfl_xor maximum on strict `>`
+// from 0.0 gives the tick's intrusion -- no NaN enters and a maximum does not depend on the order, so the result is the mirror's sequential
+// scan's.  On a reset the same lane restores the same slots it moved: one lane, the same addresses, program order.  The state outputs are
+// strided over the lanes.  Plain loads and stores: a scene belongs to one wave.  The arithmetic is tmpc_arith's, the source
+// mpc_planner/episode.h compiles too: every output is bit-equal to the independent modules.py::episode_step.
+__global__ __launch_bounds__(64) void tmpc_episode_step_kernel(int R, int P, int nx, EpisodeOptions o, const double *cmd, double *plant,
+                                                               const double *plant0, const int *count, double *raw_pos, double *raw_vel,
+                                                               const double *raw_radius, const double *raw_pos0, const double *raw_vel0,
+                                                               const double *box, const double *goal, int *episode, double *episode_f, double *log,
+                                                               uint8_t *was_reset, double *state4, double *state_nx, double *state_batch,
+                                                               int *planner_ids, int *selection, int *segment)
+{
+#pragma clang fp contract(off)
+    const int q = blockIdx.x, lane = threadIdx.x;
+    int cnt = count[q];
+    cnt = cnt < 0 ? 0 : (cnt > R ? R : cnt);
+    // 1. the plant
+    double p[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) p[i] = plant[(size_t)q * 6 + i];
+    const double cmd_v = cmd[(size_t)q * 2], cmd_w = cmd[(size_t)q * 2 + 1];
+    const double h = o.control_dt / (double)o.substeps;
+    for (int it = 0; it < o.substeps; it++) tmpc_arith::plant_substep(cmd_v, cmd_w, h, o.max_acceleration, o.max_angular_velocity, p);
+    // 2. the obstacles, 3. the intrusion
+    const bool boxed = box != nullptr;
+    double xlo = 0.0, xhi = 0.0, ylo = 0.0, yhi = 0.0;
+    if (boxed) { xlo = box[(size_t)q * 4]; xhi = box[(size_t)q * 4 + 1]; ylo = box[(size_t)q * 4 + 2]; yhi = box[(size_t)q * 4 + 3]; }
+    double *rp = raw_pos + (size_t)q * R * 2, *rv = raw_vel + (size_t)q * R * 2;
+    double intrusion = 0.0;
+    for (int i = lane; i < cnt; i += 64) {
+        double ox = rp[i * 2], oy = rp[i * 2 + 1], vx = rv[i * 2], vy = rv[i * 2 + 1];
+        tmpc_arith::obstacle_step(ox, vx, o.control_dt, boxed, xlo, xhi);
+        tmpc_arith::obstacle_step(oy, vy, o.control_dt, boxed, ylo, yhi);
+        rp[i * 2] = ox; rp[i * 2 + 1] = oy; rv[i * 2] = vx; rv[i * 2 + 1] = vy;
+        const double cand = tmpc_arith::intrusion_candidate(o.robot_radius, raw_radius[(size_t)q * R + i], ox, oy, p[0], p[1]);
+        if (cand > intrusion) intrusion = cand;
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        const double other = __shfl_xor(intrusion, s, 64);
+        if (other > intrusion) intrusion = other;
+    }
+    // 4. the counters, 5. the verdict (wave-uniform)
+    int ticks = episode[(size_t)q * 4] + 1, collisions = episode[(size_t)q * 4 + 1] + (intrusion > 0.0 ? 1 : 0), finished = episode[(size_t)q * 4 + 2];
+    double max_intrusion = episode_f[(size_t)q * 2];
+    if (intrusion > max_intrusion) max_intrusion = intrusion;
+    bool completed = p[0] > o.goal_x;
+    if (goal) completed = completed || tmpc_arith::within_distance(p[0], p[1], goal[(size_t)q * 3], goal[(size_t)q * 3 + 1], goal[(size_t)q * 3 + 2]);
+    const bool reset = completed || (o.timeout_ticks > 0 && ticks >= o.timeout_ticks);
+    // 6. the log and the restart
+    if (reset) {
+        if (lane == 0 && finished >= 0 && finished < o.max_episodes) {
+            double *row = log + ((size_t)q * o.max_episodes + finished) * 4;
+            row[0] = (double)ticks * o.control_dt; row[1] = completed ? 1.0 : 0.0; row[2] = (double)collisions; row[3] = max_intrusion;
+        }
+        finished += 1;
+#pragma unroll
+        for (int i = 0; i < 6; i++) p[i] = plant0[(size_t)q * 6 + i];
+        for (int i = lane; i < cnt; i += 64) {
+            const double *rp0 = raw_pos0 + (size_t)q * R * 2, *rv0 = raw_vel0 + (size_t)q * R * 2;
+            rp[i * 2] = rp0[i * 2]; rp[i * 2 + 1] = rp0[i * 2 + 1]; rv[i * 2] = rv0[i * 2]; rv[i * 2 + 1] = rv0[i * 2 + 1];
+        }
+        ticks = 0; collisions = 0; max_intrusion = 0.0;
+        if (planner_ids) for (int e = lane; e < P; e += 64) planner_ids[(size_t)q * P + e] = -1;
+        if (lane == 0) {
+            if (selection) { selection[(size_t)q * 3] = -1; selection[(size_t)q * 3 + 1] = 0; selection[(size_t)q * 3 + 2] = -1; }
+            if (segment) segment[q] = -1;
+        }
+    }
+    if (lane == 0) {
+        episode[(size_t)q * 4] = ticks; episode[(size_t)q * 4 + 1] = collisions; episode[(size_t)q * 4 + 2] = finished; episode[(size_t)q * 4 + 3] = 0;
+        episode_f[(size_t)q * 2] = max_intrusion; episode_f[(size_t)q * 2 + 1] = intrusion;
+        was_reset[q] = reset ? 1 : 0;
+#pragma unroll
+        for (int i = 0; i < 6; i++) plant[(size_t)q * 6 + i] = p[i];
+#pragma unroll
+        for (int i = 0; i < 4; i++) state4[(size_t)q * 4 + i] = p[i];
+    }
+    // 7. the planner's states: entries 0 .. 3 from the plant, the rest zeroed on a reset only
+    auto entry = [&](int col) { return col == 0 ? p[0] : col == 1 ? p[1] : col == 2 ? p[2] : p[3]; };     // (selects: p stays in registers)
+    if (state_nx)
+        for (int e = lane; e < nx; e += 64) {
+            if (e < 4) state_nx[(size_t)q * nx + e] = entry(e);
+            else if (reset) state_nx[(size_t)q * nx + e] = 0.0;
+        }
+    if (state_batch) {
+        const size_t total = (size_t)P * nx;
+        for (size_t e = lane; e < total; e += 64) {
+            const int col = (int)(e % (size_t)nx);
+            if (col < 4) state_batch[(size_t)q * total + e] = entry(col);
+            else if (reset) state_batch[(size_t)q * total + e] = 0.0;
+        }
+    }
+}
+
 
 // ---- f-3: scenario -> polygon on device (SH-MPC, BASELINE config 5) ------------------------------------------------
 // The reference delegates this to the external scenario_module (scenario_constraints.cpp:47,76-79; source absent), so

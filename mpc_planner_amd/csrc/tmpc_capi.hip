@@ -604,6 +604,8 @@ struct Events {
 // the entry points of the device row writers, for the hand-written layout (tmpc_hip.h) and for the columns of generated solvers' module stacks
 // (tmpc_hip_stack.h, tmpc_hip_stack_env.h, tmpc_hip_stack_scenario.h): one body per writer, two thin entry points; no_batch, launch_flat, read_stack_columns
 #include "tmpc_row_entries.hpp"
+// the world of a closed loop (tmpc_hip_episode.h): plant step, obstacle motion, episode log -- no parameter row, no batch
+#include "tmpc_episode_entry.hpp"
 
 extern "C" {
 

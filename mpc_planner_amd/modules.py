@@ -1297,3 +1297,125 @@ def decomp_halfspaces(path, length, s0, v, dt, points, R, n_rows, state_x=0.0):
     live = np.arange(n_rows)[None, :] < count[:, None]
     nan = lambda x: np.where(live, x, np.nan)
     return dict(rows=rows, count=count, status=status, a1=nan(rows[:, :, 0]), a2=nan(rows[:, :, 1]), b=nan(rows[:, :, 2]))
+
+
+# ---- the episode step: host mirror of tmpc_episode_step_kernel and of mpc_planner/episode.h, bit for bit ------------------
+# The world of a closed loop for ONE scene: a velocity-commanded unicycle, obstacles that move at constant velocity and bounce inside a box,
+# the intrusion measure, and the bookkeeping of JackalPlanner::loop / reset (ros1_jackalsimulator.cpp:146-226, :359-378), Planner::reset
+# (planner.cpp:231-245) and ExperimentUtil::update / onTaskComplete (experiment_util.cpp:27-110).  Scalar by scalar on Python floats (IEEE
+# doubles, no fused multiply-add, a correctly rounded sqrt) in the kernel's operation order.
+
+
+def _small_angle(a):
+    """(sin a, cos a, sin a / a) for |a| <= 1/16: fixed Horner polynomials in a^2 through a^9, a^10 and a^8; sin a = a (sin a / a)."""
+    z = a * a
+    sinc = (((z * (1.0 / 362880.0) + (-1.0 / 5040.0)) * z + (1.0 / 120.0)) * z + (-1.0 / 6.0)) * z + 1.0
+    cs = ((((z * (-1.0 / 3628800.0) + (1.0 / 40320.0)) * z + (-1.0 / 720.0)) * z + (1.0 / 24.0)) * z + (-1.0 / 2.0)) * z + 1.0
+    return a * sinc, cs, sinc
+
+
+def plant_substep(p, cmd_v, cmd_w, h, max_acceleration, max_angular_velocity):
+    """One substep h of the plant p = (x, y, psi, v, c, s) -> the new six floats: w clipped by two comparisons (a NaN passes), dv clipped to
+    +-max_acceleration h when the limit is positive, the exact arc of the mean velocity through the half angle a = (w h) / 2, (c, s) rotated
+    twice by a and renormalised, psi += w h."""
+    import math
+    x, y, psi, v, c, s = (float(t) for t in p)
+    w = float(cmd_w)
+    if w > max_angular_velocity:
+        w = max_angular_velocity
+    if w < -max_angular_velocity:
+        w = -max_angular_velocity
+    dv = float(cmd_v) - v
+    if max_acceleration > 0.0:
+        lim = max_acceleration * h
+        if dv > lim:
+            dv = lim
+        if dv < -lim:
+            dv = -lim
+    v1 = v + dv
+    vm = (v + v1) / 2.0
+    a = (w * h) / 2.0
+    sn, cs, sinc = _small_angle(a)
+    cm = c * cs - s * sn
+    sm = s * cs + c * sn
+    d = (vm * h) * sinc
+    x = x + d * cm
+    y = y + d * sm
+    c2 = cm * cs - sm * sn
+    s2 = sm * cs + cm * sn
+    nn = c2 * c2 + s2 * s2
+    n = math.sqrt(nn) if nn >= 0.0 else float("nan")
+    return [x, y, psi + w * h, v1, c2 / n, s2 / n]
+
+
+def episode_step(cmd, plant, plant0, count, raw_pos, raw_vel, raw_radius, raw_pos0, raw_vel0, episode, episode_f, log, substeps, timeout_ticks,
+                 control_dt, max_acceleration, max_angular_velocity, robot_radius, goal_x=float("inf"), box=None, goal=None, state_nx=None,
+                 state_batch=None, planner_ids=None, selection=None, segment=None):
+    """One control period of one scene (host mirror of tmpc_episode_step; include/tmpc_hip_episode.h states the seven steps).  IN PLACE on the
+    scene's rows of the device arrays, as numpy arrays (views): plant [6], raw_pos / raw_vel [n_slots][2], episode [4] i32, episode_f [2],
+    log [max_episodes][4], and -- each may be None -- state_nx [nx], state_batch [P][nx], planner_ids [P], selection [3], segment [1].
+    cmd [2], plant0 [6], raw_radius [n_slots], raw_pos0 / raw_vel0, box [4] or None and goal [3] or None are read.  Slots at or beyond the
+    clipped count are neither read nor written.  Returns (was_reset, state4)."""
+    import math
+    control_dt = float(control_dt); max_acceleration = float(max_acceleration); max_angular_velocity = float(max_angular_velocity)
+    robot_radius = float(robot_radius); goal_x = float(goal_x)
+    n_slots, max_episodes = len(raw_radius), len(log)
+    cnt = min(max(int(count), 0), n_slots)
+    # 1. the plant
+    p = [float(t) for t in plant]
+    h = control_dt / float(substeps)
+    for _ in range(int(substeps)):
+        p = plant_substep(p, cmd[0], cmd[1], h, max_acceleration, max_angular_velocity)
+    # 2. the obstacles, 3. the intrusion
+    intrusion = 0.0
+    for i in range(cnt):
+        for axis in range(2):
+            pos = float(raw_pos[i][axis]) + float(raw_vel[i][axis]) * control_dt
+            raw_pos[i][axis] = pos
+            if box is not None and (pos < float(box[2 * axis]) or pos > float(box[2 * axis + 1])):
+                raw_vel[i][axis] = -float(raw_vel[i][axis])
+        dx = float(raw_pos[i][0]) - p[0]
+        dy = float(raw_pos[i][1]) - p[1]
+        dd = dx * dx + dy * dy
+        cand = (robot_radius + float(raw_radius[i])) - (math.sqrt(dd) if dd >= 0.0 else float("nan"))
+        if cand > intrusion:
+            intrusion = cand
+    # 4. the counters, 5. the verdict
+    ticks = int(episode[0]) + 1
+    collisions = int(episode[1]) + (1 if intrusion > 0.0 else 0)
+    finished = int(episode[2])
+    max_intrusion = float(episode_f[0])
+    if intrusion > max_intrusion:
+        max_intrusion = intrusion
+    completed = p[0] > goal_x
+    if goal is not None:
+        dx = p[0] - float(goal[0])
+        dy = p[1] - float(goal[1])
+        dd = dx * dx + dy * dy
+        completed = completed or ((math.sqrt(dd) if dd >= 0.0 else float("nan")) < float(goal[2]))
+    reset = bool(completed or (timeout_ticks > 0 and ticks >= timeout_ticks))
+    # 6. the log and the restart
+    if reset:
+        if 0 <= finished < max_episodes:
+            log[finished] = (float(ticks) * control_dt, 1.0 if completed else 0.0, float(collisions), max_intrusion)
+        finished += 1
+        p = [float(t) for t in plant0]
+        for i in range(cnt):
+            raw_pos[i] = raw_pos0[i]
+            raw_vel[i] = raw_vel0[i]
+        ticks, collisions, max_intrusion = 0, 0, 0.0
+        if planner_ids is not None:
+            planner_ids[:] = -1
+        if selection is not None:
+            selection[:] = (-1, 0, -1)
+        if segment is not None:
+            segment[:] = -1
+    episode[:] = (ticks, collisions, finished, 0)
+    episode_f[:] = (max_intrusion, intrusion)
+    plant[:] = p
+    # 7. the planner's states
+    for out in ([] if state_nx is None else [state_nx]) + ([] if state_batch is None else list(state_batch)):
+        out[0:4] = p[0:4]
+        if reset:
+            out[4:] = 0.0
+    return reset, np.array(p[0:4])
