@@ -9,6 +9,7 @@ Host-side mirror of the reference's solver / module interface for this one hot p
   stack_env.py   -- ctypes binding of include/tmpc_hip_stack_env.h: path window, road and decomp rows of generated solvers, by column
   stack_scenario.py -- ctypes binding of include/tmpc_hip_stack_scenario.h: scenario rows and support of generated solvers, by column
   episode.py     -- ctypes binding of include/tmpc_hip_episode.h: plant step, obstacle motion and episode log of a closed loop; EpisodeWorld
+  guidance_search.py -- ctypes binding of include/tmpc_hip_guidance_search.h: the guidance search on device; GuidanceSearchState
   csrc/          -- HIP kernels (gfx950) and the C-ABI shim
 """
 __all__ = ["parameters", "modules", "scenes"]

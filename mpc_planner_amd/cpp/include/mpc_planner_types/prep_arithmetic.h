@@ -1,6 +1,6 @@
 /* mpc_planner_types/prep_arithmetic.h -- the double-precision arithmetic of data preparation (road rows, obstacle preparation, path tracking,
- * path fitting, free-space decomposition, the guidance hand-off, the episode step), written ONCE for the device kernels (csrc/tmpc_aux_kernels.hpp) and the Solver-free C++ headers
- * (reference_path.h, free_space.h, guidance_handoff.h, data_preparation.h, episode.h, Contouring in modules_hip.h): both compile these functions, so they cannot drift apart.  The independent statement the
+ * path fitting, free-space decomposition, the guidance hand-off, the episode step, the guidance search), written ONCE for the device kernels (csrc/tmpc_aux_kernels.hpp) and the Solver-free C++ headers
+ * (reference_path.h, free_space.h, guidance_handoff.h, data_preparation.h, episode.h, guidance_search.h, Contouring in modules_hip.h): both compile these functions, so they cannot drift apart.  The independent statement the
  * tests compare both against is the numpy mirror, mpc_planner_amd/modules.py; every function keeps the mirror's operation order, and nothing is
  * fused into multiply-adds (the pragma under clang; build host code with -ffp-contract=off).  Plain functions on doubles: no containers, no
  * planner types.  A cubic is its eight coefficients c = (ax bx cx dx ay by cy dy): x(t) = ((ax t + bx) t + cx) t + dx, the same for y. */
@@ -417,6 +417,374 @@ namespace tmpc_arith
         TMPC_ARITH_NO_FMA
         const double dx = ox - x, dy = oy - y;
         return (robot_radius + radius) - sqrt(dx * dx + dy * dy);
+    }
+
+    /* ---- the guidance search: a visibility-PRM on the stage grid, a homotopy filter by winding numbers and the selection of
+     * the cheapest topology classes.  Decisions (integers), copies and fixed-order + - x / sqrt expressions only.  The search of one scene is
+     * written once, gs_scene below, over a lane policy W: the device kernel runs it with the 64 lanes of a wave (lane-strided loops, votes,
+     * integer sums, a minimum with an index tie-break: no reduction whose result depends on the lane order), the host twin
+     * (mpc_planner_modules/guidance_search.h) with GsOneLane.  Everything outside the lane-strided loops is wave-uniform: every lane holds
+     * the same value, takes the same branch and stores the same value to a table entry ---- */
+    constexpr int GS_MAX_OBSTACLES = 32, GS_MAX_GOALS = 16, GS_GUARDS = 32, GS_CONNECTORS = 128, GS_KEPT = 16, GS_MAX_NODES = 64, GS_MAX_STAGES = 64,
+                  GS_MAX_CHAIN = 31, GS_MAX_SAMPLES = 256, GS_MAX_EXPANSIONS = 65536;
+    enum { GS_GUARDS_FULL = 1, GS_CONNECTORS_FULL = 2, GS_EXPANSIONS_STOPPED = 4, GS_PATH_TOO_LONG = 8 };
+
+    /* the fields of tmpc_guidance_search_options behind `size` */
+    struct GsOptions { int n_paths, n_samples, n_nodes_max, max_expansions; unsigned long long seed; double robot_radius, max_velocity, margin, weight_length; };
+
+    /* what tmpc_guidance_search refuses (N + 1 stages have to fit the tables: every handle's N does) */
+    TMPC_ARITH_FN bool gs_valid(const GsOptions &o, int n_scenes, int n_goals, int max_obstacles, int N)
+    {
+        TMPC_ARITH_NO_FMA
+        const double inf = __builtin_huge_val();
+        return n_scenes > 0 && n_goals >= 1 && n_goals <= GS_MAX_GOALS && max_obstacles >= 1 && max_obstacles <= GS_MAX_OBSTACLES && N >= 1 &&
+               N < GS_MAX_STAGES && o.n_paths >= 1 && o.n_paths <= GS_KEPT && o.n_samples >= 0 && o.n_samples <= GS_MAX_SAMPLES &&
+               o.n_nodes_max >= 2 && o.n_nodes_max <= GS_MAX_NODES && o.max_expansions >= 1 && o.max_expansions <= GS_MAX_EXPANSIONS &&
+               o.robot_radius >= 0.0 && o.max_velocity > 0.0 && o.max_velocity < inf && o.weight_length > 0.0 && o.weight_length < inf &&
+               o.margin >= 0.0 && o.margin < inf;
+    }
+
+    /* the tables of one scene: LDS on the device (about 42 KB), an object on the host */
+    struct GsWork {
+        double opos[GS_MAX_OBSTACLES][GS_MAX_STAGES][2];     /* the real obstacles by STAGE: stage k sees prepared step max(k - 1, 0) */
+        double orr2[GS_MAX_OBSTACLES];                       /* (r_j + robot_radius)^2 */
+        double gxy[GS_GUARDS][2], gcost[GS_GUARDS];          /* guards: position, the goal's cost */
+        int gk[GS_GUARDS], ggoal[GS_GUARDS];                 /* stage; goal index, -1 for the start and for sample guards */
+        double cxy[GS_CONNECTORS][2], clen[GS_CONNECTORS];   /* connectors (g1, s, g2): the sample, the two legs' length */
+        int cg1[GS_CONNECTORS], cg2[GS_CONNECTORS], ck[GS_CONNECTORS];
+        double a[GS_MAX_STAGES][2], b[GS_MAX_STAGES][2];     /* the two polylines of a homotopy test, by stage */
+        double kcost[GS_KEPT];                               /* kept paths: cost, connectors, the connector chain, the goal's guard */
+        int knc[GS_KEPT], kgoal[GS_KEPT], kchain[GS_KEPT][GS_MAX_CHAIN];
+        int chain[GS_MAX_CHAIN], it[GS_MAX_CHAIN + 1];       /* the enumeration's stack: the candidate path */
+        int order[GS_KEPT], cls[GS_KEPT];
+    };
+
+    /* the host's lane policy: one lane */
+    struct GsOneLane {
+        static constexpr int width = 1;
+        int lane() const { return 0; }
+        bool any(bool b) const { return b; }
+        int sum(int v) const { return v; }
+        void argmin(double &, int &) const {}
+        void sync() const {}
+    };
+
+    /* splitmix64, counter-based, as tmpc_sample_scenarios draws its bits: the scene's key, then the bits of counter ctr */
+    TMPC_ARITH_FN unsigned long long gs_mix(unsigned long long z)
+    {
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    }
+    TMPC_ARITH_FN unsigned long long gs_key(unsigned long long seed, int q) { return gs_mix(seed ^ gs_mix((unsigned long long)q + 0x51ED270B1ull)); }
+    TMPC_ARITH_FN unsigned long long gs_bits(unsigned long long key, unsigned long long ctr) { return gs_mix(key + (ctr + 1ull) * 0x9E3779B97F4A7C15ull); }
+    TMPC_ARITH_FN double gs_unit(unsigned long long bits) { TMPC_ARITH_NO_FMA return (double)(bits >> 11) * (1.0 / 9007199254740992.0); }
+    TMPC_ARITH_FN double gs_sample_coordinate(double lo, double hi, unsigned long long bits) { TMPC_ARITH_NO_FMA return lo + (hi - lo) * gs_unit(bits); }
+    TMPC_ARITH_FN bool gs_finite(double x) { return x == x && fabs(x) < __builtin_huge_val(); }
+    /* one coordinate of the connection a -> b at stage k: the endpoints as they are */
+    TMPC_ARITH_FN double gs_lerp(double a, double b, int k, int ka, int kb)
+    {
+        TMPC_ARITH_NO_FMA
+        return k == ka ? a : k == kb ? b : a + (b - a) * ((double)(k - ka) / (double)(kb - ka));
+    }
+    TMPC_ARITH_FN double gs_dist2(double ax, double ay, double bx, double by) { TMPC_ARITH_NO_FMA const double dx = bx - ax, dy = by - ay; return dx * dx + dy * dy; }
+    TMPC_ARITH_FN double gs_length(double ax, double ay, double bx, double by) { TMPC_ARITH_NO_FMA return sqrt(gs_dist2(ax, ay, bx, by)); }
+    TMPC_ARITH_FN bool gs_reachable(double d2, double max_velocity, int dk, double dt) { TMPC_ARITH_NO_FMA const double lim = (max_velocity * (double)dk) * dt; return d2 <= lim * lim; }
+    /* one polygon edge u -> w of a winding number about the origin, by the crossing rule: +1 for an upward crossing with the origin on the
+     * left, -1 for a downward one with the origin on the right */
+    TMPC_ARITH_FN int gs_crossing(double ux, double uy, double wx, double wy)
+    {
+        TMPC_ARITH_NO_FMA
+        const double c = ux * wy - uy * wx;
+        if (uy <= 0.0) return (wy > 0.0 && c > 0.0) ? 1 : 0;
+        return (wy <= 0.0 && c < 0.0) ? -1 : 0;
+    }
+    /* the winding number of the closed polygon v [n][2] about the origin (the statement the tests hold against atan2) */
+    TMPC_ARITH_FN int gs_winding(const double *v, int n)
+    {
+        int wn = 0;
+        for (int e = 0; e < n; e++) { const int f = e + 1 == n ? 0 : e + 1; wn += gs_crossing(v[e * 2], v[e * 2 + 1], v[f * 2], v[f * 2 + 1]); }
+        return wn;
+    }
+
+    /* is the connection (ka, xa, ya) -> (kb, xb, yb) valid: ka < kb, reachable at max_velocity, clear of every real obstacle at every stage
+     * >= 1 of [ka, kb].  The stages x obstacles over the lanes, one vote */
+    template <class W> TMPC_ARITH_FN bool gs_connection_valid(const W &w, const GsWork &t, int n_real, const GsOptions &o, double dt, int ka, double xa,
+                                                              double ya, int kb, double xb, double yb)
+    {
+        TMPC_ARITH_NO_FMA
+        if (!(ka < kb)) return false;
+        bool bad = !gs_reachable(gs_dist2(xa, ya, xb, yb), o.max_velocity, kb - ka, dt);
+        const int items = (kb - ka + 1) * n_real;
+        for (int e = w.lane(); e < items; e += W::width) {
+            const int k = ka + e / n_real, j = e % n_real;
+            if (k >= 1 && !(gs_dist2(gs_lerp(xa, xb, k, ka, kb), gs_lerp(ya, yb, k, ka, kb), t.opos[j][k][0], t.opos[j][k][1]) >= t.orr2[j])) bad = true;
+        }
+        return !w.any(bad);
+    }
+    /* the two-leg polyline (k0, p0) -> (k1, p1) -> (k2, p2) at every stage of [k0, k2] */
+    template <class W> TMPC_ARITH_FN void gs_expand_legs(const W &w, double (*buf)[2], int k0, double x0, double y0, int k1, double x1, double y1, int k2,
+                                                         double x2, double y2)
+    {
+        w.sync();
+        for (int k = k0 + w.lane(); k <= k2; k += W::width) {
+            buf[k][0] = k <= k1 ? gs_lerp(x0, x1, k, k0, k1) : gs_lerp(x1, x2, k, k1, k2);
+            buf[k][1] = k <= k1 ? gs_lerp(y0, y1, k, k0, k1) : gs_lerp(y1, y2, k, k1, k2);
+        }
+        w.sync();
+    }
+    /* node i of the path (nc connectors `chain`, then the goal's guard): start, c, g, c', g', ..., goal; a direct path has nc = 0 */
+    TMPC_ARITH_FN int gs_path_nodes(int nc) { return nc > 0 ? 1 + 2 * nc : 2; }
+    TMPC_ARITH_FN void gs_path_node(const GsWork &t, int nc, const int *chain, int goal, int i, int &k, double &x, double &y)
+    {
+        if (i & 1) {
+            if (nc == 0) { k = t.gk[goal]; x = t.gxy[goal][0]; y = t.gxy[goal][1]; }
+            else { const int c = chain[(i - 1) / 2]; k = t.ck[c]; x = t.cxy[c][0]; y = t.cxy[c][1]; }
+        } else {
+            const int g = i == 0 ? 0 : t.cg2[chain[i / 2 - 1]];
+            k = t.gk[g]; x = t.gxy[g][0]; y = t.gxy[g][1];
+        }
+    }
+    /* a path at every stage 0 .. N: stage k lies on the first leg that ends at or after it */
+    template <class W> TMPC_ARITH_FN void gs_expand_path(const W &w, const GsWork &t, double (*buf)[2], int N, int nc, const int *chain, int goal)
+    {
+        w.sync();
+        const int n = gs_path_nodes(nc);
+        for (int k = w.lane(); k <= N; k += W::width) {
+            int ka, kb; double xa, ya, xb, yb;
+            gs_path_node(t, nc, chain, goal, 0, ka, xa, ya);
+            gs_path_node(t, nc, chain, goal, 1, kb, xb, yb);
+            for (int i = 2; i < n && kb < k; i++) { ka = kb; xa = xb; ya = yb; gs_path_node(t, nc, chain, goal, i, kb, xb, yb); }
+            buf[k][0] = gs_lerp(xa, xb, k, ka, kb); buf[k][1] = gs_lerp(ya, yb, k, ka, kb);
+        }
+        w.sync();
+    }
+    /* are the polylines t.a and t.b, given at every stage of [ka, kb], equivalent: for every real obstacle the winding number about the origin
+     * of the closed polygon a(k) - o(k), k ascending, then b(k) - o(k), k descending, is 0.  The polygon's edges over the lanes, one integer
+     * sum per obstacle */
+    template <class W> TMPC_ARITH_FN bool gs_equivalent(const W &w, const GsWork &t, int n_real, int ka, int kb)
+    {
+        TMPC_ARITH_NO_FMA
+        const int m = kb - ka + 1, n = 2 * m;
+        for (int j = 0; j < n_real; j++) {
+            int local = 0;
+            for (int e = w.lane(); e < n; e += W::width) {
+                const int f = e + 1 == n ? 0 : e + 1;
+                const int ke = e < m ? ka + e : kb - (e - m), kf = f < m ? ka + f : kb - (f - m);
+                const double(*pe)[2] = e < m ? t.a : t.b, (*pf)[2] = f < m ? t.a : t.b;
+                local += gs_crossing(pe[ke][0] - t.opos[j][ke][0], pe[ke][1] - t.opos[j][ke][1], pf[kf][0] - t.opos[j][kf][0], pf[kf][1] - t.opos[j][kf][1]);
+            }
+            if (w.sum(local) != 0) return false;
+        }
+        return true;
+    }
+    /* a candidate path (the enumeration's stack t.chain, nc connectors, the goal's guard) against the kept list: one path per class */
+    template <class W> TMPC_ARITH_FN void gs_consider(const W &w, GsWork &t, int n_real, const GsOptions &o, int N, int nc, int goal, int &n_kept, int &status)
+    {
+        TMPC_ARITH_NO_FMA
+        const int n = gs_path_nodes(nc);
+        if (n > o.n_nodes_max) { status |= GS_PATH_TOO_LONG; return; }
+        double acc = 0.0;
+        {
+            int ka, kb; double xa, ya, xb, yb;
+            gs_path_node(t, nc, t.chain, goal, 0, ka, xa, ya);
+            for (int i = 1; i < n; i++) { gs_path_node(t, nc, t.chain, goal, i, kb, xb, yb); acc = acc + gs_length(xa, ya, xb, yb); xa = xb; ya = yb; }
+        }
+        const double cost = o.weight_length * acc + t.gcost[goal];
+        gs_expand_path(w, t, t.a, N, nc, t.chain, goal);
+        int slot = -1;
+        for (int p = 0; p < n_kept && slot < 0; p++) {
+            gs_expand_path(w, t, t.b, N, t.knc[p], t.kchain[p], t.kgoal[p]);
+            if (gs_equivalent(w, t, n_real, 0, N)) {
+                if (!(cost < t.kcost[p])) return;
+                slot = p;
+            }
+        }
+        if (slot < 0) {
+            if (n_kept < GS_KEPT) slot = n_kept++;
+            else {
+                int worst = 0;
+                for (int p = 1; p < n_kept; p++) if (t.kcost[p] >= t.kcost[worst]) worst = p;
+                if (!(cost < t.kcost[worst])) return;
+                slot = worst;
+            }
+        }
+        w.sync();
+        t.kcost[slot] = cost; t.knc[slot] = nc; t.kgoal[slot] = goal;
+        for (int i = 0; i < nc; i++) t.kchain[slot][i] = t.chain[i];
+        w.sync();
+    }
+
+    /* The guidance search of scene q (include/tmpc_hip_guidance_search.h states the arrays and the algorithm).  Every pointer is the whole
+     * array; was_reset may be null. */
+    template <class W> TMPC_ARITH_FN void gs_scene(const W &w, GsWork &t, int q, int N, double dt, int n_goals, int M, const GsOptions &o, const double *state4,
+                                                   const double *goals, const double *obstacle_pos, const double *obstacle_radius, const int *selected,
+                                                   const unsigned char *was_reset, double *prev_traj, int *prev_class, int *prev_count, int *next_class,
+                                                   double *nodes, int *node_count, int *traj_count, int *topology_class, int *status_out)
+    {
+        TMPC_ARITH_NO_FMA
+        const int lane = w.lane(), S = N + 1, R = o.n_nodes_max, P = o.n_paths;
+        int status = 0;
+        /* the real obstacles, by stage */
+        int n_real = 0;
+        for (int s = 0; s < M; s++) {
+            if (selected[(size_t)q * M + s] < 0) continue;
+            const double rr = obstacle_radius[(size_t)q * M + s] + o.robot_radius;
+            t.orr2[n_real] = rr * rr;
+            for (int e = lane; e < S * 2; e += W::width) {
+                const int k = e >> 1, step = k >= 1 ? k - 1 : 0;
+                t.opos[n_real][k][e & 1] = obstacle_pos[(((size_t)q * M + s) * N + step) * 2 + (e & 1)];
+            }
+            n_real++;
+        }
+        /* the guards: the start, then the present goals; the sampling box */
+        const double sx = state4[(size_t)q * 4], sy = state4[(size_t)q * 4 + 1];
+        int n_guards = 1;
+        t.gk[0] = 0; t.ggoal[0] = -1; t.gxy[0][0] = sx; t.gxy[0][1] = sy; t.gcost[0] = 0.0;
+        double lox = sx, hix = sx, loy = sy, hiy = sy;
+        for (int i = 0; i < n_goals; i++) {
+            const double *g = goals + ((size_t)q * n_goals + i) * 3;
+            if (!gs_finite(g[0]) || !gs_finite(g[1])) continue;
+            t.gk[n_guards] = N; t.ggoal[n_guards] = i; t.gxy[n_guards][0] = g[0]; t.gxy[n_guards][1] = g[1]; t.gcost[n_guards] = g[2];
+            n_guards++;
+            if (g[0] < lox) lox = g[0];
+            if (g[0] > hix) hix = g[0];
+            if (g[1] < loy) loy = g[1];
+            if (g[1] > hiy) hiy = g[1];
+        }
+        lox = lox - o.margin; hix = hix + o.margin; loy = loy - o.margin; hiy = hiy + o.margin;
+        w.sync();
+        /* the visibility-PRM: the samples in order */
+        int n_conn = 0;
+        const unsigned long long key = gs_key(o.seed, q);
+        for (int i = 0; i < o.n_samples && N >= 2; i++) {
+            const int k = 1 + (int)(gs_bits(key, 3ull * (unsigned long long)i) % (unsigned long long)(N - 1));
+            const double x = gs_sample_coordinate(lox, hix, gs_bits(key, 3ull * (unsigned long long)i + 1ull));
+            const double y = gs_sample_coordinate(loy, hiy, gs_bits(key, 3ull * (unsigned long long)i + 2ull));
+            unsigned visible = 0u;
+            for (int g = 0; g < n_guards; g++) {
+                const int kg = t.gk[g];
+                if (kg == k) continue;
+                const bool ok = kg < k ? gs_connection_valid(w, t, n_real, o, dt, kg, t.gxy[g][0], t.gxy[g][1], k, x, y)
+                                       : gs_connection_valid(w, t, n_real, o, dt, k, x, y, kg, t.gxy[g][0], t.gxy[g][1]);
+                if (ok) visible |= 1u << g;
+            }
+            if (visible == 0u) {
+                if (n_guards < GS_GUARDS) {
+                    t.gk[n_guards] = k; t.ggoal[n_guards] = -1; t.gxy[n_guards][0] = x; t.gxy[n_guards][1] = y; t.gcost[n_guards] = 0.0;
+                    n_guards++;
+                    w.sync();
+                } else status |= GS_GUARDS_FULL;
+                continue;
+            }
+            /* the nearest visible guard either side in time: the guards over the lanes, a minimum with the lowest index on ties */
+            int g1 = -1, g2 = -1;
+            double d1 = 0.0, d2 = 0.0;
+            for (int g = lane; g < n_guards; g += W::width) {
+                if (!((visible >> g) & 1u)) continue;
+                const double d = gs_dist2(t.gxy[g][0], t.gxy[g][1], x, y);
+                if (t.gk[g] < k) { if (g1 < 0 || d < d1) { g1 = g; d1 = d; } }
+                else if (g2 < 0 || d < d2) { g2 = g; d2 = d; }
+            }
+            w.argmin(d1, g1);
+            w.argmin(d2, g2);
+            if (g1 < 0 || g2 < 0) continue;
+            const int k1 = t.gk[g1], k2 = t.gk[g2];
+            const double x1 = t.gxy[g1][0], y1 = t.gxy[g1][1], x2 = t.gxy[g2][0], y2 = t.gxy[g2][1];
+            const double len = gs_length(x1, y1, x, y) + gs_length(x, y, x2, y2);
+            gs_expand_legs(w, t.a, k1, x1, y1, k, x, y, k2, x2, y2);
+            int slot = -1;
+            bool dropped = false;
+            for (int c = 0; c < n_conn && slot < 0 && !dropped; c++) {
+                if (t.cg1[c] != g1 || t.cg2[c] != g2) continue;
+                gs_expand_legs(w, t.b, k1, x1, y1, t.ck[c], t.cxy[c][0], t.cxy[c][1], k2, x2, y2);
+                if (gs_equivalent(w, t, n_real, k1, k2)) {
+                    if (len < t.clen[c]) slot = c;
+                    else dropped = true;
+                }
+            }
+            if (dropped) continue;
+            if (slot < 0) {
+                if (n_conn >= GS_CONNECTORS) { status |= GS_CONNECTORS_FULL; continue; }
+                slot = n_conn++;
+            }
+            w.sync();
+            t.cg1[slot] = g1; t.cg2[slot] = g2; t.ck[slot] = k; t.cxy[slot][0] = x; t.cxy[slot][1] = y; t.clen[slot] = len;
+            w.sync();
+        }
+        /* the paths: the direct connections in goal order, then the chains, depth first with the connectors in table order */
+        int n_kept = 0;
+        for (int g = 1; g < n_guards; g++)
+            if (t.ggoal[g] >= 0 && gs_connection_valid(w, t, n_real, o, dt, 0, sx, sy, t.gk[g], t.gxy[g][0], t.gxy[g][1]))
+                gs_consider(w, t, n_real, o, N, 0, g, n_kept, status);
+        int depth = 0, visits = 0;
+        t.it[0] = 0;
+        w.sync();
+        while (depth >= 0) {
+            const int g = depth == 0 ? 0 : t.cg2[t.chain[depth - 1]];
+            int c = t.it[depth];
+            while (c < n_conn && t.cg1[c] != g) c++;
+            if (c >= n_conn) { depth--; continue; }
+            if (visits >= o.max_expansions) { status |= GS_EXPANSIONS_STOPPED; break; }
+            visits++;
+            w.sync();
+            t.it[depth] = c + 1; t.chain[depth] = c;
+            w.sync();
+            const int g2 = t.cg2[c];
+            if (t.ggoal[g2] >= 0) gs_consider(w, t, n_real, o, N, depth + 1, g2, n_kept, status);
+            else if (depth + 1 < GS_MAX_CHAIN) { depth++; w.sync(); t.it[depth] = 0; w.sync(); }
+        }
+        /* the kept paths, stably by ascending cost */
+        w.sync();
+        for (int i = 0; i < n_kept; i++) {
+            int j = i;
+            while (j > 0 && t.kcost[t.order[j - 1]] > t.kcost[i]) { t.order[j] = t.order[j - 1]; j--; }
+            t.order[j] = i;
+        }
+        w.sync();
+        const int count = n_kept < P ? n_kept : P;
+        /* class identity across ticks: previous trajectories name classes, against this tick's obstacles */
+        int n_prev = prev_count[q], next = next_class[q];
+        if (was_reset && was_reset[q]) { n_prev = 0; next = 0; }
+        n_prev = n_prev < 0 ? 0 : (n_prev > P ? P : n_prev);
+        unsigned claimed = 0u;
+        for (int i = 0; i < count; i++) {
+            const int p = t.order[i];
+            gs_expand_path(w, t, t.a, N, t.knc[p], t.kchain[p], t.kgoal[p]);
+            int cls = -1;
+            for (int r = 0; r < n_prev && cls < 0; r++) {
+                if ((claimed >> r) & 1u) continue;
+                w.sync();
+                for (int k = lane; k <= N; k += W::width) {
+                    const double *pt = prev_traj + (((size_t)q * P + r) * S + (k + 1 < N ? k + 1 : N)) * 2;
+                    t.b[k][0] = k == 0 ? sx : pt[0]; t.b[k][1] = k == 0 ? sy : pt[1];
+                }
+                w.sync();
+                if (gs_equivalent(w, t, n_real, 0, N)) { cls = prev_class[(size_t)q * P + r]; claimed |= 1u << r; }
+            }
+            if (cls < 0) cls = next++;
+            t.cls[i] = cls;
+        }
+        w.sync();
+        /* the outputs and the carried arrays */
+        for (int i = 0; i < P; i++) {
+            const size_t f = (size_t)q * P + i;
+            if (i >= count) {
+                if (lane == 0) { node_count[f] = 0; topology_class[f] = -1; prev_class[f] = -1; }
+                continue;
+            }
+            const int p = t.order[i], nc = t.knc[p], n = gs_path_nodes(nc);
+            gs_expand_path(w, t, t.a, N, nc, t.kchain[p], t.kgoal[p]);
+            for (int e = lane; e < n; e += W::width) {
+                int k; double x, y;
+                gs_path_node(t, nc, t.kchain[p], t.kgoal[p], e, k, x, y);
+                double *nd = nodes + (f * R + e) * 3;
+                nd[0] = (double)k * dt; nd[1] = x; nd[2] = y;
+            }
+            for (int e = lane; e < S * 2; e += W::width) prev_traj[f * S * 2 + e] = t.a[e >> 1][e & 1];
+            if (lane == 0) { node_count[f] = n; topology_class[f] = t.cls[i]; prev_class[f] = t.cls[i]; }
+        }
+        if (lane == 0) { traj_count[q] = count; prev_count[q] = count; next_class[q] = next; status_out[q] = status; }
     }
 }
 #endif

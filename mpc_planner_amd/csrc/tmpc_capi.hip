@@ -606,6 +606,8 @@ struct Events {
 #include "tmpc_row_entries.hpp"
 // the world of a closed loop (tmpc_hip_episode.h): plant step, obstacle motion, episode log -- no parameter row, no batch
 #include "tmpc_episode_entry.hpp"
+// the guidance search (tmpc_hip_guidance_search.h): topology-distinct trajectories per scene -- no parameter row, no batch
+#include "tmpc_guidance_search_entry.hpp"
 
 extern "C" {
 

@@ -1419,3 +1419,233 @@ def episode_step(cmd, plant, plant0, count, raw_pos, raw_vel, raw_radius, raw_po
         if reset:
             out[4:] = 0.0
     return reset, np.array(p[0:4])
+
+
+# ---- the guidance search: host mirror of tmpc_guidance_search, bit for bit --------------------------------------------------
+GS_GUARDS, GS_CONNECTORS, GS_KEPT = 32, 128, 16
+_GS_MASK = (1 << 64) - 1
+
+
+def _gs_mix(z):
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _GS_MASK
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _GS_MASK
+    return z ^ (z >> 31)
+
+
+def gs_sample_bits(seed, scene, i):
+    """The three 64-bit draws of sample i of a scene: splitmix64 of (seed, scene, i, component), the generator of sample_scenarios."""
+    key = _gs_mix((int(seed) & _GS_MASK) ^ _gs_mix((int(scene) + 0x51ED270B1) & _GS_MASK))
+    return [_gs_mix((key + (3 * i + c + 1) * 0x9E3779B97F4A7C15) & _GS_MASK) for c in range(3)]
+
+
+def winding_number(poly):
+    """Winding number about the origin of the closed polygon poly [n][2] by the crossing rule: comparisons and the cross product
+    u_x w_y - u_y w_x only, an integer."""
+    u = np.asarray(poly, np.float64)
+    w = np.roll(u, -1, axis=0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]
+        up = (u[:, 1] <= 0.0) & (w[:, 1] > 0.0) & (c > 0.0)
+        down = (u[:, 1] > 0.0) & (w[:, 1] <= 0.0) & (c < 0.0)
+    return int(up.sum()) - int(down.sum())
+
+
+def _gs_line(ka, pa, kb, pb, ks):
+    """The connection a -> b at the stages ks: p_a + (p_b - p_a) ((k - k_a) / (k_b - k_a)), the endpoints as they are."""
+    ks = np.asarray(ks)
+    with np.errstate(invalid="ignore", over="ignore"):
+        f = (ks - ka).astype(np.float64) / float(kb - ka)
+        p = pa[None, :] + (pb - pa)[None, :] * f[:, None]
+    p[ks == ka] = pa
+    p[ks == kb] = pb
+    return p
+
+
+def _gs_polyline(nodes, S):
+    """The polyline through nodes [(k, x, y), ...] of increasing stage at every stage it spans, as an array indexed by stage [S][2]."""
+    out = np.full((S, 2), np.nan)
+    for (ka, xa, ya), (kb, xb, yb) in zip(nodes[:-1], nodes[1:]):
+        ks = np.arange(ka, kb + 1)
+        out[ks] = _gs_line(ka, np.array([xa, ya]), kb, np.array([xb, yb]), ks)
+    return out
+
+
+def gs_equivalent(A, B, ka, kb, opos):
+    """Are the polylines A, B (indexed by stage) equivalent over [ka, kb]: for every obstacle (opos [n][S][2], by stage) the polygon
+    A(k) - o(k) ascending, B(k) - o(k) descending does not wind about the origin."""
+    for o in opos:
+        with np.errstate(invalid="ignore", over="ignore"):
+            poly = np.concatenate([A[ka:kb + 1] - o[ka:kb + 1], (B[ka:kb + 1] - o[ka:kb + 1])[::-1]])
+        if winding_number(poly) != 0:
+            return False
+    return True
+
+
+def gs_connection_valid(ka, pa, kb, pb, opos, rr2, max_velocity, dt):
+    """Is the connection valid: k_a < k_b, |p_b - p_a|^2 <= (max_velocity (k_b - k_a) dt)^2, and at every stage k >= 1 of [k_a, k_b]
+    |p(k) - o_j(k)|^2 >= (r_j + robot_radius)^2 for every obstacle.  A NaN anywhere: invalid."""
+    if not ka < kb:
+        return False
+    pa, pb = np.asarray(pa, np.float64), np.asarray(pb, np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = pb - pa
+        lim = (max_velocity * float(kb - ka)) * dt
+        if not d[0] * d[0] + d[1] * d[1] <= lim * lim:
+            return False
+        if len(opos) == 0:
+            return True
+        ks = np.arange(max(ka, 1), kb + 1)
+        e = _gs_line(ka, pa, kb, pb, ks)[None, :, :] - opos[:, ks, :]
+        return bool(np.all(e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1] >= rr2[:, None]))
+
+
+def guidance_search(start, goals, obstacle_pos, obstacle_radius, selected, N, dt, scene, n_paths, n_samples, seed, n_nodes_max, max_expansions,
+                    robot_radius, max_velocity, margin, weight_length, prev_traj, prev_class, prev_count, next_class, nodes, node_count,
+                    topology_class, was_reset=False):
+    """The guidance search of one scene (host mirror of tmpc_guidance_search; include/tmpc_hip_guidance_search.h states the algorithm, U20).
+    start [>= 2], goals [n_goals][3] = (x, y, cost), obstacle_pos [M][N][2], obstacle_radius [M] and selected [M] as prepare_obstacles
+    leaves them; `scene` is the scene's index (it enters the samples' counter).  IN PLACE on the scene's rows of the device arrays (views):
+    the carried prev_traj [n_paths][N + 1][2], prev_class [n_paths], prev_count [1], next_class [1] and the outputs nodes [n_paths][R][3],
+    node_count [n_paths], topology_class [n_paths].  Returns (traj_count, status)."""
+    import math
+    N, S, R, P = int(N), int(N) + 1, int(n_nodes_max), int(n_paths)
+    dt, max_velocity, weight_length, margin = float(dt), float(max_velocity), float(weight_length), float(margin)
+    real = [j for j in range(len(selected)) if int(selected[j]) >= 0]
+    stage_step = np.maximum(np.arange(S) - 1, 0)
+    opos = np.asarray(obstacle_pos, np.float64)[real][:, stage_step, :] if real else np.zeros((0, S, 2))
+    rr = np.asarray(obstacle_radius, np.float64)[real] + float(robot_radius)
+    rr2 = rr * rr
+    valid = lambda a, b: gs_connection_valid(a[0], a[1:], b[0], b[1:], opos, rr2, max_velocity, dt)
+    length = lambda a, b: math.sqrt((b[1] - a[1]) * (b[1] - a[1]) + (b[2] - a[2]) * (b[2] - a[2]))
+    status = 0
+    # guards: (k, x, y), the goal index and cost beside them
+    sx, sy = float(start[0]), float(start[1])
+    guards, goal_of, goal_cost = [(0, sx, sy)], [-1], [0.0]
+    for i, g in enumerate(np.asarray(goals, np.float64)):
+        if np.isfinite(g[0]) and np.isfinite(g[1]):
+            guards.append((N, float(g[0]), float(g[1]))); goal_of.append(i); goal_cost.append(float(g[2]))
+    xs, ys = [g[1] for g in guards], [g[2] for g in guards]
+    lox, hix, loy, hiy = min(xs) - margin, max(xs) + margin, min(ys) - margin, max(ys) + margin
+    # the visibility-PRM
+    connectors = []                                                    # [g1, g2, (k, x, y), length]
+    for i in range(int(n_samples) if N >= 2 else 0):
+        u = gs_sample_bits(seed, scene, i)
+        s = (1 + u[0] % (N - 1), lox + (hix - lox) * (float(u[1] >> 11) * 2.0 ** -53), loy + (hiy - loy) * (float(u[2] >> 11) * 2.0 ** -53))
+        visible = [g for g, gd in enumerate(guards) if gd[0] != s[0] and (valid(gd, s) if gd[0] < s[0] else valid(s, gd))]
+        if not visible:
+            if len(guards) < GS_GUARDS:
+                guards.append(s); goal_of.append(-1); goal_cost.append(0.0)
+            else:
+                status |= 1
+            continue
+        d2 = lambda g: (s[1] - guards[g][1]) * (s[1] - guards[g][1]) + (s[2] - guards[g][2]) * (s[2] - guards[g][2])
+        before = [g for g in visible if guards[g][0] < s[0]]
+        after = [g for g in visible if guards[g][0] > s[0]]
+        if not before or not after:
+            continue
+        g1, g2 = min(before, key=lambda g: (d2(g), g)), min(after, key=lambda g: (d2(g), g))
+        cand_len = length(guards[g1], s) + length(s, guards[g2])
+        A = _gs_polyline([guards[g1], s, guards[g2]], S)
+        for c in connectors:
+            if c[0] == g1 and c[1] == g2 and gs_equivalent(A, _gs_polyline([guards[g1], c[2], guards[g2]], S), guards[g1][0], guards[g2][0], opos):
+                if cand_len < c[3]:
+                    c[2], c[3] = s, cand_len
+                break
+        else:
+            if len(connectors) < GS_CONNECTORS:
+                connectors.append([g1, g2, s, cand_len])
+            else:
+                status |= 2
+    # the paths
+    kept = []                                                          # [cost, node list, polyline]
+
+    def consider(path, goal_guard):
+        nonlocal status
+        if len(path) > R:
+            status |= 8
+            return
+        acc = 0.0
+        for a, b in zip(path[:-1], path[1:]):
+            acc = acc + length(a, b)
+        cost = weight_length * acc + goal_cost[goal_guard]
+        line = _gs_polyline(path, S)
+        for kp in kept:
+            if gs_equivalent(line, kp[2], 0, N, opos):
+                if cost < kp[0]:
+                    kp[:] = [cost, path, line]
+                return
+        if len(kept) < GS_KEPT:
+            kept.append([cost, path, line])
+            return
+        worst = 0
+        for p in range(1, len(kept)):
+            if kept[p][0] >= kept[worst][0]:
+                worst = p
+        if cost < kept[worst][0]:
+            kept[worst] = [cost, path, line]
+
+    for g in range(1, len(guards)):
+        if goal_of[g] >= 0 and valid(guards[0], guards[g]):
+            consider([guards[0], guards[g]], g)
+    visits = 0
+
+    class _Stop(Exception):
+        pass
+
+    def descend(g, path):
+        nonlocal visits, status
+        for c in connectors:
+            if c[0] != g:
+                continue
+            if visits >= max_expansions:
+                status |= 4
+                raise _Stop()
+            visits += 1
+            longer = path + [c[2], guards[c[1]]]
+            if goal_of[c[1]] >= 0:
+                consider(longer, c[1])
+            else:
+                descend(c[1], longer)
+
+    try:
+        descend(0, [guards[0]])
+    except _Stop:
+        pass
+    # insertion by ascending cost, stable (a cost that is not a number stays where it is met)
+    order = []
+    for i in range(len(kept)):
+        j = len(order)
+        while j > 0 and kept[order[j - 1]][0] > kept[i][0]:
+            j -= 1
+        order.insert(j, i)
+    count = min(len(kept), P)
+    # class identity
+    n_prev, nxt = int(prev_count[0]), int(next_class[0])
+    if was_reset:
+        n_prev, nxt = 0, 0
+    n_prev = min(max(n_prev, 0), P)
+    shifted = []
+    for r in range(n_prev):
+        line = np.asarray(prev_traj[r], np.float64)[np.minimum(np.arange(S) + 1, N)].copy()
+        line[0] = (sx, sy)
+        shifted.append(line)
+    claimed, classes = set(), []
+    for i in range(count):
+        line = kept[order[i]][2]
+        for r in range(n_prev):
+            if r not in claimed and gs_equivalent(line, shifted[r], 0, N, opos):
+                classes.append(int(prev_class[r])); claimed.add(r)
+                break
+        else:
+            classes.append(nxt); nxt += 1
+    for i in range(P):
+        if i >= count:
+            node_count[i] = 0; topology_class[i] = -1; prev_class[i] = -1
+            continue
+        path = kept[order[i]][1]
+        for e, (k, x, y) in enumerate(path):
+            nodes[i][e] = (float(k) * dt, x, y)
+        node_count[i] = len(path); topology_class[i] = classes[i]; prev_class[i] = classes[i]
+        prev_traj[i] = kept[order[i]][2]
+    prev_count[0] = count; next_class[0] = nxt
+    return count, status
